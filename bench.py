@@ -12,24 +12,29 @@ per GPU B=16 patches of 192x192 (LR 96x96).  One step = one pass of the hot path
 
 Inputs are resident in HBM before the timed region.  value = HR patches/s over all ranks.
 
-ONE invocation measures BOTH arithmetic builds, each over exactly --steps timed steps after --warmup:
-  * top level of the JSON line: the **fp32 parity build** -- exact-fp32 MFMA (v_mfma_f32_32x32x2_f32), the
-    reference's own precision and the build every 1e-3 golden test runs; MFMA-bound (peak 157.3 TFLOP/s);
+A plain run times the headline alone: the **fp32 parity build** -- exact-fp32 MFMA (v_mfma_f32_32x32x2_f32), the
+reference's own precision and the build every 1e-3 golden test runs -- over exactly --steps timed steps after --warmup.
+``--dump-outputs DIR`` then writes what the last timed step computed (see dump_outputs).
+
+``--full`` adds everything else, each build over the same --steps after --warmup:
+  * top level of the JSON line: the fp32 parity build, as in a plain run; MFMA-bound (peak 157.3 TFLOP/s);
+  * ``split_build``: the bf16x3 build (fp32 tensors, trunk contractions on hi / lo bf16 operand pairs);
   * ``perf_build``: the **bf16 matrix-core build** (SURVEY 8d / BASELINE.json config 2 name bf16 for the perf
     configs; fp32 accumulate and statistics) -- HBM-bound, the regime the north star's 60 % target is stated in.
 Each record carries the roofline of the kernel with the LARGEST total time per step (trunk forward conv, trunk
-data-gradient conv and trunk weight gradient are probed live with HIP events on the launch stream) and a
-whole-step fraction (SURVEY 8d algorithmic flops / bytes over the measured step time).  ``cpu_baseline``: the
-oracle (CPU restatement, torch-CPU fp32) timed on this host's cores on the same batch (1 warm-up + best of 2 timed steps,
-~6 s each on a 16-core share); rank 0, N=1 only.
+data-gradient conv and trunk weight gradient are probed live with HIP events on the launch stream).  Every record, plain
+or full, carries a whole-step fraction (SURVEY 8d algorithmic flops / bytes over the measured step time).
+``cpu_baseline`` (--full): the oracle (CPU restatement, torch-CPU fp32) timed on this host's cores on the same batch
+(1 warm-up + best of 2 timed steps, ~6 s each on a 16-core share); rank 0, N=1 only.
 
-``configs`` (``--configs none`` skips it): BASELINE.json's configs 2-5 as iteration rates over all N ranks -- a full SRGAN
+``configs`` (--full; ``--configs none`` skips it): BASELINE.json's configs 2-5 as iteration rates over all N ranks -- a full SRGAN
 iteration (train.py:45-108: ONE G forward, D step on real + detached fake, G step through D and the VGG content
 extractor, both fused Adam steps; with N > 1 the gradient buckets of BOTH networks all-reduced from inside their backward
 schedules) of each config's networks at its sizes in the bf16 build, replayed from one segmented HIP graph, with the
 algorithmic flops / bytes of one iteration and the fractions of the MI355X peaks they amount to.  N = 1 times cfg2-cfg5; N > 1
 times the configs BASELINE.json calls "8xMI355X DP" (cfg3, cfg4, cfg5).  BASELINE.json's metric string reads "96^2 crops, x4":
 that workload is ``configs.cfg3``; the top-level value is the north star's headline (x2 generator, LR 96 -> SR 192).
+``--precision`` and ``--configs`` given explicitly select builds / configs in a plain run too.
 
 ``--gpus N`` with N > 1 starts the N rank processes itself (``torch.distributed.run``, one per GPU, rendezvous
 on 127.0.0.1) BEFORE anything touches the GPU, unless it already runs under such a launcher (WORLD_SIZE set).
@@ -101,7 +106,7 @@ def make_step(device, rank, world, use_graph, log):
         loss = 10.0 * torch.mean(torch.pow(hr - fake, 2))
         net.zero_grad(set_to_none=True)
         loss.backward()          # with a reducer: every finished bucket is announced from inside the backward pass
-        return loss
+        return loss, fake.detach()
 
     graphed = None
     if use_graph:
@@ -121,20 +126,38 @@ def make_step(device, rank, world, use_graph, log):
 
     def step():
         if graphed is not None:
-            loss = graphed()
+            out = graphed()
             if reducer is not None:
                 reducer.launch_remaining()
         else:
-            loss = fwd_bwd()
+            out = fwd_bwd()
         if reducer is not None:
             reducer.finish()      # the compute stream waits for the side stream's reductions; no host sync
         opt.step()
-        return loss
+        return out
 
     return step, net, graphed is not None
 
 
-def timed_run(device, rank, world, precision, steps, warmup, use_graph, log):
+def dump_outputs(path, loss, sr, net):
+    """What a caller of the timed step receives from its last step, one DIR/<name>.npy each (float32; float64 for the
+    integer batch counters), ~18 MB in all: ``loss``, ``sr`` (the generator's output), ``state.<key>`` (every parameter and
+    buffer of the network after the Adam step) and ``grad.<name>`` (every parameter's gradient of that step)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {'loss': loss, 'sr': sr}
+    arrays.update(('state.' + k, v) for k, v in net.state_dict().items())
+    arrays.update(('grad.' + k, p.grad) for k, p in net.named_parameters() if p.grad is not None)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        t = t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()
+        np.save(os.path.join(path, name + '.npy'), t.numpy())
+
+
+def timed_run(device, rank, world, precision, steps, warmup, use_graph, log, dump=None):
+    """-> (seconds of the `steps` timed steps, HIP graph used, loss of the last step); `dump`: a directory the last step's
+    outputs are written to (dump_outputs)"""
     import torch
     import torch.distributed as dist
     sub('engine').set_precision(precision)
@@ -150,7 +173,7 @@ def timed_run(device, rank, world, precision, steps, warmup, use_graph, log):
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss = step()
+        loss, sr = step()
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -158,7 +181,9 @@ def timed_run(device, rank, world, precision, steps, warmup, use_graph, log):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = float(loss.item())
-    del step, net
+    if dump is not None:
+        dump_outputs(dump, loss, sr, net)
+    del step, net, sr
     torch.cuda.empty_cache()
     return dt, graphed, final_loss
 
@@ -601,17 +626,28 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='measure beyond the headline too: the bf16x3 and bf16 builds, per-kernel '
+                    'rooflines, the BASELINE.json configs and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write what the headline build's last timed step computed to DIR/<name>.npy")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU baseline out')
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend (nccl = RCCL; gloo for rehearsals)')
     ap.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly instead of replaying HIP graphs')
-    ap.add_argument('--precision', choices=['both', 'fp32', 'bf16x3', 'bf16'], default=os.environ.get('SISR_BENCH_PRECISION', 'both'),
-                    help='both (default): fp32 parity build at top level + bf16 build as perf_build; or one build only')
-    ap.add_argument('--configs', default='all', help="BASELINE.json configs timed as full SRGAN iteration rates over all ranks: "
-                    "'all' (N = 1: cfg2-cfg5; N > 1: cfg3-cfg5), 'none' or a comma list of cfg2,cfg3,cfg4,cfg5")
+    ap.add_argument('--precision', choices=['both', 'fp32', 'bf16x3', 'bf16'], default=os.environ.get('SISR_BENCH_PRECISION'),
+                    help='both (default with --full): fp32 parity build at top level + bf16x3 as split_build + bf16 as perf_build; '
+                    'or one build only (fp32: the default of a plain run)')
+    ap.add_argument('--configs', help="BASELINE.json configs timed as full SRGAN iteration rates over all ranks: "
+                    "'all' (the default with --full; N = 1: cfg2-cfg5; N > 1: cfg3-cfg5), 'none' (the default of a plain run) "
+                    "or a comma list of cfg2,cfg3,cfg4,cfg5")
     ap.add_argument('--config-iters', type=int, default=10)
     ap.add_argument('--dry-run-ranks', action='store_true',
                     help='launcher self-test: start the ranks, all-reduce a 1 over them and print the count (no GPU work)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if args.precision is None:
+        args.precision = 'both' if args.full else 'fp32'
+    if args.configs is None:
+        args.configs = 'all' if args.full else 'none'
 
     env_world = os.environ.get('WORLD_SIZE')
     if env_world is None and args.gpus > 1:
@@ -660,10 +696,14 @@ def main():
     records = {}
     for prec in builds:
         _fresh_allocator()
-        dt, graphed, final_loss = timed_run(device, rank, world, prec, args.steps, args.warmup, not args.no_graph, log)
+        dump = args.dump_outputs if rank == 0 and prec == builds[0] else None
+        dt, graphed, final_loss = timed_run(device, rank, world, prec, args.steps, args.warmup, not args.no_graph, log, dump)
         if rank == 0:
             ms = dt / args.steps * 1e3
-            roof, elt = kernel_rooflines(device, prec)
+            if args.full:
+                roof, elt = kernel_rooflines(device, prec)
+            else:
+                roof, elt = None, 2 if sub('engine').act_dtype() == torch.bfloat16 else 4
             records[prec] = {
                 'value': round(world * B * args.steps / dt, 2), 'unit': 'HR patches/s', 'ms_per_step': round(ms, 3),
                 'dtype': {'fp32': 'f32', 'bf16x3': 'bf16x3 (fp32 tensors; hi/lo bf16 MFMA operands, fp32 accumulate)', 'bf16': 'bf16'}[prec], 'steps': args.steps, 'warmup': args.warmup,
@@ -691,8 +731,10 @@ def main():
             'dtype': head['dtype'], 'data': 'synthetic',
             'config': {'workload': workload, 'per_gpu_batch': B, 'hr': HR, 'lr': LR, 'parallelism': 'dp%d' % world,
                        'hip_graph': head['hip_graph'], 'final_loss': head['final_loss']},
-            'roofline': head['roofline'], 'whole_step': head['whole_step'],
         }
+        if head['roofline'] is not None:                        # --full: the per-kernel probes
+            rec['roofline'] = head['roofline']
+        rec['whole_step'] = head['whole_step']
         if len(builds) == 3:
             rec['split_build'] = records['bf16x3']
             rec['perf_build'] = records['bf16']
@@ -712,13 +754,13 @@ def main():
         if rank == 0:
             rec['configs'] = cfg_recs
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             rec['cpu_baseline'] = cpu_baseline()
         # the numbers a truncated tail of this (long) line must still show, last
         rec['summary'] = {'value': rec['value'], 'unit': rec['unit'], 'ms_per_step': rec['ms_per_step'], 'dtype': rec['dtype'], 'n_gpus': world,
                           'perf_build_value': rec.get('perf_build', {}).get('value'), 'perf_build_ms_per_step': rec.get('perf_build', {}).get('ms_per_step'),
                           'configs_ms_per_iteration': {k: v.get('ms_per_iteration') for k, v in rec.get('configs', {}).items()},
-                          'roofline_frac': rec['roofline'].get('frac')}
+                          'roofline_frac': rec.get('roofline', {}).get('frac')}
         print(json.dumps(rec), flush=True)
     if world > 1:
         dist.destroy_process_group()

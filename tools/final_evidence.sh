@@ -8,7 +8,7 @@ cd $GRAFT_REPO_ROOT
 if [ "${3:-}" != nobench ]; then
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1 || { echo "smoke failed"; tail -3 $out/smoke.log; exit 1; }
     tail -3 $out/smoke.log
-    t0=$(date +%s); timeout -k 10 900 python bench.py > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail -3 $out/bench.err; exit 1; }
+    t0=$(date +%s); timeout -k 10 900 python bench.py --full > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail -3 $out/bench.err; exit 1; }
     echo "bench wall $(( $(date +%s) - t0 )) s"
 fi
 bash tools/evidence_stats.sh ${1:-final} || exit 1
