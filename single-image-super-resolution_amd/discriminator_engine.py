@@ -10,8 +10,6 @@ materialisation is the final 16 x fc_in flatten.  The data gradient of the strid
 four output-parity classes (stride-1 convs with 1/2/2/4 taps) -- no zero-stuffed work.  The FC
 layers stream their 75-302 MB weight exactly once per pass.
 """
-import os
-
 import torch
 
 from . import _lib as L
@@ -94,38 +92,18 @@ def run_backward(sv, grad_out, need_dx, sink=None, params=()):
     if not sv.training:
         raise NotImplementedError('backward through an eval-mode discriminator forward is not implemented')
     topo, P = sv.topo, sv.P
-    grads = {}
-    wg = E.WeightGradBatch()
-    pending = E.PendingSlabs()            # the layers' slab reductions wait for the flush: one launch instead of one per layer
-    wb = E.WgradDeepBatch()               # ... and so do the weight-gradient kernels of the 3x3 stack themselves (one launch per stride)
+    # the layers' slab reductions wait for the flush: one launch instead of one per layer ... and so do the weight-gradient kernels
+    # of the 3x3 stack themselves (one launch per stride), their slab sums in the SAME list: one reduction launch per eight jobs
+    book = E.BackwardBook(P, topo.conv_refs(), params, sink, own_batch_slabs=False)
+    grads, by_id, announced, flush, conv_bwd = book.grads, book.by_id, book.announced, book.flush, book.conv_bwd
     grad_out = grad_out.contiguous()
     n = sv.x.shape[0]
-    by_id = {id(p): p for p in params}
-    announced = set()
-    refs = topo.conv_refs()
-
-    def flush(tag):
-        """un-pack the weight gradients collected so far (one launch) and announce every new gradient to the sink"""
-        wb.run(pending)
-        pending.flush()
-        for ref_id, (gw, gb) in wg.run().items():
-            ref = next(r for r in refs if id(r) == ref_id)
-            if gw is not None:
-                grads[id(ref.weight)] = gw
-            if gb is not None:
-                grads[id(ref.bias)] = gb
-        wg.items = []
-        if sink is not None:
-            new = [k for k in grads if k not in announced and k in by_id]
-            announced.update(new)
-            sink.ready([(by_id[k], grads[k]) for k in new], tag)
-
     factored = None
     if sv.head:
         d1, dw2, db2, db1 = E.fc_head_backward(grad_out, sv.out, sv.h1, topo.fc2.weight, LEAKY)
         world = getattr(sink, 'world', 1) if sink is not None else 1
         if (world > 1 and getattr(sink, 'enabled', False) and hasattr(sink, 'gather') and id(topo.fc1.weight) in by_id
-                and E.fc_wgrad_rows_ok(world * n, sv.flat.shape[1], topo.fc1.weight.shape[0]) and os.environ.get('SISR_FC_FACTORED', '1') != '0'):
+                and E.fc_wgrad_rows_ok(world * n, sv.flat.shape[1], topo.fc1.weight.shape[0]) and E._on('SISR_FC_FACTORED')):
             # data-parallel: the 75-302 MB weight gradient is d1^T x, a rank-16 product -- the ranks exchange the two FACTORS (an
             # all-gather of N x 1.2-4.8 MB, issued now: it has the whole conv stack's backward to hide behind) and every rank forms
             # the MEAN gradient itself from all ranks' rows at the end of this schedule (same rows, same kernel: the same bits on
@@ -150,23 +128,6 @@ def run_backward(sv, grad_out, need_dx, sink=None, params=()):
         dflat = E.fc1_dgrad(d1, topo.fc1.weight)
     _, hl, wl, cl = sv.last_shape
     g = E.nchw_to_nhwc(dflat, dflat.shape[1], n, hl, wl, cl)              # grad wrt activated last map
-
-    def conv_bwd(ref, x_op, dy_op, need_dgrad=True, y_mode=L.Y_NHWC, bnb=None):
-        """weight gradient + data gradient; bnb = (x, consts, slope) names the BatchNorm (and the LeakyReLU behind it) the data
-        gradient arrives at: where the conv kernel can (conv_deep.hip), that BatchNorm's backward reductions come out of its
-        epilogue and (gradient, partial rows) is returned"""
-        p = P[id(ref)]
-        want_w, want_b = ref.weight.requires_grad, ref.bias is not None and ref.bias.requires_grad
-        if want_w or want_b:
-            red = wb.add(p, x_op, dy_op)
-            wg.add(p, red if red is not None else E.conv_wgrad(p, x_op, dy_op, defer=pending), want_w, want_b)
-        if not need_dgrad:
-            return None
-        if bnb is None:
-            return E.conv_dgrad(p, dy_op, y_mode=y_mode)
-        if E.can_fuse_bn_backward(p):
-            return E.conv_dgrad(p, dy_op, y_mode=y_mode, bnb=bnb)
-        return E.conv_dgrad(p, dy_op, y_mode=y_mode), None
 
     part, done = None, 0
     for i in range(len(topo.blocks) - 1, -1, -1):

@@ -7,7 +7,9 @@ leaky-relu slope (PReLU / LeakyReLU / ReLU) that its consumer applies while stag
 LDS, so BatchNorm / activation layers never make their own pass over HBM.
 """
 import ctypes as C
+import enum
 import os
+from collections import namedtuple
 
 import torch
 
@@ -17,6 +19,16 @@ from . import _lib as L
 # contraction on the bf16 matrix cores (fp32 accumulate, fp32 statistics) and keep their NHWC tensors as bf16 in HBM
 # (storage_bf16() below).
 PRECISION = os.environ.get('SISR_PRECISION', 'fp32')
+
+
+def _knob(name, default):
+    """an environment switch, read when it is used (tests set them between calls)"""
+    return os.environ.get(name, default)
+
+
+def _on(name):
+    """an on / off switch: on unless the environment says NAME=0"""
+    return os.environ.get(name, '1') != '0'
 
 
 def set_precision(p):
@@ -36,7 +48,7 @@ def storage_bf16():
     """bf16 build: NHWC activation / gradient tensors whose channel count is a multiple of 32 live in HBM as bf16
     (SURVEY 8d's bf16 bytes); arithmetic, accumulation and BatchNorm statistics stay fp32.  SISR_STORAGE=f32 keeps
     fp32 tensors with bf16 matrix-core operands (the earlier layout; A/B switch)."""
-    return PRECISION == 'bf16' and os.environ.get('SISR_STORAGE', 'bf16') != 'f32'
+    return PRECISION == 'bf16' and _knob('SISR_STORAGE', 'bf16') != 'f32'
 
 
 def act_dtype(channels=64):
@@ -61,6 +73,32 @@ def _copy_struct(s):
 
 def _align4(n):
     return (n + 3) & ~3
+
+
+def _slope(s):
+    """a leaky slope (device scalar tensor | float | None = identity) -> (device pointer | None, float) as the descriptors take it"""
+    if isinstance(s, torch.Tensor):
+        return s.data_ptr(), 1.0
+    return None, 1.0 if s is None else float(s)
+
+
+class Kind(enum.IntEnum):
+    """the kernel family one role (forward, data gradient, weight gradient) of a layer is planned for.  (An IntEnum from 0 so that
+    tests and tools may go on reading a kind as "runs on a bf16 kernel" by truth value.)"""
+    F32 = 0             # the exact-fp32 kernels (fp32 tensors; 'bf16x3' splits their operands)
+    BF16 = 1            # the generic bf16 kernels and the persistent trunk kernels behind the same entry point
+    DEEP = 2            # conv_deep.hip: split-K implicit GEMM with a weight image of its own
+    DEEP_S2X4 = 3       # conv_deep.hip, ONE launch over the four output-parity classes of a stride-2 data gradient
+
+    @property
+    def bf16(self):
+        """runs on a bf16-tensor kernel (the sisr_conv2d_bf16 / sisr_conv2d_wgrad_bf16 entry points)"""
+        return self != Kind.F32
+
+    @property
+    def deep(self):
+        """the conv_deep.hip family"""
+        return self in (Kind.DEEP, Kind.DEEP_S2X4)
 
 
 class Operand:
@@ -110,12 +148,18 @@ class Operand:
         setattr(d, names[8], self.pro)
         if not g and hasattr(d, 'x_out'):
             d.x_out = _ptr(self.x_out)
-        if isinstance(self.slope, torch.Tensor):
-            setattr(d, names[9], self.slope.data_ptr())
-            setattr(d, names[10], 1.0)
-        else:
-            setattr(d, names[9], None)
-            setattr(d, names[10], 1.0 if self.slope is None else float(self.slope))
+        for n, v in zip(names[9:], _slope(self.slope)):
+            setattr(d, n, v)
+
+
+def _conv_desc(n, h, w, cin, ho, wo, cout, kh, kw, stride, pad_y, pad_x, y_s=1, y_o=(0, 0), y_hw=None):
+    """a ConvDesc of this geometry whose output pixel (a, b) is stored at (y_s a + y_o[0], y_s b + y_o[1]) of a y_hw image"""
+    d = L.ConvDesc()
+    d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout = n, h, w, cin, ho, wo, cout
+    d.KH, d.KW, d.stride, d.pad_y, d.pad_x = kh, kw, stride, pad_y, pad_x
+    d.y_sy = d.y_sx = y_s
+    (d.y_oy, d.y_ox), (d.y_H, d.y_W) = y_o, y_hw or (ho, wo)
+    return d
 
 
 class ConvGeom:
@@ -137,7 +181,7 @@ class ConvGeom:
         """this role (0 forward, 1 data gradient) of the layer is planned for the split-K implicit-GEMM family (conv_deep.hip):
         bf16 tensors, 3x3, channels in 32s / 64s, no PixelShuffle store; the trunk geometry stays with the persistent trunk
         kernels wherever they take it (H % 8 == 0, W % 16 == 0)"""
-        if PRECISION != 'bf16' or not storage_bf16() or os.environ.get('SISR_DEEP', '1') == '0':
+        if PRECISION != 'bf16' or not storage_bf16() or not _on('SISR_DEEP'):
             return False
         if self.k != 3 or self.shuffle2:
             return False
@@ -145,7 +189,7 @@ class ConvGeom:
         if cin % 32 or cout % 64:
             return False
         trunk_shape = (self.cin == 64 and self.cout == 64 and self.stride == 1 and h % 8 == 0 and w % 16 == 0
-                       and os.environ.get('SISR_TRUNK', '1') != '0')
+                       and _on('SISR_TRUNK'))
         if trunk_shape and not (role == 1 and self.deep_dgrad):
             return False
         return True
@@ -159,30 +203,25 @@ class ConvGeom:
         hc, wc = (h - py + 1) // 2, (w - px + 1) // 2
         if khc == 0 or kwc == 0 or hc <= 0 or wc <= 0:
             return None
-        d = L.ConvDesc()
-        d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout = n, ho, wo, self.cout, hc, wc, self.cin
-        d.KH, d.KW, d.stride, d.pad_y, d.pad_x = khc, kwc, 1, pady, padx
-        d.y_sy = d.y_sx = 2
-        d.y_oy, d.y_ox, d.y_H, d.y_W = py, px, h, w
-        bf = PRECISION == 'bf16' and self.cout % 32 == 0 and lib.sisr_conv2d_plan_bf16(C.byref(d)) == 0
-        if not bf:
-            L.check(lib.sisr_conv2d_plan(C.byref(d)), 'sisr_conv2d_plan(dgrad stride-2 class)')
-        elif self._deep_ok(1, h, w) and lib.sisr_conv2d_deep_plan(C.byref(d), 0, 0 if self.light_backward else 128, 1) == 0:
-            bf = 2                                                    # conv_deep.hip
-        return (d, r0y, r0x, bf if bf == 2 else bool(bf))
+        d = _conv_desc(n, ho, wo, self.cout, hc, wc, self.cin, khc, kwc, 1, pady, padx, y_s=2, y_o=(py, px), y_hw=(h, w))
+        return S2Class(d, r0y, r0x, self._plan_conv(lib, d, 1, PRECISION == 'bf16', h, w, 'dgrad stride-2 class'))
+
+    def _plan_conv(self, lib, d, role, want_bf16, h, w, what):
+        """plan descriptor d (role 0 forward, 1 data gradient) for the best family that takes it -> Kind"""
+        if not (want_bf16 and d.Cin % 32 == 0 and lib.sisr_conv2d_plan_bf16(C.byref(d)) == 0):
+            L.check(lib.sisr_conv2d_plan(C.byref(d)), 'sisr_conv2d_plan(%s)' % what)
+            return Kind.F32
+        bn = 128 if role == 1 and not self.light_backward else 0
+        if self._deep_ok(role, h, w) and lib.sisr_conv2d_deep_plan(C.byref(d), 0, bn, 1) == 0:
+            return Kind.DEEP                                          # (its own weight image)
+        return Kind.BF16
 
     def _s2_deep_plan(self, lib, n, h, w, ho, wo):
         """stride-2 data gradient as ONE conv_deep.hip launch over the four output-parity classes (even sizes): -> (descriptor of
         the 2 x 2-tap class convolution, [(taps y, taps x, R0y, R0x)] per class c = 2 py + px) or None"""
-        if h % 2 or w % 2 or self.k != 3 or self.pad != 1 or not self._deep_ok(1, h, w) or os.environ.get('SISR_DEEP_S2X4', '1') == '0':
+        if h % 2 or w % 2 or self.k != 3 or self.pad != 1 or not self._deep_ok(1, h, w):
             return None
-        d = L.ConvDesc()
-        d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout = n, ho, wo, self.cout, h // 2, w // 2, self.cin
-        d.KH = d.KW = 2
-        d.stride, d.pad_y, d.pad_x = 1, 0, 0
-        d.y_sy = d.y_sx = 2
-        d.y_oy = d.y_ox = 0
-        d.y_H, d.y_W = h, w
+        d = _conv_desc(n, ho, wo, self.cout, h // 2, w // 2, self.cin, 2, 2, 1, 0, 0, y_s=2, y_hw=(h, w))
         if (ho, wo) != (h // 2, w // 2) or lib.sisr_conv2d_plan_bf16(C.byref(d)) != 0:
             return None
         if lib.sisr_conv2d_deep_plan(C.byref(d), 0, 0 if self.light_backward else 128, 4) != 0:
@@ -193,84 +232,86 @@ class ConvGeom:
                 khc, pady, r0y = _s2_taps(self.k, self.pad, py)
                 kwc, padx, r0x = _s2_taps(self.k, self.pad, px)
                 assert pady == 0 and padx == 0 and khc <= 2 and kwc <= 2
-                cls.append((khc, kwc, r0y, r0x))
+                cls.append(S2Taps(khc, kwc, r0y, r0x))
         return d, cls
 
-    def plans(self, n, h, w, max_pixel_blocks=None):
-        """-> (fwd desc, dgrad desc | [4 class descs] | None, wgrad desc, kinds) where kinds =
-        (fwd_bf16, dgrad_bf16, wgrad_bf16) tells which kernel family each template was planned for."""
-        if max_pixel_blocks is None:
-            max_pixel_blocks = int(os.environ.get('SISR_WGRAD_PIXEL_BLOCKS', '512'))      # A/B knob of the wgrad grids
-        key = (n, h, w, PRECISION, storage_bf16(), max_pixel_blocks, os.environ.get('SISR_DEEP', '1'), os.environ.get('SISR_WGRAD_DEEP', '1'),
-               os.environ.get('SISR_WGRAD_DEEP_PB', ''))
+    def plans(self, n, h, w, max_pixel_blocks=512):
+        """-> (fwd desc, dgrad desc | S2x4 | [4 x S2Class | None], wgrad desc, kinds) where kinds = (forward, data gradient, weight
+        gradient) names the Kind each template was planned for.  (The four-class list reports Kind.F32 whatever its classes run on:
+        each S2Class carries its own kind.)"""
+        key = (n, h, w, PRECISION, storage_bf16(), max_pixel_blocks, _knob('SISR_DEEP', '1'), _knob('SISR_WGRAD_DEEP', '1'),
+               _knob('SISR_WGRAD_DEEP_PB', ''))
         if key in self._plans:
             return self._plans[key]
         lib = L.lib()
         ho, wo = self.out_hw(h, w)
-        f = L.ConvDesc()
-        f.N, f.H, f.W, f.Cin, f.Ho, f.Wo, f.Cout = n, h, w, self.cin, ho, wo, self.cout
-        f.KH = f.KW = self.k
-        f.stride, f.pad_y, f.pad_x = self.stride, self.pad, self.pad
-        f.y_sy = f.y_sx = 1
-        f.y_oy = f.y_ox = 0
-        f.y_H, f.y_W = ho, wo
+        f = _conv_desc(n, h, w, self.cin, ho, wo, self.cout, self.k, self.k, self.stride, self.pad, self.pad)
         f.y_mode = L.Y_SHUFFLE2 if self.shuffle2 else L.Y_NHWC
         want_bf16 = PRECISION == 'bf16' and self.k * self.k <= 9
-        f_bf = want_bf16 and self.cin % 32 == 0 and lib.sisr_conv2d_plan_bf16(C.byref(f)) == 0
-        if not f_bf:
-            L.check(lib.sisr_conv2d_plan(C.byref(f)), 'sisr_conv2d_plan(fwd)')
-        elif self._deep_ok(0, h, w) and lib.sisr_conv2d_deep_plan(C.byref(f), 0, 0, 1) == 0:
-            f_bf = 2                                                  # kind 2: conv_deep.hip (its own weight image)
-        d = None
-        d_bf = False
+        f_kind = self._plan_conv(lib, f, 0, want_bf16, h, w, 'fwd')
+        d_kind = Kind.F32
         if self.stride == 1:
-            d = L.ConvDesc()      # data gradient: conv over dy with flipped taps, roles swapped
-            d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout = n, ho, wo, self.cout, h, w, self.cin
-            d.KH = d.KW = self.k
-            d.stride = 1
-            d.pad_y = d.pad_x = self.k - 1 - self.pad
-            d.y_sy = d.y_sx = 1
-            d.y_H, d.y_W = h, w
-            d_bf = want_bf16 and self.cout % 32 == 0 and lib.sisr_conv2d_plan_bf16(C.byref(d)) == 0
-            if not d_bf:
-                L.check(lib.sisr_conv2d_plan(C.byref(d)), 'sisr_conv2d_plan(dgrad)')
-            elif self._deep_ok(1, h, w) and lib.sisr_conv2d_deep_plan(C.byref(d), 0, 0 if self.light_backward else 128, 1) == 0:
-                d_bf = 2
+            pad = self.k - 1 - self.pad      # data gradient: conv over dy with flipped taps, roles swapped
+            d = _conv_desc(n, ho, wo, self.cout, h, w, self.cin, self.k, self.k, 1, pad, pad)
+            d_kind = self._plan_conv(lib, d, 1, want_bf16, h, w, 'dgrad')
         else:
             x4 = self._s2_deep_plan(lib, n, h, w, ho, wo) if want_bf16 else None
             if x4 is not None:
-                d, d_bf = S2x4(*x4), 3                               # kind 3: one launch over the four parity classes
+                d, d_kind = S2x4(*x4), Kind.DEEP_S2X4
             else:
                 d = [self._s2_class_plan(lib, n, h, w, ho, wo, py, px) for py in (0, 1) for px in (0, 1)]
         g = L.WgradDesc()
         g.N, g.H, g.W, g.Cin, g.Ho, g.Wo, g.Cout = n, h, w, self.cin, ho, wo, self.cout
         g.KH = g.KW = self.k
         g.stride, g.pad_y, g.pad_x = self.stride, self.pad, self.pad
-        g_bf = False
+        g_kind = Kind.F32
         if want_bf16 and self.cin % 32 == 0:
             # few-channel outputs (the generator's 3-channel last conv): the bf16 kernel runs on the gradient
             # image padded to 4 channels (conv_wgrad materialises it), 16x the exact-fp32 matrix rate
             g.Cout = (self.cout + 3) // 4 * 4 if self.cout < 32 else self.cout
-            g_bf = g.Cout % 4 == 0 and lib.sisr_wgrad_plan_bf16(C.byref(g), max_pixel_blocks) == 0
-            if g_bf and self.k == 3 and self.pad == 1:
-                lib.sisr_wgrad_deep_plan(C.byref(g), 0)               # 3x3, channels in 64s: wgrad_deep.hip (g.deep.enabled)
-        if not g_bf:
+            if g.Cout % 4 == 0 and lib.sisr_wgrad_plan_bf16(C.byref(g), max_pixel_blocks) == 0:
+                g_kind = Kind.BF16
+                if self.k == 3 and self.pad == 1:
+                    lib.sisr_wgrad_deep_plan(C.byref(g), 0)           # 3x3, channels in 64s: wgrad_deep.hip (g.deep.enabled)
+        if g_kind == Kind.F32:
             g.Cout = self.cout
             L.check(lib.sisr_wgrad_plan(C.byref(g), max_pixel_blocks), 'sisr_wgrad_plan')
         g.slab_stride = g.slab_elems + g.CoutPad
-        self._plans[key] = (f, d, g, (f_bf if f_bf == 2 else bool(f_bf), d_bf if d_bf in (2, 3) else bool(d_bf), bool(g_bf)))
+        self._plans[key] = (f, d, g, (f_kind, d_kind, g_kind))
         return self._plans[key]
+
+
+# one output-parity class c = 2 py + px of a stride-2 data gradient: as a stride-1 conv of its own (descriptor, Kind), or as its taps
+# inside an S2x4 launch.  Forward tap (r, s) of class tap (r', s') is (r0y - 2 r', r0x - 2 s').
+S2Class = namedtuple('S2Class', 'desc r0y r0x kind')
+S2Taps = namedtuple('S2Taps', 'kh kw r0y r0x')
 
 
 class S2x4:
     """the data gradient of a stride-2 layer planned as one conv_deep.hip launch over its four output-parity classes"""
 
     def __init__(self, desc, classes):
-        self.desc, self.classes = desc, classes          # classes[c] = (taps y, taps x, R0y, R0x), c = 2 py + px
+        self.desc, self.classes = desc, classes          # classes[c]: S2Taps, c = 2 py + px
 
     def image_slots(self, c, cout_fwd, cin_fwd):
         """fp32 slots of class c's weight image [cout_fwd / 32][taps y][cin_fwd][2 * 32 + 8] bf16 (KW = 2 row format)"""
-        return ((cout_fwd // 32) * self.classes[c][0] * cin_fwd * 72 + 1) // 2
+        return ((cout_fwd // 32) * self.classes[c].kh * cin_fwd * 72 + 1) // 2
+
+
+DG_NONE, DG_CONV, DG_CLASSES, DG_X4 = 'none', 'conv', 'classes', 'x4'
+
+
+def _dgrad_shape(d):
+    """which of its shapes a data-gradient plan (ConvGeom.plans()[1]) has: DG_CONV one stride-1 conv, DG_X4 an S2x4, DG_CLASSES four
+    S2Class | None, DG_NONE nothing planned"""
+    if d is None or isinstance(d, S2x4):
+        return DG_NONE if d is None else DG_X4
+    return DG_CLASSES if isinstance(d, list) else DG_CONV
+
+
+def _all_deep(classes):
+    """every one of the four classes exists and runs on conv_deep.hip (whose epilogue can emit BatchNorm-backward partial rows)"""
+    return all(c is not None and c.kind == Kind.DEEP for c in classes)
 
 
 def _s2_taps(k, pad, parity):
@@ -297,33 +338,33 @@ class Prepared:
 def _trunk_ldsimg(gm, plan_f, plan_d, kinds):
     """(forward, data-gradient) mode of the LDS-order weight image of the fp32-tensor trunk conv (SisrWeightDesc.f_ldsimg /
     d_ldsimg): 0 none, 1 fp32 values, 2 split pairs -- for 3x3 64 -> 64 convs on the fp32 kernels"""
-    if os.environ.get('SISR_TRUNK_LDSIMG', '1') == '0' or gm.k != 3 or gm.cin != 64 or gm.cout != 64 or gm.stride != 1:
+    if gm.k != 3 or gm.cin != 64 or gm.cout != 64 or gm.stride != 1:
         return 0, 0
     mode = 2 if mfma_split() else 1
-    okf = not kinds[0] and plan_f.plan.CK == 32 and plan_f.plan.CoutPad == 64 and plan_f.plan.n_chunk == 2
-    okd = (plan_d is not None and not isinstance(plan_d, list) and not kinds[1] and plan_d.plan.CK == 32
-           and plan_d.plan.CoutPad == 64 and plan_d.plan.n_chunk == 2)
-    return (mode if okf else 0), (mode if okd else 0)
+
+    def ok(desc, kind):
+        return kind == Kind.F32 and desc.plan.CK == 32 and desc.plan.CoutPad == 64 and desc.plan.n_chunk == 2
+    return (mode if ok(plan_f, kinds[0]) else 0), (mode if _dgrad_shape(plan_d) == DG_CONV and ok(plan_d, kinds[1]) else 0)
 
 
 def _trunk_lanes(gm, plan_f, plan_d, kinds):
     """(forward, data-gradient): the bf16 weight buffer also gets the lane-order image of the persistent trunk kernels
     (SisrWeightDesc.bf_f_lanes / bf_d_lanes) -- only where those kernels can take the layer: 3x3, stride 1, 64 input channels,
-    64 couts (or the 256 of the upscale conv) on the generic bf16 family (kind True, not the deep family's 2)"""
-    if os.environ.get('SISR_TRUNK_LANES', '1') == '0' or gm.k != 3 or gm.stride != 1:
+    64 couts (or the 256 of the upscale conv) on the generic bf16 family (Kind.BF16, not the deep family)"""
+    if gm.k != 3 or gm.stride != 1:
         return False, False
-    lf = kinds[0] is True and gm.cin == 64 and plan_f.plan.CK == 32 and plan_f.plan.CoutPad in (64, 256)
-    ld = (kinds[1] is True and plan_d is not None and not isinstance(plan_d, list) and gm.cout == 64 and gm.cin == 64
+    lf = kinds[0] == Kind.BF16 and gm.cin == 64 and plan_f.plan.CK == 32 and plan_f.plan.CoutPad in (64, 256)
+    ld = (kinds[1] == Kind.BF16 and _dgrad_shape(plan_d) == DG_CONV and gm.cout == 64 and gm.cin == 64
           and plan_d.plan.CK == 32 and plan_d.plan.CoutPad == 64)
     return lf, ld
 
 
 def _img_slots(desc, kind, lanes=False, ldsimg=0):
-    """fp32 slots of one packed weight image: kind 2 = conv_deep.hip's bf16 image, True = the generic bf16 image (twice with the
-    lane-order copy), False = the fp32 image (plus the LDS-order copy)"""
-    if kind == 2:
+    """fp32 slots of one packed weight image: conv_deep.hip's bf16 image, the generic bf16 image (twice with the lane-order copy)
+    or the fp32 image (plus the LDS-order copy)"""
+    if kind == Kind.DEEP:
         return (desc.deep.wimg_elems + 1) // 2
-    if kind:
+    if kind == Kind.BF16:
         return ((desc.plan.wpk_elems + 1) // 2) * (2 if lanes else 1)
     return desc.plan.wpk_elems + (L.WLDS_WORDS if ldsimg else 0)
 
@@ -339,161 +380,165 @@ def invalidate_weight_caches():
     _WEIGHT_EPOCH[0] += 1
 
 
+def _layout_weights(items, need_dgrad):
+    """Host-only pass of prepare_weights (no device call): per layer a Prepared with plans, kinds, lanes, ldsimg and offs[i] =
+    (forward image, data-gradient image(s) | None, sigma block, power-iteration scratch): an image is (buffer, offset, slots),
+    the last two are offsets into 's'.  sizes: fp32 slots of 'b' (images rebuilt on every call), 'd' (conv_deep.hip's), 's'."""
+    sizes = {'b': 0, 'd': 0, 's': 0}
+
+    def take(buf, n):
+        off = sizes[buf]
+        sizes[buf] += n
+        return (buf, off, n)
+
+    def image(desc, kind, lanes=False, ldsimg=0):
+        return take('d' if kind == Kind.DEEP else 'b', _align4(_img_slots(desc, kind, lanes, ldsimg)))
+    preps, offs = [], []
+    for ref, n, h, w in items:
+        gm = ref.geom
+        p = Prepared()
+        f, d, g, p.kinds = gm.plans(n, h, w)
+        p.ref, p.plans = ref, (f, d, g)
+        p.lanes = _trunk_lanes(gm, f, d, p.kinds)
+        p.ldsimg = _trunk_ldsimg(gm, f, d, p.kinds)
+        off_f = image(f, p.kinds[0], p.lanes[0], p.ldsimg[0])
+        shape = _dgrad_shape(d) if need_dgrad else DG_NONE
+        off_d = None
+        if shape == DG_X4:
+            off_d = [take('d', _align4(d.image_slots(c, gm.cout, gm.cin))) for c in range(4)]
+        elif shape == DG_CLASSES:
+            off_d = [None if c is None else image(c.desc, c.kind) for c in d]
+        elif shape == DG_CONV:
+            off_d = image(d, p.kinds[1], p.lanes[1], p.ldsimg[1])
+        rows, cols = gm.cout, gm.cin * gm.k * gm.k
+        sn = ref.u is not None
+        off_s = take('s', 4 + (_align4(rows) + _align4(cols) if sn else 0))[1]
+        off_w = take('s', _align4((rows + 15) // 16 * cols + rows) if sn else 0)[1]     # power-iteration scratch: [ceil(rows/16)][cols] + [rows]
+        preps.append(p)
+        offs.append((off_f, off_d, off_s, off_w))
+    return preps, offs, sizes
+
+
+# SisrWeightDesc fields of the two whole-conv roles: (deep image, bf16 image, prefix of its CoutPad / CK / lanes, fp32 image,
+# its LDS-order mode, prefix of its plan fields)
+_ROLE_FIELDS = (('wdp_fwd', 'wbf_fwd', 'bf_f_', 'wpk_fwd', 'f_ldsimg', 'f_'),
+                ('wdp_dgrad', 'wbf_dgrad', 'bf_d_', 'wpk_dgrad', 'd_ldsimg', 'd_'))
+_PLAN_FIELDS = ('CK', 'PS', 'KROWP', 'n_chunk', 'CoutPad')
+
+
+def _fill_role(t, role, desc, kind, image, lanes, ldsimg, deep_hit):
+    """the image of one whole-conv role (0 forward, 1 stride-1 data gradient) -> it is a conv_deep.hip image"""
+    wdp, wbf, bf, wpk, lds, pl = _ROLE_FIELDS[role]
+    if kind == Kind.DEEP:
+        vals = () if deep_hit else ((wdp, image.data_ptr()),)
+    elif kind == Kind.BF16:
+        vals = ((wbf, image.data_ptr()), (bf + 'CoutPad', desc.plan.CoutPad), (bf + 'CK', desc.plan.CK), (bf + 'lanes', int(lanes)))
+    else:
+        vals = ((wpk, image.data_ptr()), (lds, ldsimg)) + tuple((pl + n, getattr(desc.plan, n)) for n in _PLAN_FIELDS)
+    for n, v in vals:
+        setattr(t, n, v)
+    return kind == Kind.DEEP
+
+
+def _fill_classes(t, classes, images, deep_hit):
+    """the images of a stride-2 data gradient's four parity classes -> any is a conv_deep.hip image"""
+    has_deep = False
+    for ci, (c, buf) in enumerate(zip(classes, images)):
+        if c is None:
+            continue
+        t.c_KH[ci], t.c_KW[ci], t.c_R0y[ci], t.c_R0x[ci] = c.desc.KH, c.desc.KW, c.r0y, c.r0x
+        if c.kind == Kind.DEEP:
+            has_deep = True
+            if not deep_hit:
+                t.wdp_dcls[ci] = buf.data_ptr()
+        elif c.kind == Kind.BF16:
+            t.wbf_dcls[ci], t.bf_c_CoutPad[ci] = buf.data_ptr(), c.desc.plan.CoutPad
+        else:
+            t.wpk_dcls[ci] = buf.data_ptr()
+            for n in _PLAN_FIELDS:
+                getattr(t, 'c_' + n)[ci] = getattr(c.desc.plan, n)
+    return has_deep
+
+
+def _fill_weight_desc(t, p, off, bufs, training, deep_hit):
+    """SisrWeightDesc `t` of one layer and the views of its Prepared `p`, from its layout record and the base tensors bufs['b' | 'd'
+    | 's'].  deep_hit: the conv_deep.hip images are cached: not packed again (null pointers).  -> the layer has such an image"""
+    off_f, off_d, off_s, off_w = off
+    ref, gm, (f, d, _) = p.ref, p.ref.geom, p.plans
+    sm = bufs['s']
+
+    def view(o):
+        return None if o is None else bufs[o[0]][o[1]:o[1] + o[2]]
+    shape = _dgrad_shape(d) if off_d is not None else DG_NONE      # (need_dgrad=False: no data-gradient image is packed)
+    p.wpk_fwd = view(off_f)
+    p.wpk_dgrad = [view(o) for o in off_d] if shape in (DG_X4, DG_CLASSES) else view(off_d)
+    p.sigma = sm[off_s:off_s + 1]
+    p.inv_sigma = sm[off_s + 1:off_s + 2]          # written next to sigma: the conv_deep.hip epilogue scale
+    t.w_orig, t.sigma, t.wdp_scaled = ref.weight.data_ptr(), p.sigma.data_ptr(), 0
+    t.Cout, t.Cin, t.KH, t.KW = gm.cout, gm.cin, gm.k, gm.k
+    t.training, t.shuffle2 = int(training), int(gm.shuffle2)
+    has_deep = _fill_role(t, 0, f, p.kinds[0], p.wpk_fwd, p.lanes[0], p.ldsimg[0], deep_hit)
+    if shape == DG_X4:
+        has_deep = True
+        t.wdp_cls_kw = 2
+        for ci, (taps, buf) in enumerate(zip(d.classes, p.wpk_dgrad)):
+            t.c_KH[ci], t.c_KW[ci], t.c_R0y[ci], t.c_R0x[ci] = taps
+            if not deep_hit:
+                t.wdp_dcls[ci] = buf.data_ptr()
+    elif shape == DG_CLASSES:
+        has_deep |= _fill_classes(t, d, p.wpk_dgrad, deep_hit)
+    elif shape == DG_CONV:
+        has_deep |= _fill_role(t, 1, d, p.kinds[1], p.wpk_dgrad, p.lanes[1], p.ldsimg[1], deep_hit)
+    p.u_used = p.v_used = None
+    if ref.u is not None:
+        rows, cols = gm.cout, gm.cin * gm.k * gm.k
+        t.sn_work = sm[off_w:].data_ptr()
+        p.u_used = sm[off_s + 4:off_s + 4 + rows]
+        p.v_used = sm[off_s + 4 + _align4(rows):off_s + 4 + _align4(rows) + cols]
+        t.u, t.v = ref.u.data_ptr(), ref.v.data_ptr()
+        t.u_used, t.v_used = p.u_used.data_ptr(), p.v_used.data_ptr()
+    return has_deep
+
+
 def prepare_weights(items, training, need_dgrad=True, cache=None):
     """items: [(ConvRef, n, h, w)].  Spectral-norm power iteration (in place on u/v when training), sigma, and the packed images
     for fwd and dgrad.  Images of the generic / trunk kernels hold W / sigma and are rebuilt on every call; the conv_deep.hip
-    images (kind 2) hold W_orig itself -- those kernels apply 1 / sigma in their epilogue (Prepared.inv_sigma) -- so with `cache`
+    images (Kind.DEEP) hold W_orig itself -- those kernels apply 1 / sigma in their epilogue (Prepared.inv_sigma) -- so with `cache`
     (a dict owned by the module) they are packed once per optimizer step, not once per forward: the discriminator runs three
     forwards per SRGAN iteration, two of them on unchanged weights (train.py:132,156,174)."""
     lib = L.lib()
     dev = items[0][0].weight.device
-    total, dtotal, small = 0, 0, 0
-    metas = []
-
-    def alloc(desc, kind, lanes=False, ldsimg=0):
-        nonlocal total, dtotal
-        n_ = _align4(_img_slots(desc, kind, lanes, ldsimg))
-        if kind == 2:
-            off = ('d', dtotal, n_)
-            dtotal += n_
-        else:
-            off = ('b', total, n_)
-            total += n_
-        return off
-    for ref, n, h, w in items:
-        f, d, g, kinds = ref.geom.plans(n, h, w)
-        lanes = _trunk_lanes(ref.geom, f, d, kinds)
-        ldsimg = _trunk_ldsimg(ref.geom, f, d, kinds)
-        off_f = alloc(f, kinds[0], lanes[0], ldsimg[0])
-        off_d = None
-        if need_dgrad and isinstance(d, S2x4):
-            off_d = []
-            for c in range(4):
-                n_ = _align4(d.image_slots(c, ref.geom.cout, ref.geom.cin))
-                off_d.append(('d', dtotal, n_))
-                dtotal += n_
-        elif need_dgrad and isinstance(d, list):
-            off_d = [None if cls is None else alloc(cls[0], cls[3]) for cls in d]
-        elif need_dgrad and d is not None:
-            off_d = alloc(d, kinds[1], lanes[1], ldsimg[1])
-        off_s = small
-        rows_, cols_ = ref.geom.cout, ref.geom.cin * ref.geom.k * ref.geom.k
-        small += 4 + (_align4(rows_) + _align4(cols_) if ref.u is not None else 0)
-        off_w = small                              # power-iteration scratch: [ceil(rows/16)][cols] + [rows]
-        small += _align4((rows_ + 15) // 16 * cols_ + rows_) if ref.u is not None else 0
-        metas.append((off_f, off_d, off_s, off_w))
-    big = torch.empty(total, dtype=torch.float32, device=dev)
-    sm = torch.empty(small, dtype=torch.float32, device=dev)
-    deep_hit = False
-    deep = None
-    if dtotal:
-        key = (_WEIGHT_EPOCH[0], dtotal, need_dgrad, torch.cuda.is_current_stream_capturing(),
+    preps, offs, sizes = _layout_weights(items, need_dgrad)
+    big = torch.empty(sizes['b'], dtype=torch.float32, device=dev)
+    sm = torch.empty(sizes['s'], dtype=torch.float32, device=dev)
+    deep, deep_hit = None, False
+    if sizes['d']:
+        key = (_WEIGHT_EPOCH[0], sizes['d'], need_dgrad, torch.cuda.is_current_stream_capturing(),
                tuple((id(ref.weight), ref.weight.data_ptr(), ref.weight._version, n, h, w) for ref, n, h, w in items))
-        if cache is not None and cache.get('key') == key and os.environ.get('SISR_WCACHE', '1') != '0':
+        if cache is not None and cache.get('key') == key:
             deep, deep_hit = cache['deep'], True
         else:
-            deep = torch.empty(dtotal, dtype=torch.float32, device=dev)
+            deep = torch.empty(sizes['d'], dtype=torch.float32, device=dev)
             if cache is not None:
                 cache['key'], cache['deep'] = key, deep
-
-    def view(off):
-        return None if off is None else (deep if off[0] == 'd' else big)[off[1]:off[1] + off[2]]
+    bufs = {'b': big, 'd': deep, 's': sm}
     table = (L.WeightDesc * len(items))()
-    out = []
     max_rows = max_cols = 1
     deep_cout = deep_cin = 0
-    for i, ((ref, n, h, w), (off_f, off_d, off_s, off_w)) in enumerate(zip(items, metas)):
-        f, d, g, kinds = ref.geom.plans(n, h, w)
-        gm = ref.geom
-        p = Prepared()
-        p.ref, p.plans, p.kinds = ref, (f, d, g), kinds
-        p.lanes = _trunk_lanes(gm, f, d, kinds)
-        p.ldsimg = _trunk_ldsimg(gm, f, d, kinds)
-        p.wpk_fwd = view(off_f)
-        p.wpk_dgrad = [view(o) for o in off_d] if isinstance(off_d, list) else view(off_d)
-        p.sigma = sm[off_s:off_s + 1]
-        p.inv_sigma = sm[off_s + 1:off_s + 2]          # written next to sigma: the conv_deep.hip epilogue scale
-        t = table[i]
-        t.w_orig = ref.weight.data_ptr()
-        t.sigma = p.sigma.data_ptr()
-        t.wdp_scaled = 0
-        has_deep = False
-        if kinds[0] == 2:
-            has_deep = True
-            if not deep_hit:
-                t.wdp_fwd = p.wpk_fwd.data_ptr()
-        elif kinds[0]:
-            t.wbf_fwd, t.bf_f_CoutPad, t.bf_f_CK = p.wpk_fwd.data_ptr(), f.plan.CoutPad, f.plan.CK
-            t.bf_f_lanes = int(p.lanes[0])
-        else:
-            t.wpk_fwd = p.wpk_fwd.data_ptr()
-            t.f_ldsimg = p.ldsimg[0]
-        if kinds[1] == 3:
-            if off_d is not None:
-                has_deep = True
-                t.wdp_cls_kw = 2
-                for ci, ((khc, kwc, r0y, r0x), buf) in enumerate(zip(d.classes, p.wpk_dgrad)):
-                    t.c_KH[ci], t.c_KW[ci], t.c_R0y[ci], t.c_R0x[ci] = khc, kwc, r0y, r0x
-                    if not deep_hit:
-                        t.wdp_dcls[ci] = buf.data_ptr()
-        elif kinds[1] == 2:
-            if off_d is not None:
-                has_deep = True
-                if not deep_hit:
-                    t.wdp_dgrad = p.wpk_dgrad.data_ptr()
-        elif kinds[1]:
-            if off_d is not None:                                     # (need_dgrad=False: no data-gradient image is packed)
-                t.wbf_dgrad, t.bf_d_CoutPad, t.bf_d_CK = p.wpk_dgrad.data_ptr(), d.plan.CoutPad, d.plan.CK
-                t.bf_d_lanes = int(p.lanes[1])
-        else:
-            t.wpk_dgrad = None if isinstance(p.wpk_dgrad, list) else _ptr(p.wpk_dgrad)
-            t.d_ldsimg = p.ldsimg[1] if (off_d is not None and not isinstance(off_d, list)) else 0
-        t.Cout, t.Cin, t.KH, t.KW = gm.cout, gm.cin, gm.k, gm.k
-        t.training, t.shuffle2 = int(training), int(gm.shuffle2)
-        t.f_CK, t.f_PS, t.f_KROWP, t.f_n_chunk, t.f_CoutPad = (f.plan.CK, f.plan.PS, f.plan.KROWP,
-                                                                 f.plan.n_chunk, f.plan.CoutPad)
-        if isinstance(off_d, list) and not isinstance(d, S2x4):
-            for ci, (cls, buf) in enumerate(zip(d, p.wpk_dgrad)):
-                if cls is None:
-                    continue
-                cd, r0y, r0x, cbf = cls
-                t.c_KH[ci], t.c_KW[ci], t.c_R0y[ci], t.c_R0x[ci] = cd.KH, cd.KW, r0y, r0x
-                if cbf == 2:
-                    has_deep = True
-                    if not deep_hit:
-                        t.wdp_dcls[ci] = buf.data_ptr()
-                    continue
-                if cbf:
-                    t.wbf_dcls[ci], t.bf_c_CoutPad[ci] = buf.data_ptr(), cd.plan.CoutPad
-                    continue
-                t.wpk_dcls[ci] = buf.data_ptr()
-                t.c_CK[ci], t.c_PS[ci], t.c_KROWP[ci] = cd.plan.CK, cd.plan.PS, cd.plan.KROWP
-                t.c_n_chunk[ci], t.c_CoutPad[ci] = cd.plan.n_chunk, cd.plan.CoutPad
-        elif off_d is not None and not kinds[1]:
-            t.d_CK, t.d_PS, t.d_KROWP, t.d_n_chunk, t.d_CoutPad = (d.plan.CK, d.plan.PS, d.plan.KROWP,
-                                                                     d.plan.n_chunk, d.plan.CoutPad)
-        if has_deep:
+    for t, p, off in zip(table, preps, offs):
+        gm = p.ref.geom
+        if _fill_weight_desc(t, p, off, bufs, training, deep_hit):
             deep_cout, deep_cin = max(deep_cout, gm.cout), max(deep_cin, gm.cin)
-        p.u_used = p.v_used = None
         max_rows, max_cols = max(max_rows, gm.cout), max(max_cols, gm.cin * gm.k * gm.k)
-        if ref.u is not None:
-            rows, cols = gm.cout, gm.cin * gm.k * gm.k
-            t.sn_work = sm[off_w:].data_ptr()
-            p.u_used = sm[off_s + 4:off_s + 4 + rows]
-            p.v_used = sm[off_s + 4 + _align4(rows):off_s + 4 + _align4(rows) + cols]
-            t.u, t.v = ref.u.data_ptr(), ref.v.data_ptr()
-            t.u_used, t.v_used = p.u_used.data_ptr(), p.v_used.data_ptr()
-        out.append(p)
     tab_dev = _table_to_device(table, dev)
-    any_sn = any(ref.u is not None for ref, _, _, _ in items)
     # sigma must exist before any image that holds W / sigma is packed; weights without spectral norm get sigma = 1 from the
     # finishing kernel of the power iteration (one workgroup per weight) -- skipped only when nothing but cached images is left
     L.check(lib.sisr_weights_sn(tab_dev.data_ptr(), len(items), max_rows, max_cols, _stream()), 'sisr_weights_sn')
-    if total:
+    if sizes['b']:
         L.check(lib.sisr_weights_pack(tab_dev.data_ptr(), len(items), max_rows, max_cols, _stream()), 'sisr_weights_pack')
-    if dtotal and not deep_hit:
+    if sizes['d'] and not deep_hit:
         L.check(lib.sisr_weights_pack_deep(tab_dev.data_ptr(), len(items), deep_cout, deep_cin, _stream()), 'sisr_weights_pack_deep')
-    return out, (big, sm, tab_dev, deep)
+    return preps, (big, sm, tab_dev, deep)
 
 
 _PIN_RING = {'buf': None, 'off': 0, 'half': 0, 'events': [[], []], 'streams': {}}
@@ -573,50 +618,58 @@ def _table_to_device(table, dev):
     return host.to(dev, non_blocking=True)
 
 
-def _attach_deep(desc, image, dev, prep):
-    """descriptor planned for conv_deep.hip: hand it that family's weight image (instead of `wpk`), the 1 / sigma its epilogue
-    applies (the image holds W_orig) and a split workspace"""
-    desc.wdeep, desc.wpk = image.data_ptr(), None
-    desc.epi_scale_p = prep.inv_sigma.data_ptr()
+def _alloc_out(n, ho, wo, c, y_mode, dev, res=None, alloc=torch.empty):
+    """the output tensor of a conv with `c` output channels over n x ho x wo pixels, by store mode"""
+    if y_mode == L.Y_NCHW:
+        return alloc((n, c, ho, wo), dtype=torch.float32, device=dev)
+    if y_mode == L.Y_SHUFFLE2:
+        return alloc((n, 2 * ho, 2 * wo, c // 4), dtype=act_dtype(c // 4), device=dev)
+    return alloc((n, ho, wo, c), dtype=act_dtype(c) if res is None else res.dtype, device=dev)
+
+
+def _bind(d, kind, prep, op, image, bias, res, out):
+    """operand, weight image, epilogue tensors and output of one conv launch.  A descriptor planned for conv_deep.hip gets that
+    family's weight image (instead of `wpk`), the 1 / sigma its epilogue applies (the image holds W_orig) and a split workspace
+    -> that workspace or None (the caller keeps it alive until the launch)"""
+    assert tuple(op.dims) == (d.N, d.H, d.W, d.Cin), (op.dims, (d.N, d.H, d.W, d.Cin))
+    op.fill(d)
+    d.wpk, d.bias, d.res, d.y = image.data_ptr(), _ptr(bias), _ptr(res), out.data_ptr()
+    d.y_bf16, d.res_bf16 = _bf(out), _bf(res)
     ws = None
-    if desc.deep.ws_bytes > 0:
-        ws = torch.empty((desc.deep.ws_bytes // 4,), dtype=torch.float32, device=dev)
-        desc.deep_ws = ws.data_ptr()
+    if kind.deep:
+        d.wdeep, d.wpk = image.data_ptr(), None
+        d.epi_scale_p = prep.inv_sigma.data_ptr()
+        if d.deep.ws_bytes > 0:
+            ws = torch.empty((d.deep.ws_bytes // 4,), dtype=torch.float32, device=out.device)
+            d.deep_ws = ws.data_ptr()
     return ws
+
+
+def _launch_conv(d, kind, what):
+    name = 'sisr_conv2d_bf16' if kind.bf16 else 'sisr_conv2d_f32'
+    L.check(getattr(L.lib(), name)(C.byref(d), _stream()), '%s(%s)' % (name, what))
 
 
 def conv_forward(prep, op, bias=None, y_mode=None, epi=L.EPI_NONE, stats=False, res=None, out=None):
     """Launch the forward conv of `prep` on lazy operand `op`.  Returns (y, stat_part, cnt_part)."""
     lib = L.lib()
-    f = _copy_struct(prep.plans[0])
+    f, kind = _copy_struct(prep.plans[0]), prep.kinds[0]
     gm = prep.ref.geom
-    n, h, w, c = op.dims
-    assert (n, h, w, c) == (f.N, f.H, f.W, f.Cin), ((n, h, w, c), (f.N, f.H, f.W, f.Cin))
     if y_mode is not None:
         f.y_mode = y_mode
     dev = op.x1.device
     if out is None:
-        if f.y_mode == L.Y_NCHW:
-            out = torch.empty((n, gm.cout, f.Ho, f.Wo), dtype=torch.float32, device=dev)
-        elif f.y_mode == L.Y_SHUFFLE2:
-            out = torch.empty((n, 2 * f.Ho, 2 * f.Wo, gm.cout // 4), dtype=act_dtype(gm.cout // 4), device=dev)
-        else:
-            out = torch.empty((n, f.Ho, f.Wo, gm.cout), dtype=act_dtype(gm.cout) if res is None else res.dtype,
-                              device=dev)
-    op.fill(f)
-    f.wpk, f.bias, f.res, f.y = prep.wpk_fwd.data_ptr(), _ptr(bias), _ptr(res), out.data_ptr()
-    f.y_bf16, f.res_bf16 = _bf(out), _bf(res)
+        out = _alloc_out(f.N, f.Ho, f.Wo, gm.cout, f.y_mode, dev, res)
+    ws = _bind(f, kind, prep, op, prep.wpk_fwd, bias, res, out)
     f.epi_act = epi
-    ws = _attach_deep(f, prep.wpk_fwd, dev, prep) if prep.kinds[0] == 2 else None          # (kept alive until the launch below)
     f.mfma_split = mfma_split()
     f.plan.variant = int(prep.lanes[0]) | (2 * prep.ldsimg[0])           # bit 0: lane-order bf16 image; bits 1-2: LDS-order fp32 image (mode)
+    trunk_eligible = lib.sisr_conv2d_trunk_eligible if kind.bf16 else lib.sisr_conv2d_trunk_f32_eligible
     fin = op.fin
     if fin is not None and not fin.done:
         # deferred BatchNorm finalisation: by this conv when it runs on a persistent trunk kernel, else stand-alone first
         fin.fill(f)
-        if os.environ.get('SISR_FUSE_BNFIN', '1') != '0' and \
-                prep.kinds[0] != 2 and \
-                (lib.sisr_conv2d_trunk_eligible if prep.kinds[0] else lib.sisr_conv2d_trunk_f32_eligible)(C.byref(f)) == 1:
+        if _on('SISR_FUSE_BNFIN') and not kind.deep and trunk_eligible(C.byref(f)) == 1:
             fin.done = True
         else:
             f.fin_stat = None
@@ -627,21 +680,18 @@ def conv_forward(prep, op, bias=None, y_mode=None, epi=L.EPI_NONE, stats=False, 
         # count depends on which kernel takes the descriptor, and that depends on the fusions requested (the upscale
         # variant of the trunk kernel has no statistics epilogue): ask with the statistics pointers already non-null
         f.stat_part = f.cnt_part = f.y
-        rows = (lib.sisr_conv2d_bf16_parts if prep.kinds[0] else lib.sisr_conv2d_f32_parts)(C.byref(f))
+        rows = (lib.sisr_conv2d_bf16_parts if kind.bf16 else lib.sisr_conv2d_f32_parts)(C.byref(f))
         sp = torch.empty((rows, 2, gm.cout), dtype=torch.float32, device=dev)
         cp = torch.empty((rows,), dtype=torch.float32, device=dev)
         f.stat_part, f.cnt_part = sp.data_ptr(), cp.data_ptr()
-    if prep.kinds[0]:
-        L.check(lib.sisr_conv2d_bf16(C.byref(f), _stream()), 'sisr_conv2d_bf16(fwd)')
-    else:
-        L.check(lib.sisr_conv2d_f32(C.byref(f), _stream()), 'sisr_conv2d_f32(fwd)')
+    _launch_conv(f, kind, 'fwd')
     return out, sp, cp
 
 
 def trunk_takes_skip_sum(prep, res, t):
     """the forward conv of `prep` runs on a persistent trunk kernel that can form the skip sum lrelu(res) + BN(t) in its
     staging (Operand.res_affine); SISR_FUSE_SKIP=0 keeps the separate elementwise pass"""
-    if os.environ.get('SISR_FUSE_SKIP', '1') == '0' or res.dtype != t.dtype or tuple(res.shape) != tuple(t.shape):
+    if not _on('SISR_FUSE_SKIP') or res.dtype != t.dtype or tuple(res.shape) != tuple(t.shape):
         return False
     f = _copy_struct(prep.plans[0])
     if (f.N, f.H, f.W, f.Cin) != tuple(res.shape):
@@ -650,144 +700,123 @@ def trunk_takes_skip_sum(prep, res, t):
     f.x1 = f.x2 = f.x_out = f.pa = f.pd = f.wpk = f.y = res.data_ptr()         # (non-null placeholders: eligibility only)
     f.pro_mode = L.PRO_RES_AFFINE
     f.x_bf16 = f.y_bf16 = _bf(res)
-    return (lib.sisr_conv2d_trunk_eligible if prep.kinds[0] else lib.sisr_conv2d_trunk_f32_eligible)(C.byref(f)) == 1
+    return (lib.sisr_conv2d_trunk_eligible if prep.kinds[0].bf16 else lib.sisr_conv2d_trunk_f32_eligible)(C.byref(f)) == 1
 
 
 def can_fuse_bn_backward(prep):
-    """the data-gradient conv of `prep` can also emit the backward reductions of the BatchNorm its output feeds
-    (generic bf16 kernel, one cout tile)"""
-    d = prep.plans[1]
-    if isinstance(d, S2x4):
+    """the data-gradient conv of `prep` can also emit the backward reductions of the BatchNorm its output feeds"""
+    d, kind = prep.plans[1], prep.kinds[1]
+    shape = _dgrad_shape(d)
+    if shape != DG_CONV:                          # stride 2: one launch, or four parity classes all on the deep family
+        return shape == DG_X4 or (shape == DG_CLASSES and _all_deep(d))
+    if kind.deep:                                 # conv_deep.hip: any number of cout tiles
         return True
-    if isinstance(d, list):                       # stride 2: the four parity classes, all on the deep family
-        return all(c is not None and c[3] == 2 for c in d)
-    if d is None:
-        return False
-    if prep.kinds[1] == 2:                        # conv_deep.hip: any number of cout tiles
-        return True
-    if not prep.kinds[1]:
+    if kind == Kind.F32:
         # fp32 build: only the persistent trunk kernel (conv_trunk_f32.hip) has that epilogue; conv_dgrad() falls back
         # to the plain launch (and returns no partial rows) when the filled descriptor turns out not to be eligible
         gm = prep.ref.geom
         return (gm.cin == 64 and gm.cout == 64 and gm.k == 3 and gm.stride == 1 and d.H % 8 == 0 and d.W % 16 == 0
-                and os.environ.get('SISR_TRUNK', '1') != '0' and os.environ.get('SISR_TRUNK_F32CONV', '1') != '0')
-    return d.plan.variant == 0 and d.plan.CoutPad == d.plan.nsub * 32
+                and _on('SISR_TRUNK') and _on('SISR_TRUNK_F32CONV'))
+    return d.plan.variant == 0 and d.plan.CoutPad == d.plan.nsub * 32        # generic bf16 kernel: one cout tile
 
 
-def _fill_bnb(d, consts, slope):
-    d.bnb_scale, d.bnb_shift, d.bnb_mean, d.bnb_invstd = (consts[0].data_ptr(), consts[1].data_ptr(),
-                                                          consts[2].data_ptr(), consts[3].data_ptr())
-    d.bnb_act = 0 if slope is None else 1
-    if isinstance(slope, torch.Tensor):
-        d.bnb_slope_p, d.bnb_slope = slope.data_ptr(), 1.0
-    else:
-        d.bnb_slope_p, d.bnb_slope = None, 1.0 if slope is None else float(slope)
+def _attach_bnb(descs, bnb, out):
+    """BatchNorm-backward epilogue of the data-gradient launches descs = [(descriptor, Kind)] whose output `out` is the gradient
+    arriving at BatchNorm(x), bnb = (x, consts, slope | None).  -> the partial rows for bn_backward(part=...), one block of rows
+    per descriptor in the order given -- or None where the kernel that takes the descriptor has no such epilogue (the fusion
+    is taken back then)"""
+    lib = L.lib()
+    x, consts, slope = bnb
+    assert tuple(x.shape) == tuple(out.shape)
+    rows = []
+    for d, kind in descs:
+        d.bnb_x, d.bnbx_bf16 = x.data_ptr(), _bf(x)
+        d.bnb_part = d.y                            # (any non-null value: the row count depends on the fusions requested)
+        rows.append((lib.sisr_conv2d_bf16_parts if kind.bf16 else lib.sisr_conv2d_f32_bnb_parts)(C.byref(d)))
+    if sum(rows) <= 0:                              # fp32 build, descriptor not taken by the persistent kernel: no fusion
+        for d, _ in descs:
+            d.bnb_x, d.bnb_part = None, None
+        return None
+    part = torch.empty((sum(rows), 2 * out.shape[-1] + 1), dtype=torch.float32, device=out.device)
+    r0 = 0
+    for (d, _), nr in zip(descs, rows):
+        d.bnb_part = part[r0:].data_ptr()
+        r0 += nr
+        d.bnb_scale, d.bnb_shift, d.bnb_mean, d.bnb_invstd = (consts[0].data_ptr(), consts[1].data_ptr(),
+                                                              consts[2].data_ptr(), consts[3].data_ptr())
+        d.bnb_act = 0 if slope is None else 1
+        d.bnb_slope_p, d.bnb_slope = _slope(slope)
+    return part
+
+
+def _launch_dgrad(descs, out, bnb, what):
+    """the launches of one data gradient in order, with the BatchNorm-backward epilogue when bnb is given -> (out, partial rows)"""
+    part = _attach_bnb(descs, bnb, out) if bnb is not None else None
+    for d, kind in descs:
+        _launch_conv(d, kind, what)
+    return out, part
+
+
+def _dgrad_x4(prep, dy_op, res, y_mode, bnb):
+    """stride 2, one launch over the four output-parity classes (conv_deep.hip)"""
+    x4, f, gm = prep.plans[1], prep.plans[0], prep.ref.geom
+    d = _copy_struct(x4.desc)
+    assert y_mode == L.Y_NHWC
+    dev = dy_op.x1.device
+    out = _alloc_out(f.N, f.H, f.W, gm.cin, y_mode, dev)
+    ws = _bind(d, Kind.DEEP_S2X4, prep, dy_op, prep.wpk_dgrad[3], None, res, out)
+    for c, buf in enumerate(prep.wpk_dgrad):
+        d.wdeep_c[c], d.deep_ckh[c] = buf.data_ptr(), x4.classes[c].kh
+    return _launch_dgrad([(d, Kind.DEEP_S2X4)], out, bnb, 'dgrad s2 x4')
+
+
+def _dgrad_classes(prep, dy_op, res, y_mode, bnb):
+    """stride 2: four output-parity classes, one launch each in class order"""
+    classes, f, gm = prep.plans[1], prep.plans[0], prep.ref.geom
+    assert y_mode == L.Y_NHWC
+    dev = dy_op.x1.device
+    complete = all(c is not None for c in classes)
+    out = _alloc_out(f.N, f.H, f.W, gm.cin, y_mode, dev, alloc=torch.empty if complete else torch.zeros)
+    descs, keep = [], []
+    for c, buf in zip(classes, prep.wpk_dgrad):
+        if c is None:
+            continue
+        d = _copy_struct(c.desc)
+        keep.append(_bind(d, c.kind, prep, dy_op, buf, None, res, out))
+        descs.append((d, c.kind))
+    # fused BatchNorm-backward reductions: every class of the deep family emits the partial rows of ITS quarter of the pixels
+    return _launch_dgrad(descs, out, bnb if _all_deep(classes) else None, 'dgrad s2')
+
+
+def _dgrad_conv(prep, dy_op, res, y_mode, bnb):
+    """stride 1: one conv over dy with the flipped weights"""
+    d, kind, gm = _copy_struct(prep.plans[1]), prep.kinds[1], prep.ref.geom
+    dev = dy_op.x1.device
+    d.y_mode = y_mode
+    out = _alloc_out(d.N, d.Ho, d.Wo, gm.cin, y_mode, dev, res)
+    ws = _bind(d, kind, prep, dy_op, prep.wpk_dgrad, None, res, out)
+    d.mfma_split = mfma_split()
+    d.plan.variant = int(prep.lanes[1]) | (2 * prep.ldsimg[1])
+    assert bnb is None or y_mode == L.Y_NHWC
+    return _launch_dgrad([(d, kind)], out, bnb, 'dgrad')
+
+
+_DGRAD = {DG_X4: _dgrad_x4, DG_CLASSES: _dgrad_classes, DG_CONV: _dgrad_conv}
 
 
 def conv_dgrad(prep, dy_op, res=None, y_mode=L.Y_NHWC, bnb=None):
     """Data gradient: conv over the (lazy) output gradient with the flipped packed weights.
     bnb = (x, consts [4,C], slope | None): the result is the gradient arriving at BatchNorm(x) (through a leaky
     activation when slope is given); returns (out, partial rows for bn_backward_finalize) in that case."""
-    lib = L.lib()
-    gm = prep.ref.geom
-    if isinstance(prep.plans[1], S2x4):          # stride 2, one launch over the four output-parity classes (conv_deep.hip)
-        x4 = prep.plans[1]
-        d = _copy_struct(x4.desc)
-        assert tuple(dy_op.dims) == (d.N, d.H, d.W, d.Cin) and y_mode == L.Y_NHWC, (dy_op.dims, (d.N, d.H, d.W, d.Cin))
-        dev = dy_op.x1.device
-        f = prep.plans[0]
-        out = torch.empty((f.N, f.H, f.W, gm.cin), dtype=act_dtype(gm.cin), device=dev)
-        dy_op.fill(d)
-        d.bias, d.res, d.y = None, _ptr(res), out.data_ptr()
-        d.y_bf16, d.res_bf16 = _bf(out), _bf(res)
-        for c, buf in enumerate(prep.wpk_dgrad):
-            d.wdeep_c[c], d.deep_ckh[c] = buf.data_ptr(), x4.classes[c][0]
-        ws = _attach_deep(d, prep.wpk_dgrad[3], dev, prep)
-        part = None
-        if bnb is not None:
-            x, consts, slope = bnb
-            assert tuple(x.shape) == tuple(out.shape)
-            d.bnb_x, d.bnbx_bf16, d.bnb_part = x.data_ptr(), _bf(x), d.y
-            rows = lib.sisr_conv2d_bf16_parts(C.byref(d))
-            part = torch.empty((rows, 2 * gm.cin + 1), dtype=torch.float32, device=dev)
-            d.bnb_part = part.data_ptr()
-            _fill_bnb(d, consts, slope)
-        L.check(lib.sisr_conv2d_bf16(C.byref(d), _stream()), 'sisr_conv2d_bf16(dgrad s2 x4)')
-        return out if bnb is None else (out, part)
-    if isinstance(prep.plans[1], list):          # stride 2: four output-parity classes
-        f = prep.plans[0]
-        dev = dy_op.x1.device
-        assert y_mode == L.Y_NHWC
-        complete = all(c is not None for c in prep.plans[1])
-        out = (torch.empty if complete else torch.zeros)((f.N, f.H, f.W, gm.cin), dtype=act_dtype(gm.cin), device=dev)
-        # fused BatchNorm-backward reductions: every class of the deep family emits the partial rows of ITS quarter of the pixels
-        fuse = bnb is not None and all(c is not None and c[3] == 2 for c in prep.plans[1])
-        descs = []
-        for cls, buf in zip(prep.plans[1], prep.wpk_dgrad):
-            if cls is None:
-                continue
-            d = _copy_struct(cls[0])
-            assert tuple(dy_op.dims) == (d.N, d.H, d.W, d.Cin), (dy_op.dims, (d.N, d.H, d.W, d.Cin))
-            dy_op.fill(d)
-            d.wpk, d.bias, d.res, d.y = buf.data_ptr(), None, _ptr(res), out.data_ptr()
-            d.y_bf16, d.res_bf16 = _bf(out), _bf(res)
-            ws = _attach_deep(d, buf, dev, prep) if cls[3] == 2 else None
-            descs.append((d, cls[3], ws))
-        part = None
-        if fuse:
-            x, consts, slope = bnb
-            assert tuple(x.shape) == tuple(out.shape)
-            rows = []
-            for d, _, _ in descs:
-                d.bnb_x, d.bnbx_bf16, d.bnb_part = x.data_ptr(), _bf(x), d.y
-                rows.append(lib.sisr_conv2d_bf16_parts(C.byref(d)))
-            part = torch.empty((sum(rows), 2 * gm.cin + 1), dtype=torch.float32, device=dev)
-            r0 = 0
-            for (d, _, _), nr in zip(descs, rows):
-                d.bnb_part = part[r0:].data_ptr()
-                r0 += nr
-                _fill_bnb(d, consts, slope)
-        for d, kind, ws in descs:
-            if kind:
-                L.check(lib.sisr_conv2d_bf16(C.byref(d), _stream()), 'sisr_conv2d_bf16(dgrad s2)')
-            else:
-                L.check(lib.sisr_conv2d_f32(C.byref(d), _stream()), 'sisr_conv2d_f32(dgrad s2)')
-        return out if bnb is None else (out, part)
-    d = _copy_struct(prep.plans[1])
-    assert tuple(dy_op.dims) == (d.N, d.H, d.W, d.Cin), (dy_op.dims, (d.N, d.H, d.W, d.Cin))
-    dev = dy_op.x1.device
-    d.y_mode = y_mode
-    if y_mode == L.Y_NCHW:
-        out = torch.empty((d.N, gm.cin, d.Ho, d.Wo), dtype=torch.float32, device=dev)
-    else:
-        out = torch.empty((d.N, d.Ho, d.Wo, gm.cin), dtype=act_dtype(gm.cin) if res is None else res.dtype, device=dev)
-    dy_op.fill(d)
-    d.wpk, d.bias, d.res, d.y = prep.wpk_dgrad.data_ptr(), None, _ptr(res), out.data_ptr()
-    d.y_bf16, d.res_bf16 = _bf(out), _bf(res)
-    d.mfma_split = mfma_split()
-    ws = _attach_deep(d, prep.wpk_dgrad, dev, prep) if prep.kinds[1] == 2 else None        # (kept alive until the launch below)
-    d.plan.variant = int(prep.lanes[1]) | (2 * prep.ldsimg[1])
-    part = None
-    if bnb is not None:
-        x, consts, slope = bnb
-        assert tuple(x.shape) == tuple(out.shape) and y_mode == L.Y_NHWC
-        d.bnb_x, d.bnbx_bf16 = x.data_ptr(), _bf(x)
-        d.bnb_part = d.y                            # (any non-null value: the row count depends on the fusions requested)
-        rows = lib.sisr_conv2d_bf16_parts(C.byref(d)) if prep.kinds[1] else lib.sisr_conv2d_f32_bnb_parts(C.byref(d))
-        if rows > 0:
-            part = torch.empty((rows, 2 * gm.cin + 1), dtype=torch.float32, device=dev)
-            d.bnb_part = part.data_ptr()
-            _fill_bnb(d, consts, slope)
-        else:                                        # fp32 build, descriptor not taken by the persistent kernel: no fusion
-            d.bnb_x, d.bnb_part = None, None
-    if prep.kinds[1]:
-        L.check(lib.sisr_conv2d_bf16(C.byref(d), _stream()), 'sisr_conv2d_bf16(dgrad)')
-    else:
-        L.check(lib.sisr_conv2d_f32(C.byref(d), _stream()), 'sisr_conv2d_f32(dgrad)')
+    out, part = _DGRAD[_dgrad_shape(prep.plans[1])](prep, dy_op, res, y_mode, bnb)
     return out if bnb is None else (out, part)
 
 
 KERNEL_COUNTS = {}          # launches per kernel family, for the tests that must see a family run (not a timing path: host counters)
+
+
+def _count(key, n=1):
+    KERNEL_COUNTS[key] = KERNEL_COUNTS.get(key, 0) + n
 
 
 class PendingSlabs:
@@ -822,7 +851,7 @@ def conv_wgrad(prep, x_op, dy_op, defer=None):
     """Weight + bias gradient in packed layout: returns the reduced [slab_elems + CoutPad] buffer.
     defer (PendingSlabs or None): leave the slab reduction to a later launch (see PendingSlabs)."""
     lib = L.lib()
-    g = _copy_struct(prep.plans[2])
+    g, bf16 = _copy_struct(prep.plans[2]), prep.kinds[2].bf16
     cout = prep.ref.geom.cout
     assert tuple(x_op.dims) == (g.N, g.H, g.W, g.Cin) and tuple(dy_op.dims) == (g.N, g.Ho, g.Wo, cout), \
         (x_op.dims, dy_op.dims)
@@ -845,24 +874,34 @@ def conv_wgrad(prep, x_op, dy_op, defer=None):
     x_op.fill(g)
     dy_op.fill(g, g=True)
     g.mfma_split = mfma_split()
-    n_slabs = (lib.sisr_wgrad_bf16_slabs if prep.kinds[2] else lib.sisr_wgrad_f32_slabs)(C.byref(g))
-    if prep.kinds[2] and g.deep.enabled and lib.sisr_wgrad_deep_eligible(C.byref(g)):
-        KERNEL_COUNTS['wgrad_deep'] = KERNEL_COUNTS.get('wgrad_deep', 0) + 1
-    lead = int(lib.sisr_wgrad_bf16_slab_lead(C.byref(g))) if prep.kinds[2] else 0     # the persistent bf16 kernel's slabs are bf16
+    n_slabs = (lib.sisr_wgrad_bf16_slabs if bf16 else lib.sisr_wgrad_f32_slabs)(C.byref(g))
+    if bf16 and g.deep.enabled and lib.sisr_wgrad_deep_eligible(C.byref(g)):
+        _count('wgrad_deep')
+    lead = int(lib.sisr_wgrad_bf16_slab_lead(C.byref(g))) if bf16 else 0     # the persistent bf16 kernel's slabs are bf16
     slab = torch.empty((n_slabs, stride), dtype=torch.float32, device=dev)
     g.slab = slab.data_ptr()
     g.bias_slab = slab.data_ptr() + 4 * g.slab_elems
-    if prep.kinds[2]:
-        L.check(lib.sisr_conv2d_wgrad_bf16(C.byref(g), _stream()), 'sisr_conv2d_wgrad_bf16')
-    else:
-        L.check(lib.sisr_conv2d_wgrad_f32(C.byref(g), _stream()), 'sisr_conv2d_wgrad_f32')
+    name = 'sisr_conv2d_wgrad_bf16' if bf16 else 'sisr_conv2d_wgrad_f32'
+    L.check(getattr(lib, name)(C.byref(g), _stream()), name)
     red = torch.empty((stride,), dtype=torch.float32, device=dev)
-    if defer is not None and os.environ.get('SISR_FUSE_SLABRED', '1') != '0':
+    if defer is not None and _on('SISR_FUSE_SLABRED'):
         defer.jobs.append((slab, red, n_slabs, stride, lead))
         return red
     L.check(lib.sisr_slab_reduce_f32(slab.data_ptr(), red.data_ptr(), n_slabs, stride, lead, _stream()),
             'sisr_slab_reduce_f32')
     return red
+
+
+def _deep_batch_key(g):
+    """members of one sisr_wgrad_deep_batch launch share the stride (a template argument) and whether the gradient prologue reads
+    a second tensor -- the library checks operand_needs_x2(gpro_mode) of every member against the first's"""
+    return g.stride, g.gpro_mode in (L.PRO_BNBWD, L.PRO_BNACT_BWD, L.PRO_ACT_BWD)
+
+
+def _trunk_batch_key(prep, g):
+    """members of one sisr_wgrad_trunk(_f32)_batch launch share the tensor family (the entry point) and the gradient prologue
+    itself -- the library's wtrunk_batch_check compares every member's gpro_mode with the first's"""
+    return prep.kinds[2].bf16, g.gpro_mode
 
 
 class WgradDeepBatch:
@@ -878,43 +917,36 @@ class WgradDeepBatch:
 
     def add(self, prep, x_op, dy_op):
         """-> reduced-gradient buffer, or None when the layer does not qualify (the caller then runs conv_wgrad as usual)"""
-        if os.environ.get('SISR_WGRAD_BATCH', '1') == '0':
+        if not _on('SISR_WGRAD_BATCH'):
             return None
-        if not prep.kinds[2]:
-            # fp32-tensor builds: the persistent trunk kernel's plain layers (Cout = 64) are batched like the bf16 build's
-            g = _copy_struct(prep.plans[2])
-            x_op.fill(g)
-            dy_op.fill(g, g=True)
-            g.mfma_split = mfma_split()
-            if (g.Cout != 64 or os.environ.get('SISR_WGRAD_TRUNK_BATCH', '1') == '0' or dy_op.mode != L.X_NHWC
-                    or not L.lib().sisr_wgrad_trunk_f32_eligible(C.byref(g))):
-                return None
-            red = torch.empty((g.slab_stride,), dtype=torch.float32, device=x_op.x1.device)
-            self.trunk.append((prep, g, x_op, dy_op, red))
-            return red
+        lib = L.lib()
         g = _copy_struct(prep.plans[2])
-        if not g.deep.enabled:
-            return None
         x_op.fill(g)
         dy_op.fill(g, g=True)
-        lib = L.lib()
+        members = self.items                                         # (the operands' tensors stay alive until run())
+        if not prep.kinds[2].bf16:
+            # fp32-tensor builds: the persistent trunk kernel's plain layers (Cout = 64) are batched like the bf16 build's
+            g.mfma_split = mfma_split()
+            if g.Cout != 64 or dy_op.mode != L.X_NHWC or not lib.sisr_wgrad_trunk_f32_eligible(C.byref(g)):
+                return None
+            members = self.trunk
+        elif not g.deep.enabled:
+            return None
         # (the last conv's kernel comes first in sisr_conv2d_wgrad_bf16's dispatch and stays; so does the persistent trunk kernel
         # where its 8 x 16 tiles fill the chip -- at LR 48 they are 288 for 256 CUs: 144 workgroups of two, and the batch measured
         # 366 us for the 33 trunk layers against 33 x 16.5 us)
-        if lib.sisr_wgrad_toimage_eligible(C.byref(g)) or not lib.sisr_wgrad_deep_eligible(C.byref(g)):
+        elif lib.sisr_wgrad_toimage_eligible(C.byref(g)) or not lib.sisr_wgrad_deep_eligible(C.byref(g)):
             return None
-        if lib.sisr_wgrad_trunk_eligible(C.byref(g)):
-            if g.N * g.H * g.W >= int(os.environ.get('SISR_WGRAD_BATCH_TRUNK_PIXELS', 384 * 128)) or os.environ.get('SISR_WGRAD_BATCH_TRUNK', '1') == '0':
+        elif lib.sisr_wgrad_trunk_eligible(C.byref(g)):
+            if g.N * g.H * g.W >= int(_knob('SISR_WGRAD_BATCH_TRUNK_PIXELS', 384 * 128)) or not _on('SISR_WGRAD_BATCH_TRUNK'):
                 # the persistent kernel keeps the layer -- and, for the plain trunk layers (Cout = 64), its launches are batched
                 # too (run(): sisr_wgrad_trunk_batch, workgroups [z * wpl, (z + 1) * wpl) serve layer z)
-                if g.Cout != 64 or os.environ.get('SISR_WGRAD_TRUNK_BATCH', '1') == '0':
+                if g.Cout != 64:
                     return None
-                red = torch.empty((g.slab_stride,), dtype=torch.float32, device=x_op.x1.device)
-                self.trunk.append((prep, g, x_op, dy_op, red))
-                return red
-            # (sisr_wgrad_bf16_slab_lead answers for the trunk kernel then: the same SISR_SLAB_BF16 rule as wgrad_deep.hip's)
+                members = self.trunk
+            # (else sisr_wgrad_bf16_slab_lead answers for the trunk kernel: the same SISR_SLAB_BF16 rule as wgrad_deep.hip's)
         red = torch.empty((g.slab_stride,), dtype=torch.float32, device=x_op.x1.device)
-        self.items.append((prep, g, x_op, dy_op, red))              # (the operands' tensors stay alive until run())
+        members.append((prep, g, x_op, dy_op, red))
         return red
 
     def run(self, pending):
@@ -926,18 +958,17 @@ class WgradDeepBatch:
         items, self.items = self.items, []
         groups = {}
         for it in items:
-            g = it[1]
-            groups.setdefault((g.stride, g.gpro_mode in (L.PRO_BNBWD, L.PRO_BNACT_BWD, L.PRO_ACT_BWD)), []).append(it)
+            groups.setdefault(_deep_batch_key(it[1]), []).append(it)
         for group in groups.values():
             work = [float(g.N) * g.Ho * g.Wo * g.Cin * g.Cout for _, g, _, _, _ in group]
             tot = sum(work)
             table = (L.WgradDesc * len(group))()
-            keep, first_wg = [], 0
+            first_wg = 0
             for i, (prep, g, x_op, dy_op, red) in enumerate(group):
                 if len(group) > 1:
                     blocks = (g.Cin // 64) * (g.Cout // 64)
                     share = max(blocks, int(round(256.0 * work[i] / tot)))
-                    cache, key = prep.ref.geom._plans, ('wgrad_deep_share', g.N, g.H, g.W, share, os.environ.get('SISR_SLAB_BF16', '1'))
+                    cache, key = prep.ref.geom._plans, ('wgrad_deep_share', g.N, g.H, g.W, share, _knob('SISR_SLAB_BF16', '1'))
                     if key not in cache:
                         t = _copy_struct(g)
                         L.check(lib.sisr_wgrad_deep_plan(C.byref(t), share), 'sisr_wgrad_deep_plan(share)')
@@ -952,12 +983,10 @@ class WgradDeepBatch:
                 table[i] = g
                 lead = int(lib.sisr_wgrad_bf16_slab_lead(C.byref(g)))
                 pending.jobs.append((slab, red, n_slabs, g.slab_stride, lead))
-                keep.append(slab)
             dev = _table_to_device(table, group[0][4].device)
             L.check(lib.sisr_wgrad_deep_batch(table, dev.data_ptr(), len(group), _stream()), 'sisr_wgrad_deep_batch')
-            KERNEL_COUNTS['wgrad_deep'] = KERNEL_COUNTS.get('wgrad_deep', 0) + len(group)
-            KERNEL_COUNTS['wgrad_deep_batch'] = KERNEL_COUNTS.get('wgrad_deep_batch', 0) + 1
-
+            _count('wgrad_deep', len(group))
+            _count('wgrad_deep_batch')
 
     def _run_trunk(self, pending):
         if not self.trunk:
@@ -966,7 +995,7 @@ class WgradDeepBatch:
         items, self.trunk = self.trunk, []
         groups = {}
         for it in items:
-            groups.setdefault((bool(it[0].kinds[2]), it[1].gpro_mode), []).append(it)
+            groups.setdefault(_trunk_batch_key(it[0], it[1]), []).append(it)
         for (is_bf16, _), group in groups.items():
             n = len(group)
             f_bytes, f_args, f_run, f_lead = ((lib.sisr_wgrad_trunk_batch_arg_bytes, lib.sisr_wgrad_trunk_batch_args, lib.sisr_wgrad_trunk_batch,
@@ -988,7 +1017,7 @@ class WgradDeepBatch:
             L.check(f_args(table, n, C.addressof(args)), 'sisr_wgrad_trunk(_f32)_batch_args')
             dev = _table_to_device(args, group[0][4].device)
             L.check(f_run(table, dev.data_ptr(), n, wpl, _stream()), 'sisr_wgrad_trunk(_f32)_batch')
-            KERNEL_COUNTS['wgrad_trunk_batch'] = KERNEL_COUNTS.get('wgrad_trunk_batch', 0) + 1
+            _count('wgrad_trunk_batch')
 
 
 class WeightGradBatch:
@@ -1009,8 +1038,8 @@ class WeightGradBatch:
         fast, slow = [], []
         for it in self.items:
             gm, g = it[0].ref.geom, it[0].plans[2]
-            ok = (it[0].kinds[2] and gm.k == 3 and gm.cin % 32 == 0 and gm.cout % 32 == 0 and not gm.shuffle2
-                  and g.CoutPad >= gm.cout and os.environ.get('SISR_WGRAD_FAST', '1') != '0')
+            ok = (it[0].kinds[2].bf16 and gm.k == 3 and gm.cin % 32 == 0 and gm.cout % 32 == 0 and not gm.shuffle2
+                  and g.CoutPad >= gm.cout)
             (fast if ok else slow).append(it)
         res = {}
         self._keep = []
@@ -1036,7 +1065,7 @@ class WeightGradBatch:
             t.grad_bias = _ptr(gb)
             t.Cout, t.Cin, t.KH, t.KW, t.shuffle2 = gm.cout, gm.cin, gm.k, gm.k, int(gm.shuffle2)
             t.CK, t.PS, t.KROWP, t.n_chunk, t.CoutPad = g.CK, g.PS, g.KROWP, g.n_chunk, g.CoutPad
-            t.layout = 1 if p.kinds[2] else 0
+            t.layout = int(p.kinds[2].bf16)
             res[id(p.ref)] = (gw, gb)
         tab = _table_to_device(table, dev)
         if is_fast:
@@ -1049,6 +1078,59 @@ class WeightGradBatch:
             L.check(lib.sisr_weights_grad(tab.data_ptr(), len(items), work.data_ptr(), parts, _stream()), 'sisr_weights_grad')
         self._keep.append((tab, work))
         return res
+
+
+class BackwardBook:
+    """What the hand-scheduled backward passes of the generator and the discriminator keep alike: the weight gradients of their
+    convs are collected (WgradDeepBatch: launched together; WeightGradBatch: un-packed together), the slab sums are deferred
+    (PendingSlabs), and flush(tag) launches what is held back and announces every new gradient to the sink
+    (distributed.GradReducer or None).  own_batch_slabs: the slab sums of the batched kernels wait in a list of their own
+    (`batch_slabs`) instead of in `slabs`."""
+
+    def __init__(self, P, refs, params, sink, own_batch_slabs):
+        self.P, self.sink = P, sink
+        self.grads = {}
+        self.wg, self.wb = WeightGradBatch(), WgradDeepBatch()
+        self.slabs = PendingSlabs()
+        self.batch_slabs = PendingSlabs() if own_batch_slabs else self.slabs
+        self.refs = {id(r): r for r in refs}
+        self.by_id = {id(p): p for p in params}
+        self.announced = set()
+
+    def flush(self, tag):
+        """un-pack the weight gradients collected so far (one launch) and announce every new gradient to the sink"""
+        self.wb.run(self.batch_slabs)
+        self.batch_slabs.flush()
+        self.slabs.flush()                      # (nothing left, no launch, where the two are one list)
+        grads = self.grads
+        for ref_id, (gw, gb) in self.wg.run().items():
+            ref = self.refs[ref_id]
+            if gw is not None:
+                grads[id(ref.weight)] = gw
+            if gb is not None:
+                grads[id(ref.bias)] = gb
+        self.wg.items = []
+        if self.sink is not None:
+            new = [k for k in grads if k not in self.announced and k in self.by_id]
+            self.announced.update(new)
+            self.sink.ready([(self.by_id[k], grads[k]) for k in new], tag)
+
+    def conv_bwd(self, ref, x_op, dy_op, need_dgrad=True, res=None, y_mode=L.Y_NHWC, bnb=None):
+        """weight gradient (batched un-packing at the flush) + data gradient.  bnb = (x, consts, slope) names the BatchNorm (and
+        the leaky activation behind it) the data gradient arrives at: where the conv kernel can, it emits that BatchNorm's
+        backward reductions from its epilogue and (gradient, partial rows) is returned instead of the gradient."""
+        p = self.P[id(ref)]
+        want_w, want_b = ref.weight.requires_grad, ref.bias is not None and ref.bias.requires_grad
+        if want_w or want_b:
+            red = self.wb.add(p, x_op, dy_op)
+            self.wg.add(p, red if red is not None else conv_wgrad(p, x_op, dy_op, defer=self.slabs), want_w, want_b)
+        if not need_dgrad:
+            return None
+        if bnb is None:
+            return conv_dgrad(p, dy_op, res=res, y_mode=y_mode)
+        if can_fuse_bn_backward(p):
+            return conv_dgrad(p, dy_op, res=res, y_mode=y_mode, bnb=bnb)
+        return conv_dgrad(p, dy_op, res=res, y_mode=y_mode), None
 
 
 class LazyBN:
@@ -1066,12 +1148,7 @@ class LazyBN:
 
     def ensure(self):
         if not self.done:
-            lib = L.lib()
-            bn, k = self.bn, self.k
-            L.check(lib.sisr_bn_finalize(self.sp.data_ptr(), self.cp.data_ptr(), self.sp.shape[0], k.shape[1],
-                                         bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                                         bn.running_var.data_ptr(), self.momentum, self.eps, k[0].data_ptr(),
-                                         k[1].data_ptr(), k[2].data_ptr(), k[3].data_ptr(), _stream()), 'sisr_bn_finalize')
+            bn_finalize(self.sp, self.cp, self.bn, self.eps, self.momentum, k=self.k)
             self.done = True
         return self.k
 
@@ -1084,11 +1161,12 @@ class LazyBN:
         d.fin_momentum, d.fin_eps = self.momentum, self.eps
 
 
-def bn_finalize(sp, cp, bn, eps=1e-5, momentum=0.1):
-    """-> consts [4, C]: scale, shift, batch mean, invstd; updates bn.running_* in place."""
+def bn_finalize(sp, cp, bn, eps=1e-5, momentum=0.1, k=None):
+    """-> consts [4, C]: scale, shift, batch mean, invstd (written into `k` when given); updates bn.running_* in place."""
     lib = L.lib()
     cch = bn.weight.numel()
-    k = torch.empty((4, cch), dtype=torch.float32, device=sp.device)
+    if k is None:
+        k = torch.empty((4, cch), dtype=torch.float32, device=sp.device)
     L.check(lib.sisr_bn_finalize(sp.data_ptr(), cp.data_ptr(), sp.shape[0], cch, bn.weight.data_ptr(),
                                  bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
                                  momentum, eps, k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
@@ -1116,10 +1194,7 @@ def bn_backward(dy, x, consts, gamma, slope=None, part=None, slabs=None):
     d = L.BnBwdDesc()
     d.P, d.C = x.numel() // cch, cch
     d.act_mode = 0 if slope is None else 1
-    if isinstance(slope, torch.Tensor):
-        d.slope_p, d.slope = slope.data_ptr(), 1.0
-    else:
-        d.slope_p, d.slope = None, 1.0 if slope is None else float(slope)
+    d.slope_p, d.slope = _slope(slope)
     dev = x.device
     if part is None:
         L.check(lib.sisr_bn_bwd_plan(C.byref(d)), 'sisr_bn_bwd_plan')
@@ -1155,8 +1230,7 @@ def eltwise_res_affine(x1, slope1, x2=None, pa=None, pd=None):
     lib = L.lib()
     cch = x1.shape[-1]
     y = torch.empty(x1.shape, dtype=act_dtype(cch), device=x1.device)
-    sp, sv = (slope1.data_ptr(), 1.0) if isinstance(slope1, torch.Tensor) else \
-        (None, 1.0 if slope1 is None else float(slope1))
+    sp, sv = _slope(slope1)
     dt = _bf(x1) | (_bf(x2) << 1) | (_bf(y) << 2)
     L.check(lib.sisr_eltwise_res_affine(x1.data_ptr(), sp, sv, _ptr(x2), _ptr(pa), _ptr(pd), y.data_ptr(),
                                         x1.numel() // cch, cch, dt, _stream()), 'sisr_eltwise_res_affine')
@@ -1192,7 +1266,7 @@ def require_gpu_tensor(x, what):
 def nhwc_to_nchw(x, out, dst_stride, pa=None, pd=None, slope=None):
     """materialise lrelu(pa*x+pd, slope) from NHWC x into an NCHW destination (rows of `out`)."""
     n, h, w, c = x.shape
-    sp, sv = (slope.data_ptr(), 1.0) if isinstance(slope, torch.Tensor) else (None, 1.0 if slope is None else float(slope))
+    sp, sv = _slope(slope)
     L.check(L.lib().sisr_nhwc_to_nchw(x.data_ptr(), _ptr(pa), _ptr(pd), sp, sv, out.data_ptr(), dst_stride,
                                       n, h, w, c, _bf(x), _stream()), 'sisr_nhwc_to_nchw')
 
@@ -1242,7 +1316,7 @@ def fc_backward(dy, x, w, in_slope=1.0, need_dx=True):
 
 def fc_head_ok(bsz, k, n):
     """the classifier head of D runs on fc_head.hip (exact-fp32 MFMA weight streaming): up to 16 batch rows, K in 64s, N in 128s"""
-    return bsz <= FC_MAX_BATCH and k % 64 == 0 and n % 128 == 0 and os.environ.get('SISR_FC_HEAD', '1') != '0'
+    return bsz <= FC_MAX_BATCH and k % 64 == 0 and n % 128 == 0
 
 
 def fc_head_forward(x, w1, b1, w2, b2, slope):
@@ -1291,7 +1365,7 @@ def fc_wgrad_rows(dy_all, x_all, w, scale):
     dw = torch.empty_like(w)
     L.check(L.lib().sisr_fc_wgrad_rows(dy_all.data_ptr(), x_all.data_ptr(), float(scale), dw.data_ptr(), rows, k, w.shape[0], _stream()),
             'sisr_fc_wgrad_rows')
-    KERNEL_COUNTS['fc_wgrad_rows'] = KERNEL_COUNTS.get('fc_wgrad_rows', 0) + 1
+    _count('fc_wgrad_rows')
     return dw
 
 

@@ -172,51 +172,12 @@ def run_backward(sv, grad_out, need_dx, sink=None, params=()):
     topo, P = sv.topo, sv.P
     E.require_gpu_tensor(grad_out, 'generator grad_output')
     grad_out = grad_out.contiguous()
-    grads = {}
-    wg = E.WeightGradBatch()
-    pending = E.PendingSlabs()            # slab sums of the weight gradients, carried by the next BatchNorm-backward finish
+    # the slab sums of the weight gradients are carried by the next BatchNorm-backward finish (book.slabs).
     # trunk sizes the persistent kernels do not take (24 x 24 maps of a x4 / x8 generator): the weight gradients of the 3x3 layers are
     # collected and launched together at the flush (engine.WgradDeepBatch); their slab sums wait in a list of their own -- a
     # BatchNorm-backward finish must not pick up a slab set whose kernel has not run yet
-    wb, pending_b = E.WgradDeepBatch(), E.PendingSlabs()
-    by_id = {id(p): p for p in params}
-    announced = set()
-    all_refs = [r for r in topo.conv_refs() if r is not None]
-
-    def flush(tag):
-        """un-pack the weight gradients collected so far (one launch) and announce every new gradient to the sink"""
-        wb.run(pending_b)
-        pending_b.flush()
-        pending.flush()
-        for ref_id, (gw, gb) in wg.run().items():
-            ref = next(r for r in all_refs if id(r) == ref_id)
-            if gw is not None:
-                grads[id(ref.weight)] = gw
-            if gb is not None:
-                grads[id(ref.bias)] = gb
-        wg.items = []
-        if sink is not None:
-            new = [k for k in grads if k not in announced and k in by_id]
-            announced.update(new)
-            sink.ready([(by_id[k], grads[k]) for k in new], tag)
-
-    def conv_bwd(ref, x_op, dy_op, need_dgrad=True, res=None, y_mode=L.Y_NHWC, bnb=None):
-        """weight gradient (batched un-packing at the end) + data gradient.  bnb = (x, consts, slope) names the
-        BatchNorm the data gradient arrives at: where the conv kernel can, it emits that BatchNorm's backward
-        reductions from its epilogue and (gradient, partial rows) is returned instead of the gradient."""
-        p = P[id(ref)]
-        want_w, want_b = ref.weight.requires_grad, ref.bias is not None and ref.bias.requires_grad
-        if want_w or want_b:
-            red = wb.add(p, x_op, dy_op)
-            wg.add(p, red if red is not None else E.conv_wgrad(p, x_op, dy_op, defer=pending), want_w, want_b)
-        if not need_dgrad:
-            return None
-        if bnb is None:
-            return E.conv_dgrad(p, dy_op, res=res, y_mode=y_mode)
-        if E.can_fuse_bn_backward(p):
-            return E.conv_dgrad(p, dy_op, res=res, y_mode=y_mode, bnb=bnb)
-        return E.conv_dgrad(p, dy_op, res=res, y_mode=y_mode), None
-
+    book = E.BackwardBook(P, [r for r in topo.conv_refs() if r is not None], params, sink, own_batch_slabs=True)
+    grads, pending, flush, conv_bwd = book.grads, book.slabs, book.flush, book.conv_bwd
     n = sv.x.shape[0]
     # ---- end conv + tanh (or, for forward_no_end, the NCHW -> NHWC change of the incoming gradient) --------
     ho, wo = sv.out.shape[2], sv.out.shape[3]
