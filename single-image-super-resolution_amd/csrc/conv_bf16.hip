@@ -19,25 +19,14 @@
 #include <cstring>
 
 #include "sisr_bf16_stage.h"
+#include "sisr_instr.h"
 
 // Phase timeline of the generic kernel (developer build only: `make trace` -> libsisr_hip_trace.so, read by
-// tools/trace_conv.py).  Thread 0 of each workgroup stamps the 100 MHz wall clock at phase boundaries.
-#ifdef SISR_CONV_TRACE
-#define SISR_TRACE_WG 4096
-#define SISR_TRACE_SLOTS 16
-__device__ unsigned long long sisr_trace_buf[SISR_TRACE_WG * SISR_TRACE_SLOTS];
-#define TR(k)                                                                                              \
-    do {                                                                                                   \
-        const unsigned wg_ = blockIdx.y * gridDim.x + blockIdx.x;                                          \
-        if (threadIdx.x == 0 && wg_ < SISR_TRACE_WG && blockIdx.z == 0)                                    \
-            sisr_trace_buf[wg_ * SISR_TRACE_SLOTS + (k)] = wall_clock64();                                 \
-    } while (0)
-extern "C" int sisr_trace_read(void* dst, int n_u64) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(sisr_trace_buf), (size_t)n_u64 * 8, 0, hipMemcpyDeviceToHost);
-}
-#else
-#define TR(k)
-#endif
+// tools/trace_conv.py).  Thread 0 of each workgroup of the grid's z = 0 plane (the other planes have no slots) stamps the
+// 100 MHz wall clock at phase boundaries.  (The z test sits in `end` -- no slots outside that plane -- and not in `who`: written
+// there the compiler orders the tests differently and the trace build's device code changes.)
+SISR_TRACE_BUFFER(sisr_trace, 4096, 16)
+#define TR(k) SISR_TRACE_STAMP_ROW(sisr_trace, threadIdx.x == 0, blockIdx.y * gridDim.x + blockIdx.x, k, blockIdx.z == 0 ? 16 : 0, wall_clock64())
 
 // merge two (count, mean, M2) partials (Chan, Golub, LeVeque); either side may be empty
 __device__ __forceinline__ void stat_merge(float& n, float& mu, float& m2, float nb, float mub, float m2b) {
@@ -98,12 +87,12 @@ __global__ void __launch_bounds__(SISR_BLOCK, 2) conv_mfma_bf16_kernel(const Sis
 
     TR(0);
 #ifdef SISR_CONV_TRACE
-    if (tid == 0 && blockIdx.y * gridDim.x + blockIdx.x < SISR_TRACE_WG && blockIdx.z == 0) {
+    if (tid == 0 && blockIdx.y * gridDim.x + blockIdx.x < sisr_trace_wgs && blockIdx.z == 0) {
         unsigned hwid;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
         unsigned xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        sisr_trace_buf[(blockIdx.y * gridDim.x + blockIdx.x) * SISR_TRACE_SLOTS + 15] = ((unsigned long long)xcc << 32) | hwid;
+        sisr_trace_buf[(blockIdx.y * gridDim.x + blockIdx.x) * sisr_trace_slots + 15] = ((unsigned long long)xcc << 32) | hwid;
     }
 #endif
     // packed weights [chunk][CoutPad][WSG] bf16: a workgroup's slice of one chunk is contiguous, 16-byte vector
@@ -621,12 +610,8 @@ extern "C" int sisr_conv2d_plan_bf16(SisrConvDesc* d) {
 
 template <int MSUB, int NSUB, int TAG, bool XBF, bool YBF>
 static int launch_conv_bf16_t(const SisrConvDesc* d, hipStream_t st) {
-    static SisrLdsCap cap;
-    if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&conv_mfma_bf16_kernel<MSUB, NSUB, TAG, XBF, YBF>), d->plan.lds_bytes, 64 * 1024)) return e;
     const dim3 grid(d->plan.tiles_x * d->plan.tiles_y, d->plan.n_groups, d->plan.CoutPad / (NSUB * 32));
-    hipLaunchKernelGGL((conv_mfma_bf16_kernel<MSUB, NSUB, TAG, XBF, YBF>), grid, dim3(SISR_BLOCK), d->plan.lds_bytes, st, *d);
-    SISR_CHECK_LAUNCH();
-    return 0;
+    return sisr_launch<conv_mfma_bf16_kernel<MSUB, NSUB, TAG, XBF, YBF>>(grid, dim3(SISR_BLOCK), d->plan.lds_bytes, SISR_LDS_BASE_DEFAULT, st, *d);
 }
 
 // storage combinations: all fp32 | bf16 in, bf16 out | bf16 in, fp32 out (NCHW images) | fp32 in, bf16 out (gradients
@@ -637,20 +622,13 @@ static int launch_conv_bf16(const SisrConvDesc* d, hipStream_t st) {
     return d->y_bf16 ? launch_conv_bf16_t<MSUB, NSUB, TAG, false, true>(d, st) : launch_conv_bf16_t<MSUB, NSUB, TAG, false, false>(d, st);
 }
 
-extern "C" int sisr_conv2d_trunk_eligible(const SisrConvDesc* d);
-int sisr_conv2d_trunk_launch(const SisrConvDesc* d, hipStream_t st);            // conv_trunk.hip
-extern "C" int sisr_conv2d_toimage_eligible(const SisrConvDesc* d);
-int sisr_conv2d_toimage_launch(const SisrConvDesc* d, hipStream_t st);          // conv_toimage.hip
-extern "C" int sisr_conv2d_deep_eligible(const SisrConvDesc* d);
-int sisr_conv2d_deep_launch(const SisrConvDesc* d, hipStream_t st);             // conv_deep.hip
-
 extern "C" int sisr_conv2d_bf16(const SisrConvDesc* d, void* stream) {
     if (!d || !d->x1 || !d->y) return SISR_E_BADARG;
     // the split-K implicit-GEMM family (conv_deep.hip): a descriptor planned for it carries that family's weight image and
     // NOT the generic one, so it either runs there or is refused -- never silently on another kernel
     if (d->deep.enabled && d->wdeep) {
         if (!sisr_conv2d_deep_eligible(d)) return SISR_E_UNSUPPORTED;
-        return sisr_conv2d_deep_launch(d, reinterpret_cast<hipStream_t>(stream));
+        return sisr_conv2d_deep_launch(d, sisr_stream(stream));
     }
     if (!d->wpk) return SISR_E_BADARG;
     if (operand_needs_x2(d->pro_mode) && !d->x2) return SISR_E_BADARG;
@@ -669,7 +647,7 @@ extern "C" int sisr_conv2d_bf16(const SisrConvDesc* d, void* stream) {
         return SISR_E_UNSUPPORTED;
     if (p.CK != BF_CK || p.PS != BF_PS || p.n_tiles <= 0 || p.lds_bytes <= 0 || p.lds_bytes > 160 * 1024)
         return SISR_E_BADARG;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = sisr_stream(stream);
     if (sisr_conv2d_toimage_eligible(d)) return sisr_conv2d_toimage_launch(d, st);      // the generator's last conv (64 -> 3)
     if (sisr_conv2d_trunk_eligible(d)) {                // the generator's trunk geometry: persistent weights-in-registers kernel
         if (d->stat_part && !d->cnt_part) return SISR_E_BADARG;

@@ -630,7 +630,7 @@ extern "C" int sisr_conv2d_deep_plan(SisrConvDesc* d, int32_t target_wg, int32_t
     if (!d) return SISR_E_BADARG;
     SisrDeepPlan& p = d->deep;
     std::memset(&p, 0, sizeof(p));
-    if (const char* e = getenv("SISR_DEEP")) if (e[0] == '0') return SISR_E_UNSUPPORTED;        // A/B switch: keep the generic kernel
+    if (sisr_switch_off("SISR_DEEP")) return SISR_E_UNSUPPORTED;        // A/B switch: keep the generic kernel
     if (d->N <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0) return SISR_E_BADARG;
     if ((d->Cin % 32) || (d->Cout % 64) || d->KH > 3 || d->KW > 3) return SISR_E_UNSUPPORTED;
     if (d->stride != 1 && d->stride != 2) return SISR_E_UNSUPPORTED;
@@ -718,18 +718,10 @@ static int launch_deep_t(const SisrConvDesc* d, hipStream_t st) {
     const int epi = deep_epi_lds(p.BN, images);
     const int lds_main = std::max(deep_main_lds(d, KW), p.split > 1 ? 0 : epi);
     if (lds_main > 160 * 1024) return SISR_E_TOOBIG;
-    static SisrLdsCap cap;
-    if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&conv_deep_kernel<NSUB, KW, NITM, TWO>), lds_main, 0)) return e;
     const dim3 grid(p.n_ntiles, p.tiles_x * p.tiles_q, p.split * p.classes);
-    hipLaunchKernelGGL((conv_deep_kernel<NSUB, KW, NITM, TWO>), grid, dim3(DP_THREADS), lds_main, st, *d);
-    SISR_CHECK_LAUNCH();
-    if (p.split > 1) {
-        static SisrLdsCap capf;
-        if (int e = sisr_raise_lds_cap(capf, reinterpret_cast<const void*>(&conv_deep_finish_kernel<NSUB>), epi, 0)) return e;
-        hipLaunchKernelGGL((conv_deep_finish_kernel<NSUB>), dim3(p.n_ntiles, p.tiles_x * p.tiles_q, p.classes), dim3(DP_THREADS), epi, st, *d);
-        SISR_CHECK_LAUNCH();
-    }
-    return 0;
+    if (int e = sisr_launch<conv_deep_kernel<NSUB, KW, NITM, TWO>>(grid, dim3(DP_THREADS), lds_main, 0, st, *d)) return e;
+    if (p.split <= 1) return 0;
+    return sisr_launch<conv_deep_finish_kernel<NSUB>>(dim3(p.n_ntiles, p.tiles_x * p.tiles_q, p.classes), dim3(DP_THREADS), epi, 0, st, *d);
 }
 
 template <int NSUB, int KW>

@@ -404,20 +404,10 @@ extern "C" int sisr_conv2d_plan(SisrConvDesc* d) {
 
 template <int MSUB, int NSUB, int TAG>
 static int launch_conv(const SisrConvDesc* d, hipStream_t st) {
-    static SisrLdsCap cap;   // raise the dynamic-LDS cap only when a plan needs it
-    if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&conv_mfma_f32_kernel<MSUB, NSUB, TAG>), d->plan.lds_bytes, 64 * 1024)) return e;
     const dim3 grid(d->plan.n_tiles, d->plan.CoutPad / (NSUB * 32));
-    hipLaunchKernelGGL((conv_mfma_f32_kernel<MSUB, NSUB, TAG>), grid, dim3(SISR_BLOCK), d->plan.lds_bytes, st, *d);
-    SISR_CHECK_LAUNCH();
-    return 0;
+    // (the dynamic-LDS cap is raised only when a plan needs more than the default)
+    return sisr_launch<conv_mfma_f32_kernel<MSUB, NSUB, TAG>>(grid, dim3(SISR_BLOCK), d->plan.lds_bytes, SISR_LDS_BASE_DEFAULT, st, *d);
 }
-
-extern "C" int sisr_conv2d_trunk_f32_eligible(const SisrConvDesc* d);
-int sisr_conv2d_trunk_f32_launch(const SisrConvDesc* d, hipStream_t st);      // conv_trunk_f32.hip
-extern "C" int sisr_conv2d_thin_eligible(const SisrConvDesc* d);
-int sisr_conv2d_thin_launch(const SisrConvDesc* d, hipStream_t st);           // conv_thin.hip
-extern "C" int sisr_conv2d_toimage_f32_eligible(const SisrConvDesc* d);
-int sisr_conv2d_toimage_launch(const SisrConvDesc* d, hipStream_t st);        // conv_toimage.hip
 
 extern "C" int sisr_conv2d_f32(const SisrConvDesc* d, void* stream) {
     // fused BatchNorm-backward partials: bf16 kernels and the persistent fp32 trunk kernel only
@@ -430,7 +420,7 @@ extern "C" int sisr_conv2d_f32(const SisrConvDesc* d, void* stream) {
     if (d->res && d->res_bf16) return SISR_E_UNSUPPORTED;
     const SisrConvPlan& p = d->plan;
     if (p.n_tiles <= 0 || p.lds_bytes <= 0 || p.lds_bytes > 160 * 1024) return SISR_E_BADARG;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = sisr_stream(stream);
     if (sisr_conv2d_trunk_f32_eligible(d)) return sisr_conv2d_trunk_f32_launch(d, st);
     if (sisr_conv2d_thin_eligible(d)) return sisr_conv2d_thin_launch(d, st);    // bf16 build: 9x9 over a 3-channel image
     if (sisr_conv2d_toimage_f32_eligible(d)) return sisr_conv2d_toimage_launch(d, st);     // the generator's last conv (64 -> 3)

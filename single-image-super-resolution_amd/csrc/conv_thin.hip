@@ -202,8 +202,7 @@ __global__ void __launch_bounds__(256, 1) conv_thin_kernel(const ThinArgs a) {
 }
 
 extern "C" int sisr_conv2d_thin_eligible(const SisrConvDesc* d) {
-    const char* sw = getenv("SISR_THIN");                       // A/B switch: SISR_THIN=0 keeps the generic kernel
-    if ((sw && sw[0] == '0') || !d) return 0;
+    if (sisr_switch_off("SISR_THIN") || !d) return 0;           // A/B switch: SISR_THIN=0 keeps the generic kernel
     if (d->x_mode != SISR_X_NCHW || d->x_bf16 || d->Cin != 3 || d->Cout != 64 || d->plan.CoutPad != 64) return 0;
     if ((d->KH != 9 && d->KH != 3) || d->KW != d->KH || d->stride != 1 || d->pad_y != (d->KH - 1) / 2 || d->pad_x != d->pad_y) return 0;
     if (d->pro_mode != SISR_PRO_NONE && d->pro_mode != SISR_PRO_TANH_BWD) return 0;

@@ -178,8 +178,7 @@ __global__ void __launch_bounds__(256, 2) conv_toimage_f32_kernel(const ToImageA
 }
 
 static int toimage_common(const SisrConvDesc* d) {
-    const char* sw = getenv("SISR_THIN");                       // A/B switch: SISR_THIN=0 keeps the generic kernels
-    if ((sw && sw[0] == '0') || !d) return 0;
+    if (sisr_switch_off("SISR_THIN") || !d) return 0;           // A/B switch: SISR_THIN=0 keeps the generic kernels
     if (d->Cin != 64 || d->Cout != 3 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_y != 1 || d->pad_x != 1) return 0;
     if (d->x_mode != SISR_X_NHWC || (d->pro_mode != SISR_PRO_NONE && d->pro_mode != SISR_PRO_ACT)) return 0;
     if (d->y_mode != SISR_Y_NCHW || d->y_bf16 || d->res || d->stat_part || d->bnb_part) return 0;

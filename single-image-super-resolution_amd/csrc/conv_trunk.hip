@@ -26,6 +26,7 @@
 #include <cstdlib>
 
 #include "sisr_bf16_stage.h"
+#include "sisr_instr.h"
 
 #define TK_TH 8
 #define TK_TW 16
@@ -42,46 +43,14 @@
 #define TK_ITEMS ((TK_NPIX * 8 + 255) / 256)   // 16-byte staging items per producer thread (6)
 #define TK_YS 68                          // output image: [32 couts][64 pixels + 4] bf16 per wave
 
-// phase timeline, developer build only (make trace; tools/trace_trunk.py): thread 0 stamps the 100 MHz wall clock
-#ifdef SISR_CONV_TRACE
-#define TT_WG 512
-#define TT_SLOTS 128
-__device__ unsigned long long sisr_ttrace_buf[TT_WG * TT_SLOTS];
-#define TT(k)                                                                                                   \
-    do {                                                                                                        \
-        if (threadIdx.x == 0 && blockIdx.x < TT_WG && (k) < TT_SLOTS) sisr_ttrace_buf[blockIdx.x * TT_SLOTS + (k)] = wall_clock64(); \
-    } while (0)
-// producer timeline: thread 256 (first producer wave), slots 64 ..
-#define TTP(k)                                                                                                  \
-    do {                                                                                                        \
-        if (threadIdx.x == 256 && blockIdx.x < TT_WG && 64 + (k) < TT_SLOTS) sisr_ttrace_buf[blockIdx.x * TT_SLOTS + 64 + (k)] = wall_clock64(); \
-    } while (0)
-#define TTC(k) do { if (threadIdx.x == 0 && blockIdx.x < TT_WG) sisr_ttrace_buf[blockIdx.x * TT_SLOTS + (k)] = clock64(); } while (0)
-extern "C" int sisr_ttrace_read(void* dst, int n_u64) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(sisr_ttrace_buf), (size_t)n_u64 * 8, 0, hipMemcpyDeviceToHost);
-}
-#else
-#define TT(k)
-#define TTP(k)
-#define TTC(k)
-#endif
-
-// barrier-wait accounting, developer build only (-DSISR_BARRIER_ACCT; tools/barrier_acct.py): every tile-loop barrier of the
-// forward kernel is bracketed by two s_memtime reads whose difference is summed in SGPRs -- no stores, no LDS drain inside
-// the loop -- and lane 0 of wave 0 (consumer) / wave 4 (producer) stores {loop cycles, cycles spent waiting at barriers}
-#ifdef SISR_BARRIER_ACCT
-__device__ unsigned long long sisr_bacct_buf[512 * 4];
-extern "C" int sisr_bacct_read(void* dst, int n_u64) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(sisr_bacct_buf), (size_t)n_u64 * 8, 0, hipMemcpyDeviceToHost);
-}
-#define BA_DECL unsigned long long ba_wait = 0, ba_t0 = clock64()
-#define BA_SYNC() do { const unsigned long long b0_ = clock64(); __syncthreads(); ba_wait += clock64() - b0_; } while (0)
-#define BA_STORE(slot) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 512) { sisr_bacct_buf[blockIdx.x * 4 + (slot)] = clock64() - ba_t0; sisr_bacct_buf[blockIdx.x * 4 + (slot) + 1] = ba_wait; } } while (0)
-#else
-#define BA_DECL
-#define BA_SYNC() __syncthreads()
-#define BA_STORE(slot)
-#endif
+// phase timeline (make trace; tools/trace_trunk.py): thread 0 -- the first consumer wave -- stamps the 100 MHz wall clock into slots
+// 0 .. 63, thread 256 -- the first producer wave -- into slots 64 ..; TTC: the shader clock at kernel start / end
+SISR_TRACE_BUFFER(sisr_ttrace, 512, 128)
+#define TT(k) SISR_TRACE_STAMP(sisr_ttrace, threadIdx.x == 0, blockIdx.x, k, 128, wall_clock64())
+#define TTP(k) SISR_TRACE_STAMP(sisr_ttrace, threadIdx.x == 256, blockIdx.x, 64 + (k), 128, wall_clock64())
+#define TTC(k) SISR_TRACE_STAMP(sisr_ttrace, threadIdx.x == 0, blockIdx.x, k, 128, clock64())
+// barrier-wait accounting of the forward kernel's tile loop (make acct): wave 0 (consumer) stores into slots 0, 1, wave 4 (producer) 2, 3
+SISR_ACCT_BUFFER(sisr_bacct, 4)
 
 struct TrunkArgs {
     const void *x1, *x2;                  // input operand(s), bf16 NHWC [N][H][W][64]
@@ -184,13 +153,6 @@ __device__ __forceinline__ u32x4 trunk_apply8(u32x4 a, u32x4 b, const f32x8& ka,
 #define TK_THREADS 512
 #ifndef TK_PF
 #define TK_PF 3                           // A-fragment prefetch distance of the data-gradient consumers' MFMA loop, in steps of 2 MFMAs
-#endif
-#ifndef TK_DEFER
-#define TK_DEFER 0                        // A/B variants: 1 = also defer sub-tile 1's epilogue under the next tile's first phase; 2 = one
-                                          // accumulator set, each sub-tile's epilogue right behind its own phase
-#endif
-#ifndef TK_EARLY
-#define TK_EARLY 0
 #endif
 #ifndef TK_PFA
 #define TK_PFA 4                          // ... of the forward consumers' phases, in MFMAs (5 and more spill: 256 VGPRs are in use)
@@ -329,40 +291,24 @@ __global__ void __launch_bounds__(TK_THREADS, 2) conv_trunk_fwd_kernel(const Tru
     __bf16* my_out = out_img + (wave & 3) * (32 * TK_YS);
     const int grp = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
 
-#if !TK_EARLY
+    // (tried: every wave's first loads issued AHEAD of this finalisation, which then ran once per role -- no change)
     if (fin) bn_finalize_in_kernel(a.fin, reinterpret_cast<double*>(lds), kfin, blockIdx.x == 0);
-#endif
     // Two role-specific tile loops with matching barrier counts (a barrier only counts arriving waves).  Written as ONE
     // loop with a role branch inside, the register allocator carries the consumers' 144 weight registers through the
     // producers' code (and the producers' staging registers through the consumers').
     if (!consumer) {
         // ---- producers: tile T + 1 into the other buffer while the consumers work on tile T ------------------------------
         int T = t_first;
-#if TK_EARLY
-        // every wave's first memory requests go out BEFORE the BatchNorm finalisation and the per-channel constants: the
-        // producers' first two tiles (and the consumers' weights) are raw loads that depend on nothing computed here.  (The
-        // finalisation is instantiated once per role: as common code between two role branches it would keep both roles'
-        // registers live at once.)
-        halo_map_init(hm, ptid, a.W);
-        issue(T, stA);
-        issue(T + t_step, stB);
-        if (fin) bn_finalize_in_kernel(a.fin, reinterpret_cast<double*>(lds), kfin, blockIdx.x == 0);
-        slope = a.slope_p ? a.slope_p[0] : a.slope;
-        easy_slope = slope >= 0.f && slope <= 1.f;
-        init_constants();
-        TTP(0);
-#else
         init_producer();
         init_constants();
         TTP(0);
         issue(T, stA);
         issue(T + t_step, stB);
-#endif
         TTP(1);
         if (T < a.total) commit(lds, stA);
         TTP(2);
         __syncthreads();
-        BA_DECL;
+        SISR_ACCT_DECL;
         // unrolled by two: each staging set has a fixed name in each half (stB holds tile T + grid in the first)
         int cur = 0;
         [[maybe_unused]] int it = 0;
@@ -372,7 +318,7 @@ __global__ void __launch_bounds__(TK_THREADS, 2) conv_trunk_fwd_kernel(const Tru
             TTP(5 + 6 * it);
             if (T + t_step < a.total) commit(lds + (cur ^ 1) * TK_HALO_BYTES, stB);
             TTP(8 + 6 * it);
-            BA_SYNC();
+            SISR_ACCT_SYNC();
             TTP(9 + 6 * it);
             T += t_step; cur ^= 1; ++it;
             if (T >= a.total) break;
@@ -381,7 +327,7 @@ __global__ void __launch_bounds__(TK_THREADS, 2) conv_trunk_fwd_kernel(const Tru
             TTP(5 + 6 * it);
             if (T + t_step < a.total) commit(lds + (cur ^ 1) * TK_HALO_BYTES, stA);
             TTP(8 + 6 * it);
-            BA_SYNC();
+            SISR_ACCT_SYNC();
             TTP(9 + 6 * it);
             T += t_step; cur ^= 1; ++it;
         }
@@ -389,12 +335,9 @@ __global__ void __launch_bounds__(TK_THREADS, 2) conv_trunk_fwd_kernel(const Tru
         // role join below carries no pending load -- with one, the compiler's wait-count bookkeeping makes the consumers
         // drain their output stores, ~2 us, before the statistics tail)
         __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0)
-        if (wave == 4) BA_STORE(2);
+        if (wave == 4) SISR_ACCT_STORE(sisr_bacct, 2);
     } else {
         init_consumer();
-#if TK_EARLY
-        if (fin) bn_finalize_in_kernel(a.fin, reinterpret_cast<double*>(lds), kfin, blockIdx.x == 0);
-#endif
         TT(2);
 #ifdef SISR_CONV_TRACE
         __builtin_amdgcn_s_waitcnt(0x0F70);                  // (trace build: when the weights have landed)
@@ -418,9 +361,6 @@ __global__ void __launch_bounds__(TK_THREADS, 2) conv_trunk_fwd_kernel(const Tru
             //           [32 couts][64 pixels] image (pixels 32 ms + 8 q + 4 kk .. + 3 of cout l31)
             //   4, 5    16-pixel block pb = 2 ms + (sl - 4) = tile row 4 g + pb: transposing reads, one 16-byte store
             auto epi = [&](int sl, const f32x16& acc, int ms, bool first, int n, int ty, int tx) {
-#ifdef SISR_ABLATE_EPI          // timing-only ablation (no output): the consumers' epilogue is skipped
-                if (a.N > 0) { asm volatile("" :: "v"(acc[0])); return; }
-#endif
                 if (sl < 4) {
                     const int q = sl;
                     // (the accumulators start from zero -- a literal operand of the first MFMA -- and the bias joins here: an
@@ -473,87 +413,23 @@ __global__ void __launch_bounds__(TK_THREADS, 2) conv_trunk_fwd_kernel(const Tru
                     af[st] = *reinterpret_cast<const bf16x8*>(pa + (t / 3) * TK_RP + (t % 3) * TK_PSB + j * 32);
                 };
 #pragma unroll
-#ifdef SISR_ABLATE_AREADS
-                for (int st = 0; st < TK_PFA; st += 2) fetch(st);
-#else
                 for (int st = 0; st < TK_PFA; ++st) fetch(st);
-#endif
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int st = 0; st < 36; ++st) {
-#ifdef SISR_ABLATE_AREADS      // timing-only ablation (wrong results): every second A fragment is not fetched but reused
-                    if (st + TK_PFA < 36 && ((st + TK_PFA) & 1) == 0) fetch(st + TK_PFA);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[st & ~1], bw[st >> 2][st & 3], acc, 0, 0, 0);
-#elif defined(SISR_ABLATE_MFMA)  // timing-only ablation (wrong results): fragment reads without the matrix instructions
-                    if (st + TK_PFA < 36) fetch(st + TK_PFA);
-                    asm volatile("" :: "v"(af[st]), "v"(bw[st >> 2][st & 3]));
-#else
                     if (st + TK_PFA < 36) fetch(st + TK_PFA);
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[st], bw[st >> 2][st & 3], acc, 0, 0, 0);
-#endif
                     under(st);
                     __builtin_amdgcn_sched_barrier(0);              // the source order IS the software pipeline
                 }
             };
             int cur = 0, it = 0;
             int n, ty, tx;
-            BA_DECL;
-#if TK_DEFER == 1
-            // sub-tile 1's epilogue deferred under the NEXT tile's first phase (its accumulators live across the barrier)
-            int T = t_first, pn = 0, pty = 0, ptx = 0;
-            if (T < a.total) {
-                // first tile (peeled): nothing to finish under its first phase
-                TT(4);
-                tile_coords(T, n, ty, tx);
-                phase(acc0, lds, 0, [&](int) {});
-                TT(6);
-                phase(acc1, lds, 1, [&](int c) { const int sl = slice_at(c); if (sl >= 0) epi(sl, acc0, 0, true, n, ty, tx); });
-                TT(8);
-                BA_SYNC();            // the next tile's image is complete; the consumers have finished reading this one
-                TT(9);
-                pn = n; pty = ty; ptx = tx;
-                T += t_step; cur ^= 1; ++it;
-            }
-            for (; T < a.total; T += t_step, cur ^= 1, ++it) {
-                TT(4 + 6 * it);
-                tile_coords(T, n, ty, tx);
-                const unsigned char* ib = lds + cur * (TK_HALO_BYTES);
-                phase(acc0, ib, 0, [&](int c) { const int sl = slice_at(c); if (sl >= 0) epi(sl, acc1, 1, false, pn, pty, ptx); });
-                TT(6 + 6 * it);
-                phase(acc1, ib, 1, [&](int c) { const int sl = slice_at(c); if (sl >= 0) epi(sl, acc0, 0, false, n, ty, tx); });
-                TT(8 + 6 * it);
-                BA_SYNC();
-                TT(9 + 6 * it);
-                pn = n; pty = ty; ptx = tx;
-            }
-            if (it > 0) {                                           // the last tile's second sub-tile
-#pragma unroll
-                for (int sl = 0; sl < 6; ++sl) epi(sl, acc1, 1, false, pn, pty, ptx);
-            }
-#elif TK_DEFER == 2
-            // ONE accumulator set: each sub-tile's epilogue follows its own 36 MFMAs.  The 16 registers this frees go to the
-            // A-fragment prefetch (8 instead of 4 in flight): the consumers are bound by LDS LATENCY at a prefetch of 4 --
-            // ablations (tools/barrier_acct.py builds): without any MFMA the 72 fragment reads of a tile still take ~2,000
-            // cycles (4 in flight x ~110 cycles each), halving the reads at the same depth changes nothing
-            for (int T = t_first; T < a.total; T += t_step, cur ^= 1, ++it) {
-                TT(4 + 6 * it);
-                tile_coords(T, n, ty, tx);
-                const unsigned char* ib = lds + cur * (TK_HALO_BYTES);
-                const bool first = it == 0;
-                phase(acc0, ib, 0, [&](int) {});
-#pragma unroll
-                for (int sl = 0; sl < 6; ++sl) epi(sl, acc0, 0, first, n, ty, tx);
-                TT(6 + 6 * it);
-                phase(acc0, ib, 1, [&](int) {});
-#pragma unroll
-                for (int sl = 0; sl < 6; ++sl) epi(sl, acc0, 1, false, n, ty, tx);
-                TT(8 + 6 * it);
-                BA_SYNC();
-                TT(9 + 6 * it);
-            }
-#else
+            SISR_ACCT_DECL;
             // sub-tile 0's epilogue under sub-tile 1's MFMAs; sub-tile 1's own epilogue follows its phase (no accumulator
-            // is carried around the loop: that costs the allocator 16 registers, which buy a deeper A prefetch here)
+            // is carried around the loop: that costs the allocator 16 registers, which buy a deeper A prefetch here).  Tried
+            // and dropped: sub-tile 1's epilogue deferred under the NEXT tile's first phase (those 16 registers of phi copies,
+            // slower), and ONE accumulator set with each epilogue right behind its own phase (the matrix pipe idles meanwhile)
             for (int T = t_first; T < a.total; T += t_step, cur ^= 1, ++it) {
                 TT(4 + 6 * it);
                 tile_coords(T, n, ty, tx);
@@ -565,12 +441,11 @@ __global__ void __launch_bounds__(TK_THREADS, 2) conv_trunk_fwd_kernel(const Tru
 #pragma unroll
                 for (int sl = 0; sl < 6; ++sl) epi(sl, acc1, 1, false, n, ty, tx);
                 TT(8 + 6 * it);
-                BA_SYNC();
+                SISR_ACCT_SYNC();
                 TT(9 + 6 * it);
             }
-#endif
             TT(1);
-            if (wave == 0) BA_STORE(0);
+            if (wave == 0) SISR_ACCT_STORE(sisr_bacct, 0);
         };
         if (a.stat_part != nullptr) consumer_loop(std::true_type{});
         else consumer_loop(std::false_type{});
@@ -945,12 +820,11 @@ static int trunk_grid(const SisrConvDesc* d) {
 
 // 1 when this descriptor (geometry + storage flags + fusions requested) can run on the trunk kernel
 extern "C" int sisr_conv2d_trunk_eligible(const SisrConvDesc* d) {
-    const char* sw = getenv("SISR_TRUNK");                      // A/B switch: SISR_TRUNK=0 keeps the generic kernel
-    if (!d || (sw && sw[0] == '0')) return 0;
+    if (!d || sisr_switch_off("SISR_TRUNK")) return 0;         // A/B switch: SISR_TRUNK=0 keeps the generic kernel
     if (d->Cin != 64 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_y != 1 || d->pad_x != 1) return 0;
     // Cout = 64 (trunk), or 256 stored through PixelShuffle(2) -- the upscale conv, forward role without statistics
-    const char* swu = getenv("SISR_TRUNK_UP");                 // A/B switch for the upscale conv alone
-    const bool up = !(swu && swu[0] == '0') && d->Cout == 256 && d->y_mode == SISR_Y_NHWC_SHUFFLE2 && d->plan.CoutPad == 256 && !d->stat_part && !d->res &&
+    const bool up_off = sisr_switch_off("SISR_TRUNK_UP");      // A/B switch for the upscale conv alone
+    const bool up = !up_off && d->Cout == 256 && d->y_mode == SISR_Y_NHWC_SHUFFLE2 && d->plan.CoutPad == 256 && !d->stat_part && !d->res &&
                     !d->bnb_part && d->pro_mode != SISR_PRO_RES_AFFINE && !d->fin_stat &&
                     (d->pro_mode == SISR_PRO_NONE || d->pro_mode == SISR_PRO_ACT || d->pro_mode == SISR_PRO_AFFINE_ACT);
     if (!up && (d->Cout != 64 || d->y_mode != SISR_Y_NHWC)) return 0;
@@ -974,7 +848,6 @@ extern "C" int sisr_conv2d_trunk_eligible(const SisrConvDesc* d) {
 
 // rows of stat_part / cnt_part (or bnb_part) a launch of this descriptor writes: the trunk kernel writes one per
 // workgroup, the generic kernels one per tile (plan.n_tiles)
-int sisr_conv2d_deep_parts(const SisrConvDesc* d);            // conv_deep.hip
 extern "C" int sisr_conv2d_bf16_parts(const SisrConvDesc* d) {
     if (!d) return SISR_E_BADARG;
     if (d->deep.enabled && d->wdeep) return sisr_conv2d_deep_parts(d);
@@ -985,21 +858,13 @@ extern "C" int sisr_conv2d_bf16_parts(const SisrConvDesc* d) {
 template <int PRO>
 static int launch_trunk_fwd(const TrunkArgs& a, int grid, hipStream_t st) {
     constexpr int lds_bytes = 2 * TK_HALO_BYTES + 4 * 32 * TK_YS * 2 + 4 * 32 * 3 * 4 + 128 * 4;
-    static SisrLdsCap cap;
-    if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&conv_trunk_fwd_kernel<PRO>), lds_bytes)) return e;
-    hipLaunchKernelGGL((conv_trunk_fwd_kernel<PRO>), dim3(grid), dim3(TK_THREADS), lds_bytes, st, a);
-    SISR_CHECK_LAUNCH();
-    return 0;
+    return sisr_launch<conv_trunk_fwd_kernel<PRO>>(dim3(grid), dim3(TK_THREADS), lds_bytes, 0, st, a);
 }
 
 template <int PRO>
 static int launch_trunk_bwd(const TrunkArgs& a, int grid, bool images, hipStream_t st) {
     const int lds_bytes = 2 * TK_HALO_BYTES + 4 * 32 * TK_YS * 2 + TK_RED_BYTES + (images ? 4 * TK_IMG : 0);
-    static SisrLdsCap cap;
-    if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&conv_trunk_bwd_kernel<PRO>), lds_bytes, 0)) return e;
-    hipLaunchKernelGGL((conv_trunk_bwd_kernel<PRO>), dim3(grid), dim3(TK_THREADS), lds_bytes, st, a);
-    SISR_CHECK_LAUNCH();
-    return 0;
+    return sisr_launch<conv_trunk_bwd_kernel<PRO>>(dim3(grid), dim3(TK_THREADS), lds_bytes, 0, st, a);
 }
 
 // called by sisr_conv2d_bf16 for eligible descriptors

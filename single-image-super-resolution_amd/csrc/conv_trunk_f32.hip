@@ -22,6 +22,7 @@
 // The two workgroups of a cout pair walk the same pixel tiles and share one statistics row: each writes its 32 channels.
 #include "sisr_dev.h"
 #include "sisr_bf16_stage.h"
+#include "sisr_instr.h"
 
 typedef unsigned cf_u32x4 __attribute__((ext_vector_type(4)));
 
@@ -29,15 +30,6 @@ typedef unsigned cf_u32x4 __attribute__((ext_vector_type(4)));
 #include <cstdlib>
 #include <type_traits>
 
-#ifndef CF_XCD_PAIRS
-#define CF_XCD_PAIRS 1
-#endif
-#ifndef CF_CHAINS
-#define CF_CHAINS 1
-#endif
-#ifndef CF_PRODPRIO
-#define CF_PRODPRIO 0
-#endif
 #define CF_TH 8
 #define CF_TW 16
 #define CF_IH (CF_TH + 2)
@@ -54,25 +46,14 @@ typedef unsigned cf_u32x4 __attribute__((ext_vector_type(4)));
 #define CF_KROWP 100                        // packed fp32 weights: [chunk][r][cout 64][krow = s * 33 + ci], rows of 100
 #define CF_PS 33
 
-// phase timeline, developer build only (make trace; tools/trace_trunk.py with ROLE=fwd SISR_PRECISION=fp32)
-#ifdef SISR_CONV_TRACE
-__device__ unsigned long long sisr_cftrace_buf[512 * 128];
-#define CFT(k) do { if (threadIdx.x == 0 && blockIdx.x < 512 && (k) < 64) sisr_cftrace_buf[blockIdx.x * 128 + (k)] = wall_clock64(); } while (0)
-#define CFTP(k) do { if (threadIdx.x == 256 && blockIdx.x < 512 && (k) < 64) sisr_cftrace_buf[blockIdx.x * 128 + 64 + (k)] = wall_clock64(); } while (0)
-// shader-clock stamps (s_memtime) at kernel start / end: in-kernel clock = delta(s_memtime) / delta(wall) x 100 MHz
-__device__ unsigned long long sisr_cfclk_buf[512 * 2];
-#define CFTC(k) do { if (threadIdx.x == 0 && blockIdx.x < 512) sisr_cfclk_buf[blockIdx.x * 2 + ((k) - 60)] = clock64(); } while (0)
-extern "C" int sisr_cfclk_read(void* dst, int n_u64) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(sisr_cfclk_buf), (size_t)n_u64 * 8, 0, hipMemcpyDeviceToHost);
-}
-extern "C" int sisr_cftrace_read(void* dst, int n_u64) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(sisr_cftrace_buf), (size_t)n_u64 * 8, 0, hipMemcpyDeviceToHost);
-}
-#else
-#define CFT(k)
-#define CFTP(k)
-#define CFTC(k)
-#endif
+// phase timeline (make trace; tools/trace_trunk.py with ROLE=fwd SISR_PRECISION=fp32): thread 0 stamps slots 0 .. 63, thread 256
+// (first producer wave) slots 64 ..
+SISR_TRACE_BUFFER(sisr_cftrace, 512, 128)
+#define CFT(k) SISR_TRACE_STAMP(sisr_cftrace, threadIdx.x == 0, blockIdx.x, k, 64, wall_clock64())
+#define CFTP(k) SISR_TRACE_STAMP(sisr_cftrace, threadIdx.x == 256, blockIdx.x, 64 + (k), 128, wall_clock64())
+// shader-clock stamps (s_memtime) at kernel start / end (k = 60, 61): in-kernel clock = delta(s_memtime) / delta(wall) x 100 MHz
+SISR_TRACE_BUFFER(sisr_cfclk, 512, 2)
+#define CFTC(k) SISR_TRACE_STAMP(sisr_cfclk, threadIdx.x == 0, blockIdx.x, (k) - 60, 2, clock64())
 
 struct CTrunkF32Args {
     const float *x1, *x2;
@@ -134,14 +115,11 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
     const int l31 = lane & 31, kk = lane >> 5;
     // block of 32 output channels, pixel-tile stream.  The workgroups of one stream stage the SAME halo tiles in the same order: they
     // sit 8 apart in the grid, i.e. (workgroups being dealt round-robin over the 8 XCDs) on ONE XCD, so that the second reader of
-    // a tile finds it in that XCD's L2 instead of fetching it again over the fabric
-#if CF_XCD_PAIRS
+    // a tile finds it in that XCD's L2 instead of fetching it again over the fabric (with the partners adjacent in the grid, i.e. on
+    // different XCDs, a forward launch read 103 MB instead of 53)
     const bool xcd = (a.streams & 7) == 0;
     const int hc = xcd ? (blockIdx.x >> 3) & ((1 << a.glog) - 1) : blockIdx.x & ((1 << a.glog) - 1);
     const int stream = xcd ? (blockIdx.x & 7) | ((blockIdx.x >> (3 + a.glog)) << 3) : blockIdx.x >> a.glog;
-#else
-    const int hc = blockIdx.x & ((1 << a.glog) - 1), stream = blockIdx.x >> a.glog;
-#endif
     const unsigned tbytes = (unsigned)a.N * (unsigned)a.H * (unsigned)a.W * 256u;
     constexpr bool TWO = PRO == SISR_PRO_BNBWD || PRO == SISR_PRO_BNACT_BWD || PRO == SISR_PRO_RES_AFFINE || PRO == SISR_PRO_ACT_BWD;
     constexpr bool SUM = PRO == SISR_PRO_RES_AFFINE;          // skip-sum prologue: lrelu(x1) + (a x2 + d), stored back once
@@ -215,9 +193,6 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
     const int n_stages = 2 * n_mine;                                                               // (tile, channel half)
 
     if (!consumer) {
-#if CF_PRODPRIO
-        __builtin_amdgcn_s_setprio(3);
-#endif
         // ---- producers: stage j + 1 = (tile (j + 1) / 2, channel half (j + 1) % 2) while the consumers multiply stage j -----
         // item k of thread pt: halo pixel pt / 8 + 32 k, channels 4 (pt % 8) .. + 3 of the 32-channel half
         const int pt = tid & 255, quad = tid & 7, m0 = pt >> 3;
@@ -383,9 +358,6 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
         int st_n = 0;
         const __amdgpu_buffer_rsrc_t ry = cf_rsrc(a.y, a.shuffle ? 4u * tbytes : tbytes), rr = cf_rsrc(a.res != nullptr ? a.res : a.y, tbytes);
         f32x16 acc;
-#if CF_CHAINS == 2
-        f32x16 acc2;                                          // second accumulation chain (odd K steps), folded into acc before the epilogue
-#endif
         f32x16 rv, xv;                                        // residual / BatchNorm-input values of the tile (requested a stage early)
         const bool has_x = a.bnb_part != nullptr;
         const __amdgpu_buffer_rsrc_t rxb = cf_rsrc(has_x ? a.bnb_x : a.y, tbytes);
@@ -410,10 +382,6 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
             if (q == 0) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[i] = bv;
-#if CF_CHAINS == 2
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc2[i] = 0.f;
-#endif
             } else {
                 // the skip gradient and the BatchNorm input of this tile, in accumulator layout: in flight behind the second
                 // half's MFMAs
@@ -447,15 +415,9 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
 #pragma unroll
                     for (int ks = 0; ks < 2; ++ks) {
                         ah[t][ks] = *reinterpret_cast<const bf16x8*>(pa + 32 * ks);
-#ifdef CF_ABLATE_BREADS        // timing-only (wrong results): the weight fragments are not read from LDS (what registers would give)
-                        al[t][ks] = *reinterpret_cast<const bf16x8*>(pa + 64 + 32 * ks);
-                        bh[t][ks] = al[t][ks]; bl[t][ks] = ah[t][ks];
-                        asm volatile("" :: "v"(pb));
-#else
                         bh[t][ks] = *reinterpret_cast<const bf16x8*>(pb + 32 * ks);
                         al[t][ks] = *reinterpret_cast<const bf16x8*>(pa + 64 + 32 * ks);
                         bl[t][ks] = *reinterpret_cast<const bf16x8*>(pb + 64 + 32 * ks);
-#endif
                     }
                 };
                 fetch_s(0);
@@ -474,6 +436,8 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
                 }
             } else {
             f32x4 af[18][2], bf[18][2];                     // half-tap u: steps s0 .. s0 + 7 = two 16-byte reads per operand
+            // (one accumulation chain: a second one over the odd K steps, folded in before the epilogue, was tried and not kept; so
+            // was a raised wave priority for the producers)
             auto fetch = [&](int u) {
                 const int t = u >> 1, s0 = 8 * (u & 1);
 #pragma unroll
@@ -489,28 +453,13 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
             for (int u = 0; u < 18; ++u) {
                 if (u + 2 < 18) fetch(u + 2);
 #pragma unroll
-#if CF_CHAINS == 2
-                for (int s = 0; s < 8; s += 2) {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u][s >> 2][s & 3], bf[u][s >> 2][s & 3], acc, 0, 0, 0);
-                    acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u][s >> 2][(s & 3) + 1], bf[u][s >> 2][(s & 3) + 1], acc2, 0, 0, 0);
-                }
-#else
                 for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u][s >> 2][s & 3], bf[u][s >> 2][s & 3], acc, 0, 0, 0);
-#endif
                 if (u + 2 < 18) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
             }
             }
             CFT(6 + 6 * j);
-#ifdef CF_ABLATE_EPI            // timing-only (no output): what the consumers' epilogue costs
-            if (q == 1 && a.N < 0) {
-#else
             if (q == 1) {
-#endif
-#if CF_CHAINS == 2
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[i] += acc2[i];
-#endif
                 // ---- epilogue of the tile: skip gradient, statistics, stores (128 contiguous bytes per pixel and half wave) ---
                 if (a.res != nullptr) {
 #pragma unroll
@@ -558,9 +507,6 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
                                                           obase + (unsigned)((p >> 4) * orow + (p & 15) * ocol), 0, 0);
                 }
             }
-#ifdef CF_ABLATE_EPI
-            asm volatile("" :: "v"(acc));
-#endif
             CFT(8 + 6 * j);
             __syncthreads();
             CFT(9 + 6 * j);
@@ -642,14 +588,12 @@ static int cf_streams(const SisrConvDesc* d) {
 
 // 1: forward role, 2: data-gradient role, 0: not this kernel's geometry / fusions
 extern "C" int sisr_conv2d_trunk_f32_eligible(const SisrConvDesc* d) {
-    const char* sw = getenv("SISR_TRUNK");                      // A/B switch: SISR_TRUNK=0 keeps the generic kernel
-    if (!d || (sw && sw[0] == '0')) return 0;
-    const char* sw2 = getenv("SISR_TRUNK_F32CONV");
-    if (sw2 && sw2[0] == '0') return 0;
-    const char* swu = getenv("SISR_TRUNK_UP");                 // A/B switch for the upscale conv alone
+    if (!d || sisr_switch_off("SISR_TRUNK")) return 0;         // A/B switch: SISR_TRUNK=0 keeps the generic kernel
+    if (sisr_switch_off("SISR_TRUNK_F32CONV")) return 0;
+    const bool up_off = sisr_switch_off("SISR_TRUNK_UP");      // A/B switch for the upscale conv alone
     // the upscale conv's data gradient: 256 -> 64 over the un-shuffling view of the gradient, activation-backward prologue: four
     // launches of the data-gradient role, one per PixelShuffle phase (see CTrunkF32Args.xsc)
-    if (!(swu && swu[0] == '0') && d->Cin == 256 && d->Cout == 64 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_y == 1 && d->pad_x == 1 &&
+    if (!up_off && d->Cin == 256 && d->Cout == 64 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_y == 1 && d->pad_x == 1 &&
         d->x_mode == SISR_X_NHWC_UNSHUFFLE2 && d->pro_mode == SISR_PRO_ACT_BWD && d->x2 && d->y_mode == SISR_Y_NHWC && !d->x_bf16 && !d->y_bf16 &&
         !d->res_bf16 && d->Ho == d->H && d->Wo == d->W && !(d->H % CF_TH) && !(d->W % CF_TW) && d->y_sy == 1 && d->y_sx == 1 && !d->y_oy && !d->y_ox &&
         d->y_H == d->Ho && d->y_W == d->Wo && d->epi_act == SISR_EPI_NONE && d->plan.CK == 32 && d->plan.PS == CF_PS && d->plan.KROWP == CF_KROWP &&
@@ -658,7 +602,7 @@ extern "C" int sisr_conv2d_trunk_f32_eligible(const SisrConvDesc* d) {
         return 2;
     if (d->Cin != 64 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_y != 1 || d->pad_x != 1) return 0;
     // Cout = 64 (trunk), or 256 stored through PixelShuffle(2) -- the upscale conv, forward role without statistics
-    const bool up = !(swu && swu[0] == '0') && d->Cout == 256 && d->y_mode == SISR_Y_NHWC_SHUFFLE2 && d->plan.CoutPad == 256 && !d->stat_part &&
+    const bool up = !up_off && d->Cout == 256 && d->y_mode == SISR_Y_NHWC_SHUFFLE2 && d->plan.CoutPad == 256 && !d->stat_part &&
                     !d->res && !d->bnb_part && !d->fin_stat &&
                     (d->pro_mode == SISR_PRO_NONE || d->pro_mode == SISR_PRO_ACT || d->pro_mode == SISR_PRO_AFFINE_ACT);
     if (!up && (d->Cout != 64 || d->y_mode != SISR_Y_NHWC || d->plan.CoutPad != 64)) return 0;
@@ -695,11 +639,7 @@ extern "C" int sisr_conv2d_f32_bnb_parts(const SisrConvDesc* d) {
 template <int PRO, bool SPLIT>
 static int launch_cf_t(const CTrunkF32Args& a, hipStream_t st) {
     constexpr int lds_bytes = 2 * CF_WCHUNK_BYTES + 2 * CF_HALO_BYTES + 4 * 32 * 3 * 4 + 128 * 4;
-    static SisrLdsCap cap;
-    if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&conv_trunk_f32_kernel<PRO, SPLIT>), lds_bytes)) return e;
-    hipLaunchKernelGGL((conv_trunk_f32_kernel<PRO, SPLIT>), dim3(a.streams << a.glog), dim3(CF_THREADS), lds_bytes, st, a);
-    SISR_CHECK_LAUNCH();
-    return 0;
+    return sisr_launch<conv_trunk_f32_kernel<PRO, SPLIT>>(dim3(a.streams << a.glog), dim3(CF_THREADS), lds_bytes, 0, st, a);
 }
 template <int PRO>
 static int launch_cf(const CTrunkF32Args& a, bool split, hipStream_t st) {

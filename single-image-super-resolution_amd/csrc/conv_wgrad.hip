@@ -255,20 +255,9 @@ extern "C" int sisr_wgrad_plan(SisrWgradDesc* d, int32_t max_pixel_blocks) {
 
 template <int NACC>
 static int launch_wgrad(const SisrWgradDesc* d, hipStream_t st) {
-    static SisrLdsCap cap;
-    if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&wgrad_mfma_f32_kernel<NACC>), d->lds_bytes, 64 * 1024)) return e;
     const dim3 grid(d->grid_x, d->n_chunk * (d->CoutPad / (d->NJ * 32)));
-    hipLaunchKernelGGL(wgrad_mfma_f32_kernel<NACC>, grid, dim3(SISR_BLOCK), d->lds_bytes, st, *d);
-    SISR_CHECK_LAUNCH();
-    return 0;
+    return sisr_launch<wgrad_mfma_f32_kernel<NACC>>(grid, dim3(SISR_BLOCK), d->lds_bytes, SISR_LDS_BASE_DEFAULT, st, *d);
 }
-
-extern "C" int sisr_wgrad_trunk_f32_eligible(const SisrWgradDesc* d);
-int sisr_wgrad_trunk_f32_launch(const SisrWgradDesc* d, hipStream_t st);      // wgrad_trunk_f32.hip
-extern "C" int sisr_wgrad_thin_eligible(const SisrWgradDesc* d);
-int sisr_wgrad_thin_launch(const SisrWgradDesc* d, hipStream_t st);           // wgrad_thin.hip
-extern "C" int sisr_wgrad_toimage_f32_eligible(const SisrWgradDesc* d);
-int sisr_wgrad_toimage_f32_launch(const SisrWgradDesc* d, hipStream_t st);    // wgrad_toimage.hip
 
 extern "C" int sisr_conv2d_wgrad_f32(const SisrWgradDesc* d, void* stream) {
     if (!d || !d->x1 || !d->g1 || !d->slab) return SISR_E_BADARG;
@@ -277,7 +266,7 @@ extern "C" int sisr_conv2d_wgrad_f32(const SisrWgradDesc* d, void* stream) {
     if (d->slab_stride < d->slab_elems) return SISR_E_BADARG;
     if (d->grid_x <= 0 || d->lds_bytes <= 0 || d->lds_bytes > 160 * 1024 || d->KH * d->NT > WG_NACC)
         return SISR_E_BADARG;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = sisr_stream(stream);
     if (sisr_wgrad_trunk_f32_eligible(d)) return sisr_wgrad_trunk_f32_launch(d, st);
     if (sisr_wgrad_thin_eligible(d)) return sisr_wgrad_thin_launch(d, st);      // bf16 build: the first conv (3-channel image)
     if (sisr_wgrad_toimage_f32_eligible(d)) return sisr_wgrad_toimage_f32_launch(d, st);    // the last conv (64 -> 3), fp32 tensors
@@ -300,7 +289,7 @@ extern "C" int sisr_slab_reduce_f32(const float* slab, float* out, int32_t n_sla
     if (!slab || !out || n_slabs <= 0 || elems <= 0) return SISR_E_BADARG;
     if ((elems & 3) || (lead_bf16 & 3) || lead_bf16 < 0 || lead_bf16 > elems) return SISR_E_BADARG;   // 16-byte units
     const int blocks = (int)((elems / 4 + SR_COLS - 1) / SR_COLS);
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(SISR_BLOCK), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream),
                        slab, out, n_slabs, elems, lead_bf16);
     SISR_CHECK_LAUNCH();
     return 0;
@@ -325,7 +314,7 @@ extern "C" int sisr_slab_reduce_multi(const void* const* slabs, void* const* out
             blocks += (int)((elems[i] / 4 + cols - 1) / cols);
         }
         j.first_block[j.n] = blocks;
-        hipLaunchKernelGGL(slab_reduce_multi_kernel, dim3(blocks), dim3(SISR_BLOCK), 0, reinterpret_cast<hipStream_t>(stream), j);
+        hipLaunchKernelGGL(slab_reduce_multi_kernel, dim3(blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream), j);
         SISR_CHECK_LAUNCH();
     }
     return 0;

@@ -172,7 +172,6 @@ __global__ void __launch_bounds__(256) fc1_dgrad_kernel(const float* __restrict_
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
-#define S_(s) reinterpret_cast<hipStream_t>(s)
 
 extern "C" int sisr_fc_head_ws_floats(int32_t N) { return FH_KQ * FH_B * N; }
 
@@ -182,9 +181,9 @@ extern "C" int sisr_fc_head_forward(const float* x, const float* W1, const float
                                     float* h1, float* y, float* ws, int32_t B, int32_t K, int32_t N, void* stream) {
     if (!x || !W1 || !h1 || !ws || B <= 0 || B > FH_B || K <= 0 || (K & 15) || N <= 0 || (N & 15)) return SISR_E_BADARG;
     if (W2 && !y) return SISR_E_BADARG;
-    hipLaunchKernelGGL(fc1_forward_kernel, dim3(N / 16, FH_KQ), dim3(256), 0, S_(stream), x, 1.f, W1, ws, B, K, N);
+    hipLaunchKernelGGL(fc1_forward_kernel, dim3(N / 16, FH_KQ), dim3(256), 0, sisr_stream(stream), x, 1.f, W1, ws, B, K, N);
     SISR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fc_head_finish_kernel, dim3(B), dim3(256), 0, S_(stream), ws, b1, h1, W2, b2, slope, y, N);
+    hipLaunchKernelGGL(fc_head_finish_kernel, dim3(B), dim3(256), 0, sisr_stream(stream), ws, b1, h1, W2, b2, slope, y, N);
     SISR_CHECK_LAUNCH();
     return 0;
 }
@@ -193,7 +192,7 @@ extern "C" int sisr_fc_head_forward(const float* x, const float* W1, const float
 extern "C" int sisr_fc_head_backward(const float* g, const float* y, const float* h1, const float* W2, float slope, float* d1,
                                      float* dW2, float* db2, float* db1, int32_t B, int32_t N, void* stream) {
     if (!g || !y || !h1 || !W2 || !d1 || !dW2 || B <= 0 || B > FH_B || N <= 0) return SISR_E_BADARG;
-    hipLaunchKernelGGL(fc_head_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, S_(stream), g, y, h1, W2, slope, d1, dW2, db2, db1, B, N);
+    hipLaunchKernelGGL(fc_head_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, sisr_stream(stream), g, y, h1, W2, slope, d1, dW2, db2, db1, B, N);
     SISR_CHECK_LAUNCH();
     return 0;
 }
@@ -201,7 +200,7 @@ extern "C" int sisr_fc_head_backward(const float* g, const float* y, const float
 // dx [B][K] = d1 [B][N] W1 [N][K]
 extern "C" int sisr_fc1_dgrad(const float* d1, const float* W1, float* dx, int32_t B, int32_t K, int32_t N, void* stream) {
     if (!d1 || !W1 || !dx || B <= 0 || B > FH_B || K <= 0 || (K & 63) || N <= 0 || (N % (16 * FH_UNROLL))) return SISR_E_BADARG;
-    hipLaunchKernelGGL(fc1_dgrad_kernel, dim3(K / 64), dim3(256), 0, S_(stream), d1, W1, dx, B, K, N);
+    hipLaunchKernelGGL(fc1_dgrad_kernel, dim3(K / 64), dim3(256), 0, sisr_stream(stream), d1, W1, dx, B, K, N);
     SISR_CHECK_LAUNCH();
     return 0;
 }
@@ -267,7 +266,7 @@ __global__ void __launch_bounds__(256, 2) fc_wgrad_rows_kernel(const float* __re
 
 extern "C" int sisr_fc_wgrad_rows(const float* dy, const float* x, float scale, float* dW, int32_t B, int32_t K, int32_t N, void* stream) {
     if (!dy || !x || !dW || B <= 0 || B > FR_MAXROWS || K <= 0 || (K & 127) || N <= 0 || (N & 63)) return SISR_E_BADARG;
-    hipLaunchKernelGGL(fc_wgrad_rows_kernel, dim3(N / 64, K / 128), dim3(256), 0, S_(stream), dy, x, scale, dW, B, K, N);
+    hipLaunchKernelGGL(fc_wgrad_rows_kernel, dim3(N / 64, K / 128), dim3(256), 0, sisr_stream(stream), dy, x, scale, dW, B, K, N);
     SISR_CHECK_LAUNCH();
     return 0;
 }

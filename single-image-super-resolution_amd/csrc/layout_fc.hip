@@ -290,8 +290,6 @@ __global__ void add_relu_masked_kernel(const float* __restrict__ a, const float*
     }
 }
 
-static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 extern "C" int sisr_maxpool2_fwd(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t dt,
                                  void* stream) {
     if (!x || !y || N <= 0 || H < 2 || W < 2 || C <= 0 || (C & 3)) return SISR_E_BADARG;
@@ -299,10 +297,10 @@ extern "C" int sisr_maxpool2_fwd(const float* x, float* y, int32_t N, int32_t H,
     const int64_t total = (int64_t)N * Ho * Wo * C4;
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
     switch (dt & 3) {
-        case 0: hipLaunchKernelGGL((maxpool2_fwd_kernel<false, false>), dim3(blocks), dim3(256), 0, S_(stream), x, y, H, W, C4, Ho, Wo, total); break;
-        case 1: hipLaunchKernelGGL((maxpool2_fwd_kernel<true, false>), dim3(blocks), dim3(256), 0, S_(stream), x, y, H, W, C4, Ho, Wo, total); break;
-        case 2: hipLaunchKernelGGL((maxpool2_fwd_kernel<false, true>), dim3(blocks), dim3(256), 0, S_(stream), x, y, H, W, C4, Ho, Wo, total); break;
-        default: hipLaunchKernelGGL((maxpool2_fwd_kernel<true, true>), dim3(blocks), dim3(256), 0, S_(stream), x, y, H, W, C4, Ho, Wo, total); break;
+        case 0: hipLaunchKernelGGL((maxpool2_fwd_kernel<false, false>), dim3(blocks), dim3(256), 0, sisr_stream(stream), x, y, H, W, C4, Ho, Wo, total); break;
+        case 1: hipLaunchKernelGGL((maxpool2_fwd_kernel<true, false>), dim3(blocks), dim3(256), 0, sisr_stream(stream), x, y, H, W, C4, Ho, Wo, total); break;
+        case 2: hipLaunchKernelGGL((maxpool2_fwd_kernel<false, true>), dim3(blocks), dim3(256), 0, sisr_stream(stream), x, y, H, W, C4, Ho, Wo, total); break;
+        default: hipLaunchKernelGGL((maxpool2_fwd_kernel<true, true>), dim3(blocks), dim3(256), 0, sisr_stream(stream), x, y, H, W, C4, Ho, Wo, total); break;
     }
     SISR_CHECK_LAUNCH();
     return 0;
@@ -315,14 +313,14 @@ extern "C" int sisr_maxpool2_relu_bwd(const float* dy, const float* x, float* dx
     const int64_t total = (int64_t)N * Ho * Wo * C4;
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
     if ((dt & 7) == 0)
-        hipLaunchKernelGGL((maxpool2_relu_bwd_kernel<false, false, false>), dim3(blocks), dim3(256), 0, S_(stream), dy, x, dx, H, W, C4, Ho, Wo, total);
+        hipLaunchKernelGGL((maxpool2_relu_bwd_kernel<false, false, false>), dim3(blocks), dim3(256), 0, sisr_stream(stream), dy, x, dx, H, W, C4, Ho, Wo, total);
     else if ((dt & 7) == 7)
-        hipLaunchKernelGGL((maxpool2_relu_bwd_kernel<true, true, true>), dim3(blocks), dim3(256), 0, S_(stream), dy, x, dx, H, W, C4, Ho, Wo, total);
+        hipLaunchKernelGGL((maxpool2_relu_bwd_kernel<true, true, true>), dim3(blocks), dim3(256), 0, sisr_stream(stream), dy, x, dx, H, W, C4, Ho, Wo, total);
     else
         return SISR_E_UNSUPPORTED;         // all fp32 or all bf16
     SISR_CHECK_LAUNCH();
     if ((H & 1) || (W & 1)) {
-        hipLaunchKernelGGL(maxpool2_bwd_edge_kernel, dim3(1024), dim3(256), 0, S_(stream), dx, N, H, W, C, (dt >> 2) & 1);
+        hipLaunchKernelGGL(maxpool2_bwd_edge_kernel, dim3(1024), dim3(256), 0, sisr_stream(stream), dx, N, H, W, C, (dt >> 2) & 1);
         SISR_CHECK_LAUNCH();
     }
     return 0;
@@ -332,7 +330,7 @@ extern "C" int sisr_add_relu_masked(const float* a, const float* b, const float*
                                     int32_t dt, void* stream) {
     if (!b || !ref || !out || n <= 0) return SISR_E_BADARG;
     const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(add_relu_masked_kernel, dim3(blocks), dim3(256), 0, S_(stream), a, b, ref, out, n, dt);
+    hipLaunchKernelGGL(add_relu_masked_kernel, dim3(blocks), dim3(256), 0, sisr_stream(stream), a, b, ref, out, n, dt);
     SISR_CHECK_LAUNCH();
     return 0;
 }
@@ -343,7 +341,7 @@ extern "C" int sisr_nhwc_to_nchw(const float* x, const float* pa, const float* p
     if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (pa && !pd) || dst_stride < (int64_t)C * H * W)
         return SISR_E_BADARG;
     const int HW = H * W;
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((HW + 31) / 32, (C + 31) / 32, N), dim3(SISR_BLOCK), 0, S_(stream),
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((HW + 31) / 32, (C + 31) / 32, N), dim3(SISR_BLOCK), 0, sisr_stream(stream),
                        x, pa, pd, slope_p, slope, y, dst_stride, HW, C, x_bf16);
     SISR_CHECK_LAUNCH();
     return 0;
@@ -353,7 +351,7 @@ extern "C" int sisr_nchw_to_nhwc(const float* x, int64_t src_stride, float* y, i
                                  int32_t C, int32_t y_bf16, void* stream) {
     if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || src_stride < (int64_t)C * H * W) return SISR_E_BADARG;
     const int HW = H * W;
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((HW + 31) / 32, (C + 31) / 32, N), dim3(SISR_BLOCK), 0, S_(stream),
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((HW + 31) / 32, (C + 31) / 32, N), dim3(SISR_BLOCK), 0, sisr_stream(stream),
                        x, src_stride, y, HW, C, y_bf16);
     SISR_CHECK_LAUNCH();
     return 0;
@@ -364,7 +362,7 @@ extern "C" int sisr_nchw_grad_to_nhwc4(const float* dy, const float* out, float*
     if (!dy || !g || N <= 0 || C <= 0 || H <= 0 || W <= 0 || Cpad < C || (Cpad & 3)) return SISR_E_BADARG;
     const int64_t HW = (int64_t)H * W, total = (int64_t)N * HW;
     const int grid = (int)std::min<int64_t>((total + SISR_BLOCK - 1) / SISR_BLOCK, 4096);
-    hipLaunchKernelGGL(nchw_grad_to_nhwc4_kernel, dim3(grid), dim3(SISR_BLOCK), 0, S_(stream), dy, out, g, HW, C, Cpad, total);
+    hipLaunchKernelGGL(nchw_grad_to_nhwc4_kernel, dim3(grid), dim3(SISR_BLOCK), 0, sisr_stream(stream), dy, out, g, HW, C, Cpad, total);
     SISR_CHECK_LAUNCH();
     return 0;
 }
@@ -372,7 +370,7 @@ extern "C" int sisr_nchw_grad_to_nhwc4(const float* dy, const float* out, float*
 extern "C" int sisr_fc_forward(const float* x, float in_slope, const float* W, const float* bias, float* y, int32_t B,
                                int32_t K, int32_t Nout, int32_t epi, void* stream) {
     if (!x || !W || !y || B <= 0 || B > FC_B || K <= 0 || (K & 3) || Nout <= 0) return SISR_E_BADARG;
-    hipLaunchKernelGGL(fc_forward_kernel, dim3((Nout + FC_R - 1) / FC_R), dim3(SISR_BLOCK), 0, S_(stream), x,
+    hipLaunchKernelGGL(fc_forward_kernel, dim3((Nout + FC_R - 1) / FC_R), dim3(SISR_BLOCK), 0, sisr_stream(stream), x,
                        in_slope, W, bias, y, B, K, Nout, epi);
     SISR_CHECK_LAUNCH();
     return 0;
@@ -397,12 +395,12 @@ extern "C" int sisr_fc_dgrad(const float* dy, const float* W, float* dx, float* 
     const int rows = fc_rows_per_split(K, Nout);
     const int splits = (Nout + rows - 1) / rows;
     const int blocks_k = ((K >> 2) + SISR_BLOCK - 1) / SISR_BLOCK;
-    hipLaunchKernelGGL(fc_dgrad_kernel, dim3(blocks_k, splits), dim3(SISR_BLOCK), rows * FC_B * 4, S_(stream), dy, W,
+    hipLaunchKernelGGL(fc_dgrad_kernel, dim3(blocks_k, splits), dim3(SISR_BLOCK), rows * FC_B * 4, sisr_stream(stream), dy, W,
                        work, B, K, Nout, rows);
     SISR_CHECK_LAUNCH();
     const int64_t elems = (int64_t)B * K;
     const int blocks = (int)std::min<int64_t>((elems / 4 + 255) / 256, 2048);
-    hipLaunchKernelGGL(fc_split_reduce_kernel, dim3(blocks), dim3(256), 0, S_(stream), work, dx, splits, elems);
+    hipLaunchKernelGGL(fc_split_reduce_kernel, dim3(blocks), dim3(256), 0, sisr_stream(stream), work, dx, splits, elems);
     SISR_CHECK_LAUNCH();
     return 0;
 }
@@ -413,11 +411,11 @@ extern "C" int sisr_fc_wgrad(const float* dy, const float* x, float in_slope, fl
     const int rows = fc_rows_per_split(K, Nout);
     const int splits = (Nout + rows - 1) / rows;
     const int blocks_k = ((K >> 2) + SISR_BLOCK - 1) / SISR_BLOCK;
-    hipLaunchKernelGGL(fc_wgrad_kernel, dim3(blocks_k, splits), dim3(SISR_BLOCK), rows * FC_B * 4, S_(stream), dy, x,
+    hipLaunchKernelGGL(fc_wgrad_kernel, dim3(blocks_k, splits), dim3(SISR_BLOCK), rows * FC_B * 4, sisr_stream(stream), dy, x,
                        in_slope, dW, B, K, Nout, rows);
     SISR_CHECK_LAUNCH();
     if (db != nullptr) {
-        hipLaunchKernelGGL(fc_bias_grad_kernel, dim3((Nout + 255) / 256), dim3(256), 0, S_(stream), dy, db, B, Nout);
+        hipLaunchKernelGGL(fc_bias_grad_kernel, dim3((Nout + 255) / 256), dim3(256), 0, sisr_stream(stream), dy, db, B, Nout);
         SISR_CHECK_LAUNCH();
     }
     return 0;
@@ -427,7 +425,7 @@ extern "C" int sisr_act_bwd(const float* dy, const float* ref, float* out, int64
                             void* stream) {
     if (!dy || !ref || !out || n <= 0 || kind < 0 || kind > 1) return SISR_E_BADARG;
     const int blocks = (int)std::min<int64_t>((n + 255) / 256, 2048);
-    hipLaunchKernelGGL(act_bwd_kernel, dim3(blocks), dim3(256), 0, S_(stream), dy, ref, out, n, kind, slope);
+    hipLaunchKernelGGL(act_bwd_kernel, dim3(blocks), dim3(256), 0, sisr_stream(stream), dy, ref, out, n, kind, slope);
     SISR_CHECK_LAUNCH();
     return 0;
 }

@@ -23,7 +23,7 @@ __global__ void mfma_selftest_kernel(float* out) {
 
 extern "C" int sisr_mfma_selftest(float* out_dev, void* stream) {
     if (!out_dev) return SISR_E_BADARG;
-    hipLaunchKernelGGL(mfma_selftest_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), out_dev);
+    hipLaunchKernelGGL(mfma_selftest_kernel, dim3(1), dim3(64), 0, sisr_stream(stream), out_dev);
     SISR_CHECK_LAUNCH();
     return 0;
 }
@@ -85,7 +85,7 @@ __global__ void tr16_selftest_kernel(short* out) {
 
 extern "C" int sisr_tr16_selftest(short* out_dev, void* stream) {
     if (!out_dev) return SISR_E_BADARG;
-    hipLaunchKernelGGL(tr16_selftest_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), out_dev);
+    hipLaunchKernelGGL(tr16_selftest_kernel, dim3(1), dim3(64), 0, sisr_stream(stream), out_dev);
     SISR_CHECK_LAUNCH();
     return 0;
 }

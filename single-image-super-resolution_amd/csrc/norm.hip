@@ -285,8 +285,6 @@ __global__ void add_kernel(const float* __restrict__ a, const float* __restrict_
 }
 
 // ---- C ABI ----------------------------------------------------------------------------------------
-static inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 extern "C" int sisr_bn_finalize(const float* stat_part, const float* cnt_part, int32_t n_tiles, int32_t C,
                                 const float* gamma, const float* beta, float* running_mean,
                                 float* running_var, float momentum, float eps, float* scale, float* shift,
@@ -294,7 +292,7 @@ extern "C" int sisr_bn_finalize(const float* stat_part, const float* cnt_part, i
     if (!stat_part || !cnt_part || n_tiles <= 0 || C <= 0 || !gamma || !beta || !running_mean || !running_var ||
         !scale || !shift || !save_mean || !save_invstd)
         return SISR_E_BADARG;
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + BNF_CH - 1) / BNF_CH), dim3(BNF_SPLITS * BNF_CH), 0, S_(stream), stat_part,
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + BNF_CH - 1) / BNF_CH), dim3(BNF_SPLITS * BNF_CH), 0, sisr_stream(stream), stat_part,
                        cnt_part, n_tiles, C, gamma, beta, running_mean, running_var, momentum, eps, scale, shift,
                        save_mean, save_invstd);
     SISR_CHECK_LAUNCH();
@@ -305,7 +303,7 @@ extern "C" int sisr_bn_eval_consts(const float* gamma, const float* beta, const 
                                    const float* running_var, float eps, int32_t C, float* scale, float* shift,
                                    void* stream) {
     if (!gamma || !beta || !running_mean || !running_var || !scale || !shift || C <= 0) return SISR_E_BADARG;
-    hipLaunchKernelGGL(bn_eval_consts_kernel, dim3((C + 255) / 256), dim3(256), 0, S_(stream), gamma, beta,
+    hipLaunchKernelGGL(bn_eval_consts_kernel, dim3((C + 255) / 256), dim3(256), 0, sisr_stream(stream), gamma, beta,
                        running_mean, running_var, eps, C, scale, shift);
     SISR_CHECK_LAUNCH();
     return 0;
@@ -328,9 +326,9 @@ extern "C" int sisr_bn_bwd(const SisrBnBwdDesc* d, void* stream) {
     const int G = d->C >> 2, PL = SISR_BLOCK / G;
     const int lds = PL * 2 * d->C * 4;
     if (lds > 64 * 1024) return SISR_E_UNSUPPORTED;
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(d->grid), dim3(SISR_BLOCK), lds, S_(stream), *d);
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(d->grid), dim3(SISR_BLOCK), lds, sisr_stream(stream), *d);
     SISR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((d->C + BWF_CH - 1) / BWF_CH), dim3(SISR_BLOCK), 0, S_(stream), *d);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((d->C + BWF_CH - 1) / BWF_CH), dim3(SISR_BLOCK), 0, sisr_stream(stream), *d);
     SISR_CHECK_LAUNCH();
     return 0;
 }
@@ -339,7 +337,7 @@ extern "C" int sisr_bn_bwd_finalize(const SisrBnBwdDesc* d, void* stream) {
     if (!d || !d->invstd || !d->mean || !d->gamma || !d->work || !d->qa || !d->qb || !d->qd || !d->dgamma || !d->dbeta ||
         d->grid <= 0 || d->C <= 0 || d->P <= 0)
         return SISR_E_BADARG;
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((d->C + BWF_CH - 1) / BWF_CH), dim3(SISR_BLOCK), 0, S_(stream), *d);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((d->C + BWF_CH - 1) / BWF_CH), dim3(SISR_BLOCK), 0, sisr_stream(stream), *d);
     SISR_CHECK_LAUNCH();
     return 0;
 }
@@ -352,7 +350,7 @@ extern "C" int sisr_bn_bwd_finalize_slab(const SisrBnBwdDesc* d, const float* sl
     if (!slab || !out || n_slabs <= 0 || elems <= 0 || (elems & 3) || (lead_bf16 & 3) || lead_bf16 < 0 || lead_bf16 > elems) return SISR_E_BADARG;
     const int fin_blocks = (d->C + BWF_CH - 1) / BWF_CH;
     const int slab_blocks = (int)((elems / 4 + SR_COLS - 1) / SR_COLS);
-    hipLaunchKernelGGL(bn_bwd_finalize_slab_kernel, dim3(fin_blocks + slab_blocks), dim3(SISR_BLOCK), 0, S_(stream), *d, fin_blocks,
+    hipLaunchKernelGGL(bn_bwd_finalize_slab_kernel, dim3(fin_blocks + slab_blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream), *d, fin_blocks,
                        slab, out, n_slabs, elems, lead_bf16);
     SISR_CHECK_LAUNCH();
     return 0;
@@ -369,7 +367,7 @@ extern "C" int sisr_eltwise_res_affine(const float* x1, const float* slope1_p, f
         const int64_t n8 = n4 / 2;
         // 2048 blocks x 256 threads: the grid stride (a multiple of 2048 octets) keeps a thread on the same channels
         const int blocks = (int)std::min<int64_t>((n8 + 255) / 256, 2048);
-        hipLaunchKernelGGL(eltwise_res_affine_bf16x8_kernel, dim3(blocks), dim3(256), 0, S_(stream), x1, slope1_p, slope1,
+        hipLaunchKernelGGL(eltwise_res_affine_bf16x8_kernel, dim3(blocks), dim3(256), 0, sisr_stream(stream), x1, slope1_p, slope1,
                            x2, pa, pd, y, n8, C);
         SISR_CHECK_LAUNCH();
         return 0;
@@ -377,7 +375,7 @@ extern "C" int sisr_eltwise_res_affine(const float* x1, const float* slope1_p, f
     const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 4096);
 #define SISR_ELT_CASE(K, A, B, Y)                                                                                      \
     case K:                                                                                                           \
-        hipLaunchKernelGGL((eltwise_res_affine_kernel<A, B, Y>), dim3(blocks), dim3(256), 0, S_(stream), x1, slope1_p, \
+        hipLaunchKernelGGL((eltwise_res_affine_kernel<A, B, Y>), dim3(blocks), dim3(256), 0, sisr_stream(stream), x1, slope1_p, \
                            slope1, x2, pa, pd, y, n4, C);                                                             \
         break;
     switch (key) {
@@ -396,13 +394,13 @@ extern "C" int sisr_prelu_slope_grad(const float* dy, const float* pre, int64_t 
     if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(pre)) & 15) return SISR_E_BADARG;   // 16-byte loads
     const int blocks = (int)std::min<int64_t>((n + 8191) / 8192, 1024);
     switch (dt & 3) {
-        case 0: hipLaunchKernelGGL((prelu_slope_partial_kernel<false, false>), dim3(blocks), dim3(SISR_BLOCK), 0, S_(stream), dy, pre, n, work); break;
-        case 1: hipLaunchKernelGGL((prelu_slope_partial_kernel<true, false>), dim3(blocks), dim3(SISR_BLOCK), 0, S_(stream), dy, pre, n, work); break;
-        case 2: hipLaunchKernelGGL((prelu_slope_partial_kernel<false, true>), dim3(blocks), dim3(SISR_BLOCK), 0, S_(stream), dy, pre, n, work); break;
-        default: hipLaunchKernelGGL((prelu_slope_partial_kernel<true, true>), dim3(blocks), dim3(SISR_BLOCK), 0, S_(stream), dy, pre, n, work); break;
+        case 0: hipLaunchKernelGGL((prelu_slope_partial_kernel<false, false>), dim3(blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream), dy, pre, n, work); break;
+        case 1: hipLaunchKernelGGL((prelu_slope_partial_kernel<true, false>), dim3(blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream), dy, pre, n, work); break;
+        case 2: hipLaunchKernelGGL((prelu_slope_partial_kernel<false, true>), dim3(blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream), dy, pre, n, work); break;
+        default: hipLaunchKernelGGL((prelu_slope_partial_kernel<true, true>), dim3(blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream), dy, pre, n, work); break;
     }
     SISR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(SISR_BLOCK), 0, S_(stream), work, blocks, out);
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(SISR_BLOCK), 0, sisr_stream(stream), work, blocks, out);
     SISR_CHECK_LAUNCH();
     return 0;
 }
@@ -411,9 +409,9 @@ extern "C" int sisr_add(const float* a, const float* b, float* y, int64_t n, int
     if (!a || !b || !y || n <= 0) return SISR_E_BADARG;
     if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(y)) & 15) return SISR_E_BADARG;
     const int blocks = (int)std::min<int64_t>((n / 4 + 255) / 256 + 1, 4096);
-    if ((dt & 7) == 0) hipLaunchKernelGGL((add_kernel<false, false, false>), dim3(blocks), dim3(256), 0, S_(stream), a, b, y, n);
-    else if ((dt & 7) == 7) hipLaunchKernelGGL((add_kernel<true, true, true>), dim3(blocks), dim3(256), 0, S_(stream), a, b, y, n);
-    else if ((dt & 7) == 4) hipLaunchKernelGGL((add_kernel<false, false, true>), dim3(blocks), dim3(256), 0, S_(stream), a, b, y, n);
+    if ((dt & 7) == 0) hipLaunchKernelGGL((add_kernel<false, false, false>), dim3(blocks), dim3(256), 0, sisr_stream(stream), a, b, y, n);
+    else if ((dt & 7) == 7) hipLaunchKernelGGL((add_kernel<true, true, true>), dim3(blocks), dim3(256), 0, sisr_stream(stream), a, b, y, n);
+    else if ((dt & 7) == 4) hipLaunchKernelGGL((add_kernel<false, false, true>), dim3(blocks), dim3(256), 0, sisr_stream(stream), a, b, y, n);
     else return SISR_E_UNSUPPORTED;
     SISR_CHECK_LAUNCH();
     return 0;

@@ -61,7 +61,7 @@ extern "C" int sisr_adam_step(const SisrAdamDesc* table_dev, int32_t n, int64_t 
     if (!table_dev || n <= 0 || total_blocks <= 0 || total_blocks >= (1ll << 31) || bias_corr1 <= 0.0 || bias_corr2 <= 0.0)
         return SISR_E_BADARG;
     // host scalars are doubles (as in torch): 1 - beta, lr / bias_corr1 ... are rounded to fp32 once, after the arithmetic
-    hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)total_blocks), dim3(SISR_BLOCK), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)total_blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream),
                        table_dev, n, (float)(lr / bias_corr1), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
                        (float)eps, (float)weight_decay, (float)(1.0 / sqrt(bias_corr2)));
     SISR_CHECK_LAUNCH();

@@ -197,7 +197,7 @@ extern "C" int sisr_resize_u8_normalize(const unsigned char* src, float* dst, in
     if ((pass_x && (!bx || !kx || ksx <= 0)) || (pass_y && (!by || !ky || ksy <= 0))) return SISR_E_BADARG;
     const int64_t total = (int64_t)N * H * W;
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(resize_u8_normalize_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, dst,
+    hipLaunchKernelGGL(resize_u8_normalize_kernel, dim3(blocks), dim3(256), 0, sisr_stream(stream), src, dst,
                        N, H0, W0, C, H, W, bx, kx, ksx, by, ky, ksy, pass_x, pass_y, mean, stdv);
     SISR_CHECK_LAUNCH();
     return 0;
@@ -210,7 +210,7 @@ extern "C" int sisr_bicubic_fwd(const float* x, float* y, int32_t NC, int32_t H,
     if (!x || !y || NC <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return SISR_E_BADARG;
     const int64_t total = (int64_t)NC * Ho * Wo;
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(bicubic_fwd_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, y,
+    hipLaunchKernelGGL(bicubic_fwd_kernel, dim3(blocks), dim3(256), 0, sisr_stream(stream), x, y,
                        NC, H, W, Ho, Wo, ac_scale(H, Ho), ac_scale(W, Wo), clampv);
     SISR_CHECK_LAUNCH();
     return 0;
@@ -219,7 +219,7 @@ extern "C" int sisr_bicubic_fwd(const float* x, float* y, int32_t NC, int32_t H,
 extern "C" int sisr_bicubic_bwd(const float* dy, const float* y_clamped, float* dx, int32_t NC, int32_t H, int32_t W,
                                 int32_t Ho, int32_t Wo, void* stream) {
     if (!dy || !dx || NC <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return SISR_E_BADARG;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = sisr_stream(stream);
     const int64_t total = (int64_t)NC * H * W;
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
     hipLaunchKernelGGL(bicubic_bwd_kernel, dim3(blocks), dim3(256), 0, st, dy, y_clamped, dx, NC, H, W, Ho, Wo,

@@ -188,9 +188,7 @@ __device__ __forceinline__ void stage_commit(const OperandView& o, const StageRe
         h[0] = (__bf16)v[0]; h[1] = (__bf16)v[1]; h[2] = (__bf16)v[2]; h[3] = (__bf16)v[3];
         if (pix0 + u * ppi < npix) *reinterpret_cast<bf16x4*>(dst + u * dst_step) = h;
         // one item at a time: the loads are already in registers, interleaving the items only multiplies temporaries
-#ifndef SISR_AB_NO_COMMIT_FENCE
         if (NIT > 4) __builtin_amdgcn_sched_barrier(0);
-#endif
     }
 }
 

@@ -645,7 +645,7 @@ static int parts_for(int64_t elems) {           // workgroups per weight for the
 // (W_orig does not change between two optimizer steps; only u, v, sigma do) runs the power iteration alone
 extern "C" int sisr_weights_sn(const SisrWeightDesc* table_dev, int32_t n, int32_t max_rows, int32_t max_cols, void* stream) {
     if (!table_dev || n <= 0 || max_rows <= 0 || max_cols <= 0) return SISR_E_BADARG;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = sisr_stream(stream);
     const int jobs_a = ((max_rows + SN_RB - 1) / SN_RB) * ((max_cols + SN_CB - 1) / SN_CB);
     hipLaunchKernelGGL(sn_wt_u_kernel, dim3(n, jobs_a), dim3(SISR_BLOCK), 0, st, table_dev);
     SISR_CHECK_LAUNCH();
@@ -660,7 +660,7 @@ extern "C" int sisr_weights_sn(const SisrWeightDesc* table_dev, int32_t n, int32
 
 extern "C" int sisr_weights_pack(const SisrWeightDesc* table_dev, int32_t n, int32_t max_rows, int32_t max_cols, void* stream) {
     if (!table_dev || n <= 0 || max_rows <= 0 || max_cols <= 0) return SISR_E_BADARG;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = sisr_stream(stream);
     // packed images are a little larger than the matrix (padding slots): parts from 2x its size
     hipLaunchKernelGGL(weights_pack_kernel, dim3(n, parts_for(2ll * max_rows * max_cols)), dim3(SISR_BLOCK), 0, st, table_dev);
     SISR_CHECK_LAUNCH();
@@ -670,7 +670,7 @@ extern "C" int sisr_weights_pack(const SisrWeightDesc* table_dev, int32_t n, int
 // the conv_deep.hip images (wdp_*) of every 3x3 weight of the table that asks for one; max_cout / max_cin over those weights
 extern "C" int sisr_weights_pack_deep(const SisrWeightDesc* table_dev, int32_t n, int32_t max_cout, int32_t max_cin, void* stream) {
     if (!table_dev || n <= 0 || max_cout <= 0 || max_cin <= 0) return SISR_E_BADARG;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = sisr_stream(stream);
     hipLaunchKernelGGL(weights_pack_deep_kernel, dim3(n, (max_cout + 31) / 32, (max_cin + 31) / 32), dim3(SISR_BLOCK), 0, st, table_dev);
     SISR_CHECK_LAUNCH();
     return 0;
@@ -694,7 +694,7 @@ extern "C" int sisr_weights_grad_tiles(const SisrWeightGradDesc* w) {
 extern "C" int sisr_weights_grad_fast(const SisrWeightGradDesc* table_dev, int32_t n, float* dot_work, int32_t max_cout,
                                       int32_t max_cin, void* stream) {
     if (!table_dev || n <= 0 || !dot_work || max_cout <= 0 || max_cin < 32) return SISR_E_BADARG;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = sisr_stream(stream);
     const int ty = (max_cout + 31) / 32, tz = max_cin / 32;
     hipLaunchKernelGGL(weights_grad_fast_kernel, dim3(n, ty, tz), dim3(SISR_BLOCK), 0, st, table_dev, dot_work);
     SISR_CHECK_LAUNCH();
@@ -707,7 +707,7 @@ extern "C" int sisr_weights_grad_fast(const SisrWeightGradDesc* table_dev, int32
 extern "C" int sisr_weights_grad(const SisrWeightGradDesc* table_dev, int32_t n, float* dot_work, int32_t parts,
                                  void* stream) {
     if (!table_dev || n <= 0 || !dot_work || parts <= 0 || parts > 65535) return SISR_E_BADARG;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = sisr_stream(stream);
     hipLaunchKernelGGL(weights_grad_dot_kernel, dim3(n, parts), dim3(SISR_BLOCK), 0, st, table_dev, dot_work);
     SISR_CHECK_LAUNCH();
     hipLaunchKernelGGL(weights_grad_kernel, dim3(n, parts), dim3(SISR_BLOCK), 0, st, table_dev, dot_work);

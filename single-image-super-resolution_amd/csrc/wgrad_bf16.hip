@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "sisr_bf16_stage.h"
+#include "sisr_instr.h"
 
 
 __device__ __forceinline__ bf16x8 frag8(const __bf16* p, int second_off) {
@@ -26,22 +27,8 @@ __device__ __forceinline__ bf16x8 frag8(const __bf16* p, int second_off) {
 }
 
 // phase timeline, developer build only (see conv_bf16.hip / tools/trace_conv.py)
-#ifdef SISR_CONV_TRACE
-#define SISR_WTRACE_WG 2048
-#define SISR_WTRACE_SLOTS 32
-__device__ unsigned long long sisr_wtrace_buf[SISR_WTRACE_WG * SISR_WTRACE_SLOTS];
-#define WTR(k)                                                                                             \
-    do {                                                                                                   \
-        const int wg_ = blockIdx.y * gridDim.x + blockIdx.x;                                               \
-        if (threadIdx.x == 0 && wg_ < SISR_WTRACE_WG && (k) < SISR_WTRACE_SLOTS)                           \
-            sisr_wtrace_buf[wg_ * SISR_WTRACE_SLOTS + (k)] = wall_clock64();                               \
-    } while (0)
-extern "C" int sisr_wtrace_read(void* dst, int n_u64) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(sisr_wtrace_buf), (size_t)n_u64 * 8, 0, hipMemcpyDeviceToHost);
-}
-#else
-#define WTR(k)
-#endif
+SISR_TRACE_BUFFER(sisr_wtrace, 2048, 32)
+#define WTR(k) SISR_TRACE_STAMP_ROW(sisr_wtrace, threadIdx.x == 0, (int)(blockIdx.y * gridDim.x + blockIdx.x), k, 32, wall_clock64())
 
 // LDS pixel strides (bf16 elements) chosen for the transposing reads: the 32 lanes of one LDS pass address
 // 4 pixels x 64 bytes, so a pixel stride of 16 or 48 banks (mod 64) puts them on 64 distinct banks.
@@ -261,20 +248,9 @@ extern "C" int sisr_wgrad_plan_bf16(SisrWgradDesc* d, int32_t max_pixel_blocks) 
 
 template <int TPW>
 static int launch_wgrad_bf16(const SisrWgradDesc* d, hipStream_t st) {
-    static SisrLdsCap cap;
-    if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&wgrad_mfma_bf16_kernel<TPW>), d->lds_bytes, 64 * 1024)) return e;
     const dim3 grid(d->grid_x, d->n_chunk * (d->CoutPad / (d->NJ * 32)));
-    hipLaunchKernelGGL(wgrad_mfma_bf16_kernel<TPW>, grid, dim3(SISR_BLOCK), d->lds_bytes, st, *d);
-    SISR_CHECK_LAUNCH();
-    return 0;
+    return sisr_launch<wgrad_mfma_bf16_kernel<TPW>>(grid, dim3(SISR_BLOCK), d->lds_bytes, SISR_LDS_BASE_DEFAULT, st, *d);
 }
-
-extern "C" int sisr_wgrad_trunk_eligible(const SisrWgradDesc* d);
-int sisr_wgrad_trunk_launch(const SisrWgradDesc* d, hipStream_t st);      // wgrad_trunk.hip
-extern "C" int sisr_wgrad_toimage_eligible(const SisrWgradDesc* d);
-int sisr_wgrad_toimage_launch(const SisrWgradDesc* d, hipStream_t st);    // wgrad_toimage.hip
-extern "C" int sisr_wgrad_deep_eligible(const SisrWgradDesc* d);
-int sisr_wgrad_deep_launch(const SisrWgradDesc* d, hipStream_t st);       // wgrad_deep.hip
 
 extern "C" int sisr_conv2d_wgrad_bf16(const SisrWgradDesc* d, void* stream) {
     if (!d || !d->x1 || !d->g1 || !d->slab) return SISR_E_BADARG;
@@ -282,7 +258,7 @@ extern "C" int sisr_conv2d_wgrad_bf16(const SisrWgradDesc* d, void* stream) {
     if (operand_needs_x2(d->gpro_mode) && !d->g2) return SISR_E_BADARG;
     if (d->slab_stride < d->slab_elems || d->CK != BF_CK || d->PS != BF_PS) return SISR_E_BADARG;
     if (d->grid_x <= 0 || d->lds_bytes <= 0 || d->lds_bytes > 160 * 1024) return SISR_E_BADARG;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = sisr_stream(stream);
     if (sisr_wgrad_trunk_eligible(d)) return sisr_wgrad_trunk_launch(d, st);
     if (sisr_wgrad_toimage_eligible(d)) return sisr_wgrad_toimage_launch(d, st);    // the generator's last conv (64 -> 3)
     if (sisr_wgrad_deep_eligible(d)) return sisr_wgrad_deep_launch(d, st);          // 3x3, channels in 64s

@@ -368,16 +368,11 @@ __global__ void __launch_bounds__(WD_THREADS, 1) wgrad_deep_table_kernel(const S
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-static bool wd_slab_bf16() {
-    const char* e = getenv("SISR_SLAB_BF16");
-    return !(e && e[0] == '0');
-}
-
 extern "C" int sisr_wgrad_deep_plan(SisrWgradDesc* d, int32_t target_wg) {
     if (!d) return SISR_E_BADARG;
     SisrWgradDeepPlan& p = d->deep;
     std::memset(&p, 0, sizeof(p));
-    if (const char* e = getenv("SISR_WGRAD_DEEP")) if (e[0] == '0') return SISR_E_UNSUPPORTED;   // A/B switch: keep the generic kernel
+    if (sisr_switch_off("SISR_WGRAD_DEEP")) return SISR_E_UNSUPPORTED;   // A/B switch: keep the generic kernel
     if (d->KH != 3 || d->KW != 3 || d->pad_y != 1 || d->pad_x != 1) return SISR_E_UNSUPPORTED;
     if (d->stride != 1 && d->stride != 2) return SISR_E_UNSUPPORTED;
     if ((d->Cin % 64) || (d->Cout % 64) || d->CoutPad != d->Cout || d->N <= 0) return SISR_E_UNSUPPORTED;
@@ -441,7 +436,7 @@ extern "C" int sisr_wgrad_deep_plan(SisrWgradDesc* d, int32_t target_wg) {
     // pixel blocks (= slabs): each workgroup walks ceil(n_tiles / n_pb) tiles (measured ~3.5 us each with the chip full: the staging
     // loads of 256 workgroups run at ~4 TB/s; + ~8 us of prologue and slab stores) in ceil(workgroups / 256) rounds; every slab is
     // written once and re-read once by the reduction
-    p.slab_bf16 = wd_slab_bf16() ? 1 : 0;
+    p.slab_bf16 = !sisr_switch_off("SISR_SLAB_BF16") ? 1 : 0;
     {
         const int blocks = p.n_cib * p.n_cob;
         const double slab_us = (double)d->slab_elems * (p.slab_bf16 ? 2 : 4) * 2.0 / 3.5e6;     // write + re-read at ~3.5 TB/s
@@ -485,17 +480,8 @@ static int launch_wd(const SisrWgradDesc* d, hipStream_t st) {
     const SisrWgradDeepPlan& p = d->deep;
     const bool two = operand_needs_x2(d->gpro_mode);
     const dim3 grid(p.n_cib * p.n_cob, p.n_pb);
-    if (two) {
-        static SisrLdsCap cap;
-        if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&wgrad_deep_kernel<S, NITX, NITD, true>), p.lds_bytes, 0)) return e;
-        hipLaunchKernelGGL((wgrad_deep_kernel<S, NITX, NITD, true>), grid, dim3(WD_THREADS), p.lds_bytes, st, *d);
-    } else {
-        static SisrLdsCap cap;
-        if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&wgrad_deep_kernel<S, NITX, NITD, false>), p.lds_bytes, 0)) return e;
-        hipLaunchKernelGGL((wgrad_deep_kernel<S, NITX, NITD, false>), grid, dim3(WD_THREADS), p.lds_bytes, st, *d);
-    }
-    SISR_CHECK_LAUNCH();
-    return 0;
+    if (two) return sisr_launch<wgrad_deep_kernel<S, NITX, NITD, true>>(grid, dim3(WD_THREADS), p.lds_bytes, 0, st, *d);
+    return sisr_launch<wgrad_deep_kernel<S, NITX, NITD, false>>(grid, dim3(WD_THREADS), p.lds_bytes, 0, st, *d);
 }
 
 int sisr_wgrad_deep_launch(const SisrWgradDesc* d, hipStream_t st) {
@@ -515,17 +501,8 @@ int sisr_wgrad_deep_launch(const SisrWgradDesc* d, hipStream_t st) {
 
 template <int S, int NITX, int NITD>
 static int launch_wd_table(const SisrWgradDesc* table_dev, int n, dim3 grid, int lds_bytes, bool two, hipStream_t st) {
-    if (two) {
-        static SisrLdsCap cap;
-        if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&wgrad_deep_table_kernel<S, NITX, NITD, true>), lds_bytes, 0)) return e;
-        hipLaunchKernelGGL((wgrad_deep_table_kernel<S, NITX, NITD, true>), grid, dim3(WD_THREADS), lds_bytes, st, table_dev, n);
-    } else {
-        static SisrLdsCap cap;
-        if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&wgrad_deep_table_kernel<S, NITX, NITD, false>), lds_bytes, 0)) return e;
-        hipLaunchKernelGGL((wgrad_deep_table_kernel<S, NITX, NITD, false>), grid, dim3(WD_THREADS), lds_bytes, st, table_dev, n);
-    }
-    SISR_CHECK_LAUNCH();
-    return 0;
+    if (two) return sisr_launch<wgrad_deep_table_kernel<S, NITX, NITD, true>>(grid, dim3(WD_THREADS), lds_bytes, 0, st, table_dev, n);
+    return sisr_launch<wgrad_deep_table_kernel<S, NITX, NITD, false>>(grid, dim3(WD_THREADS), lds_bytes, 0, st, table_dev, n);
 }
 
 // table_host: the n fully filled descriptors (all wgrad_deep-eligible, same stride, all with or all without a two-tensor gradient
@@ -550,7 +527,7 @@ extern "C" int sisr_wgrad_deep_batch(const SisrWgradDesc* table_host, const Sisr
         total += p.n_cib * p.n_cob * p.n_pb;
         lds = std::max(lds, p.lds_bytes);
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = sisr_stream(stream);
     const dim3 grid(total);
     return S == 1 ? launch_wd_table<1, 6, 4>(table_dev, n, grid, lds, two, st) : launch_wd_table<2, 10, 3>(table_dev, n, grid, lds, two, st);
 }

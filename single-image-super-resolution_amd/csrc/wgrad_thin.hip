@@ -287,11 +287,10 @@ static int wn_cus() { return sisr_cu_slots(); }
 
 // 9: the generator's first conv, 3: the discriminator's, 0: not taken
 static int wn_ks(const SisrWgradDesc* d) {
-    const char* sw = getenv("SISR_THIN");                       // A/B switch: SISR_THIN=0 keeps the generic kernel
-    if ((sw && sw[0] == '0') || !d) return 0;
+    if (sisr_switch_off("SISR_THIN") || !d) return 0;           // A/B switch: SISR_THIN=0 keeps the generic kernel
     if (d->KH != d->KW || (d->KH != 9 && d->KH != 3) || d->stride != 1 || d->pad_y != d->KH / 2 || d->pad_x != d->KH / 2) return 0;
     const int ks = d->KH;
-    if (ks == 3) { const char* s3 = getenv("SISR_THIN3"); if (s3 && s3[0] == '0') return 0; }
+    if (ks == 3 && sisr_switch_off("SISR_THIN3")) return 0;
     const int krowp = ks == 9 ? WN_KROWP : 12;
     if (d->Cin != 3 || d->Cout != 64 || d->CoutPad != 64 || d->n_chunk != 1 || d->PS != 3 || d->KROWP != krowp) return 0;
     if (d->x_mode != SISR_X_NCHW || d->x_bf16 || d->pro_mode != SISR_PRO_NONE) return 0;
@@ -316,11 +315,6 @@ int sisr_wgrad_thin_launch(const SisrWgradDesc* d, hipStream_t st) {
     if (actb && !d->g2) return SISR_E_BADARG;
     const int ks = wn_ks(d);
     if (!ks) return SISR_E_UNSUPPORTED;
-    static SisrLdsCap cap_t, cap_f, cap_t3, cap_f3;
-    if (int e = sisr_raise_lds_cap(cap_t, reinterpret_cast<const void*>(&wgrad_thin_kernel<true, 9>), lds_bytes)) return e;
-    if (int e = sisr_raise_lds_cap(cap_f, reinterpret_cast<const void*>(&wgrad_thin_kernel<false, 9>), lds_bytes)) return e;
-    if (int e = sisr_raise_lds_cap(cap_t3, reinterpret_cast<const void*>(&wgrad_thin_kernel<true, 3>), lds_bytes)) return e;
-    if (int e = sisr_raise_lds_cap(cap_f3, reinterpret_cast<const void*>(&wgrad_thin_kernel<false, 3>), lds_bytes)) return e;
     WThinArgs a;
     a.x = d->x1; a.g1 = d->g1; a.g2 = d->g2; a.slab = d->slab; a.bias_slab = d->bias_slab;
     a.slope_p = d->gpro_slope_p; a.slope = d->gpro_slope;
@@ -329,14 +323,11 @@ int sisr_wgrad_thin_launch(const SisrWgradDesc* d, hipStream_t st) {
     a.per_img = a.tiles_x * (d->H / WN_TH);
     a.total = a.per_img * d->N;
     a.slab_stride = d->slab_stride;
-    const int grid = wn_grid(d);
+    const dim3 grid(wn_grid(d)), block(256);
     if (ks == 9) {
-        if (actb) hipLaunchKernelGGL((wgrad_thin_kernel<true, 9>), dim3(grid), dim3(256), lds_bytes, st, a);
-        else hipLaunchKernelGGL((wgrad_thin_kernel<false, 9>), dim3(grid), dim3(256), lds_bytes, st, a);
-    } else {
-        if (actb) hipLaunchKernelGGL((wgrad_thin_kernel<true, 3>), dim3(grid), dim3(256), lds_bytes, st, a);
-        else hipLaunchKernelGGL((wgrad_thin_kernel<false, 3>), dim3(grid), dim3(256), lds_bytes, st, a);
+        if (actb) return sisr_launch<wgrad_thin_kernel<true, 9>>(grid, block, lds_bytes, 0, st, a);
+        return sisr_launch<wgrad_thin_kernel<false, 9>>(grid, block, lds_bytes, 0, st, a);
     }
-    SISR_CHECK_LAUNCH();
-    return 0;
+    if (actb) return sisr_launch<wgrad_thin_kernel<true, 3>>(grid, block, lds_bytes, 0, st, a);
+    return sisr_launch<wgrad_thin_kernel<false, 3>>(grid, block, lds_bytes, 0, st, a);
 }

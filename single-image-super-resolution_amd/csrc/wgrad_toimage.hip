@@ -202,8 +202,7 @@ __global__ void __launch_bounds__(256, 1) wgrad_toimage_kernel(const WToImageArg
 static int wi_cus() { return sisr_cu_slots(); }
 
 extern "C" int sisr_wgrad_toimage_eligible(const SisrWgradDesc* d) {
-    const char* sw = getenv("SISR_THIN");                       // A/B switch: SISR_THIN=0 keeps the generic kernel
-    if ((sw && sw[0] == '0') || !d) return 0;
+    if (sisr_switch_off("SISR_THIN") || !d) return 0;           // A/B switch: SISR_THIN=0 keeps the generic kernel
     if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_y != 1 || d->pad_x != 1) return 0;
     // (planned by sisr_wgrad_plan_bf16 for the gradient padded to 4 channels: that fixes the slab layout)
     if (d->Cin != 64 || d->Cout != 4 || d->CoutPad != WI_CP || d->n_chunk != 2 || d->CK != 32 || d->slab_elems != WI_SLAB) return 0;
@@ -225,11 +224,7 @@ int sisr_wgrad_toimage_slabs(const SisrWgradDesc* d) { return wi_grid(d); }
 template <bool ACT, bool TANHB>
 static int wi_launch(const WToImageArgs& a, int grid, hipStream_t st) {
     constexpr int lds_bytes = WI_XBYTES + WI_GBYTES;
-    static SisrLdsCap cap;
-    if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&wgrad_toimage_kernel<ACT, TANHB>), lds_bytes)) return e;
-    hipLaunchKernelGGL((wgrad_toimage_kernel<ACT, TANHB>), dim3(grid), dim3(256), lds_bytes, st, a);
-    SISR_CHECK_LAUNCH();
-    return 0;
+    return sisr_launch<wgrad_toimage_kernel<ACT, TANHB>>(dim3(grid), dim3(256), lds_bytes, 0, st, a);
 }
 
 int sisr_wgrad_toimage_launch(const SisrWgradDesc* d, hipStream_t st) {
@@ -404,8 +399,7 @@ __global__ void __launch_bounds__(256, 1) wgrad_toimage_f32_kernel(const WToImag
 }
 
 extern "C" int sisr_wgrad_toimage_f32_eligible(const SisrWgradDesc* d) {
-    const char* sw = getenv("SISR_THIN");                       // A/B switch: SISR_THIN=0 keeps the generic kernel
-    if ((sw && sw[0] == '0') || !d) return 0;
+    if (sisr_switch_off("SISR_THIN") || !d) return 0;           // A/B switch: SISR_THIN=0 keeps the generic kernel
     if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_y != 1 || d->pad_x != 1) return 0;
     if (d->Cin != 64 || d->Cout != 3 || d->CoutPad < 3 || d->CoutPad > 256 || d->CK < 1 || d->n_chunk * d->CK != 64) return 0;
     if (d->PS < d->CK || d->KROWP < 2 * d->PS + d->CK || d->slab_elems != d->n_chunk * 3 * d->KROWP * d->CoutPad) return 0;
@@ -419,11 +413,7 @@ extern "C" int sisr_wgrad_toimage_f32_eligible(const SisrWgradDesc* d) {
 template <bool ACT, bool TANHB>
 static int wj_launch(const WToImageF32Args& a, int grid, hipStream_t st) {
     constexpr int lds_bytes = WJ_XBYTES + WJ_GBYTES + 256;
-    static SisrLdsCap cap;
-    if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&wgrad_toimage_f32_kernel<ACT, TANHB>), lds_bytes)) return e;
-    hipLaunchKernelGGL((wgrad_toimage_f32_kernel<ACT, TANHB>), dim3(grid), dim3(256), lds_bytes, st, a);
-    SISR_CHECK_LAUNCH();
-    return 0;
+    return sisr_launch<wgrad_toimage_f32_kernel<ACT, TANHB>>(dim3(grid), dim3(256), lds_bytes, 0, st, a);
 }
 
 int sisr_wgrad_toimage_f32_launch(const SisrWgradDesc* d, hipStream_t st) {

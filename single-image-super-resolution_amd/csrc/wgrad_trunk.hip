@@ -22,6 +22,7 @@
 // Slab layout as the generic kernel's ([chunk][tap][ci 32][64 co] + bias row), so the reduction and un-packing
 // kernels are shared.
 #include "sisr_bf16_stage.h"
+#include "sisr_instr.h"
 
 #include <algorithm>
 #include <cstring>
@@ -40,17 +41,9 @@
 #define WT_THREADS 512
 
 // phase timeline, developer build only (make trace; tools/trace_trunk.py with ROLE=wgrad)
-#ifdef SISR_CONV_TRACE
-__device__ unsigned long long sisr_wttrace_buf[512 * 128];
-#define WTT(k) do { if (threadIdx.x == 0 && blockIdx.x < 512 && (k) < 64) sisr_wttrace_buf[blockIdx.x * 128 + (k)] = wall_clock64(); } while (0)
-#define WTTP(k) do { if (threadIdx.x == 256 && blockIdx.x < 512 && (k) < 64) sisr_wttrace_buf[blockIdx.x * 128 + 64 + (k)] = wall_clock64(); } while (0)
-extern "C" int sisr_wttrace_read(void* dst, int n_u64) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(sisr_wttrace_buf), (size_t)n_u64 * 8, 0, hipMemcpyDeviceToHost);
-}
-#else
-#define WTT(k)
-#define WTTP(k)
-#endif
+SISR_TRACE_BUFFER(sisr_wttrace, 512, 128)
+#define WTT(k) SISR_TRACE_STAMP(sisr_wttrace, threadIdx.x == 0, blockIdx.x, k, 64, wall_clock64())
+#define WTTP(k) SISR_TRACE_STAMP(sisr_wttrace, threadIdx.x == 256, blockIdx.x, 64 + (k), 128, wall_clock64())
 
 struct WTrunkArgs {
     const void *x1, *g1, *g2;
@@ -384,15 +377,13 @@ static int wtrunk_grid(const SisrWgradDesc* d) {
 }
 
 extern "C" int sisr_wgrad_trunk_eligible(const SisrWgradDesc* d) {
-    const char* sw = getenv("SISR_TRUNK");                      // A/B switch: SISR_TRUNK=0 keeps the generic kernel
-    if (!d || (sw && sw[0] == '0')) return 0;
-    const char* sw2 = getenv("SISR_TRUNK_WGRAD");
-    if (sw2 && sw2[0] == '0') return 0;
+    if (!d || sisr_switch_off("SISR_TRUNK")) return 0;         // A/B switch: SISR_TRUNK=0 keeps the generic kernel
+    if (sisr_switch_off("SISR_TRUNK_WGRAD")) return 0;
     if (d->Cin != 64 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_y != 1 || d->pad_x != 1) return 0;
     // Cout = 64 (trunk: BatchNorm-backward gradient prologues), or 256 with the gradient stored shuffled and an
     // activation-backward prologue -- the upscale conv
-    const char* swu = getenv("SISR_TRUNK_UP");                 // A/B switch for the upscale conv alone
-    const bool up = !(swu && swu[0] == '0') && d->Cout == 256 && d->g_mode == SISR_X_NHWC_UNSHUFFLE2 && d->CoutPad == 256 &&
+    const bool up_off = sisr_switch_off("SISR_TRUNK_UP");      // A/B switch for the upscale conv alone
+    const bool up = !up_off && d->Cout == 256 && d->g_mode == SISR_X_NHWC_UNSHUFFLE2 && d->CoutPad == 256 &&
                     d->gpro_mode == SISR_PRO_ACT_BWD && (int64_t)d->N * d->H * d->W * 512 < (1ll << 31);
     if (!up && (d->Cout != 64 || d->g_mode != SISR_X_NHWC || d->CoutPad != 64)) return 0;
     if (d->x_mode != SISR_X_NHWC || !d->x_bf16 || !d->g_bf16) return 0;
@@ -405,27 +396,19 @@ extern "C" int sisr_wgrad_trunk_eligible(const SisrWgradDesc* d) {
     return xp && gp ? 1 : 0;
 }
 
-// slabs a launch of this descriptor writes (rows of `slab` at slab_stride): one per workgroup
-extern "C" int sisr_wgrad_toimage_eligible(const SisrWgradDesc* d);
-int sisr_wgrad_toimage_slabs(const SisrWgradDesc* d);                         // wgrad_toimage.hip
-extern "C" int sisr_wgrad_deep_eligible(const SisrWgradDesc* d);               // wgrad_deep.hip
-
 // The persistent kernel writes the gradient part of its slabs as bf16 (231 slabs x 147 KB written and re-read per layer were
 // two thirds of the finishing launch; a partial sum rounded to bf16 costs up to ~2e-3 relative on a cancelling total, inside this
 // build's error budget -- its tensors are bf16).  SISR_SLAB_BF16=0 keeps fp32 slabs (A/B).
-static bool wtrunk_slab_bf16() {
-    const char* e = getenv("SISR_SLAB_BF16");
-    return !(e && e[0] == '0');
-}
 // leading elements of every slab row that the launch of `d` stores as bf16 (pass it to sisr_slab_reduce_f32 /
 // sisr_bn_bwd_finalize_slab); 0: fp32 slabs
 extern "C" int64_t sisr_wgrad_bf16_slab_lead(const SisrWgradDesc* d) {
     if (!d) return 0;
-    if (sisr_wgrad_trunk_eligible(d)) return wtrunk_slab_bf16() ? (int64_t)d->slab_elems : 0;
+    if (sisr_wgrad_trunk_eligible(d)) return !sisr_switch_off("SISR_SLAB_BF16") ? (int64_t)d->slab_elems : 0;
     if (sisr_wgrad_toimage_eligible(d)) return 0;
     return sisr_wgrad_deep_eligible(d) && d->deep.slab_bf16 ? (int64_t)d->slab_elems : 0;
 }
 
+// slabs a launch of this descriptor writes (rows of `slab` at slab_stride): one per workgroup
 extern "C" int sisr_wgrad_bf16_slabs(const SisrWgradDesc* d) {
     if (!d) return SISR_E_BADARG;
     if (sisr_wgrad_trunk_eligible(d)) return wtrunk_grid(d) / (d->Cout == 256 ? 4 : 1);
@@ -436,11 +419,7 @@ extern "C" int sisr_wgrad_bf16_slabs(const SisrWgradDesc* d) {
 template <int GPRO>
 static int launch_wtrunk(const WTrunkArgs& a, int grid, hipStream_t st) {
     constexpr int lds_bytes = 2 * (WT_XBYTES + WT_DBYTES) + 2 * 64 * 4;
-    static SisrLdsCap cap;
-    if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&wgrad_trunk_kernel<GPRO>), lds_bytes)) return e;
-    hipLaunchKernelGGL((wgrad_trunk_kernel<GPRO>), dim3(grid), dim3(WT_THREADS), lds_bytes, st, a);
-    SISR_CHECK_LAUNCH();
-    return 0;
+    return sisr_launch<wgrad_trunk_kernel<GPRO>>(dim3(grid), dim3(WT_THREADS), lds_bytes, 0, st, a);
 }
 
 static WTrunkArgs wtrunk_args(const SisrWgradDesc* d);
@@ -470,7 +449,7 @@ static WTrunkArgs wtrunk_args(const SisrWgradDesc* d) {
     a.m_tiles_x = fdiv_magic(a.tiles_x); a.m_per_img = fdiv_magic(a.per_img);
     a.xpro = d->pro_mode;
     a.glog = d->Cout == 256 ? 2 : 0; a.cout_pad = d->Cout == 256 ? 256 : 64; a.gshuffle = d->g_mode == SISR_X_NHWC_UNSHUFFLE2 ? 1 : 0;
-    a.slab_bf16 = wtrunk_slab_bf16() ? 1 : 0;
+    a.slab_bf16 = !sisr_switch_off("SISR_SLAB_BF16") ? 1 : 0;
     return a;
 }
 
@@ -505,19 +484,11 @@ extern "C" int sisr_wgrad_trunk_batch_args(const SisrWgradDesc* descs, int32_t n
 extern "C" int sisr_wgrad_trunk_batch(const SisrWgradDesc* descs, const void* args_dev, int32_t n, int32_t wgs_per_layer, void* stream) {
     if (!args_dev || wgs_per_layer <= 0 || (int64_t)n * wgs_per_layer > 65535) return SISR_E_BADARG;
     if (int e = wtrunk_batch_check(descs, n)) return e;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = sisr_stream(stream);
     constexpr int lds_bytes = 2 * (WT_XBYTES + WT_DBYTES) + 2 * 64 * 4;
     const WTrunkArgs* table = static_cast<const WTrunkArgs*>(args_dev);
-    const dim3 grid(n * wgs_per_layer);
-    if (descs[0].gpro_mode == SISR_PRO_BNBWD) {
-        static SisrLdsCap cap;
-        if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&wgrad_trunk_table_kernel<SISR_PRO_BNBWD>), lds_bytes)) return e;
-        hipLaunchKernelGGL((wgrad_trunk_table_kernel<SISR_PRO_BNBWD>), grid, dim3(WT_THREADS), lds_bytes, st, table, wgs_per_layer);
-    } else {
-        static SisrLdsCap cap;
-        if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&wgrad_trunk_table_kernel<SISR_PRO_BNACT_BWD>), lds_bytes)) return e;
-        hipLaunchKernelGGL((wgrad_trunk_table_kernel<SISR_PRO_BNACT_BWD>), grid, dim3(WT_THREADS), lds_bytes, st, table, wgs_per_layer);
-    }
-    SISR_CHECK_LAUNCH();
-    return 0;
+    const dim3 grid(n * wgs_per_layer), block(WT_THREADS);
+    if (descs[0].gpro_mode == SISR_PRO_BNBWD)
+        return sisr_launch<wgrad_trunk_table_kernel<SISR_PRO_BNBWD>>(grid, block, lds_bytes, 0, st, table, wgs_per_layer);
+    return sisr_launch<wgrad_trunk_table_kernel<SISR_PRO_BNACT_BWD>>(grid, block, lds_bytes, 0, st, table, wgs_per_layer);
 }

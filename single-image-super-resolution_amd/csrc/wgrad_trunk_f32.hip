@@ -18,6 +18,7 @@
 // reduction and un-packing kernels are shared.  One slab per workgroup.
 #include "sisr_dev.h"
 #include "sisr_bf16_stage.h"
+#include "sisr_instr.h"
 
 #include <algorithm>
 #include <cstring>
@@ -42,22 +43,8 @@
 #define WF_PS 33                            // generic fp32 plan: krow = s * PS + ci
 #define WF_KROWP 100
 
-// barrier-wait accounting, developer build only (-DSISR_BARRIER_ACCT; tools/barrier_acct.py): see conv_trunk.hip
-#ifdef SISR_BARRIER_ACCT
-__device__ unsigned long long sisr_wfacct_buf[512 * 8];
-extern "C" int sisr_wfacct_read(void* dst, int n_u64) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(sisr_wfacct_buf), (size_t)n_u64 * 8, 0, hipMemcpyDeviceToHost);
-}
-#define WFA_DECL unsigned long long ba_wait = 0, ba_t0 = clock64()
-#define WFA_SYNC() do { const unsigned long long b0_ = clock64(); __syncthreads(); ba_wait += clock64() - b0_; } while (0)
-#define WFA_STORE(slot) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 512) { sisr_wfacct_buf[blockIdx.x * 8 + (slot)] = clock64() - ba_t0; sisr_wfacct_buf[blockIdx.x * 8 + (slot) + 1] = ba_wait; } } while (0)
-#define WFA_MARK(slot) do { if (threadIdx.x == 0 && blockIdx.x < 512) sisr_wfacct_buf[blockIdx.x * 8 + (slot)] = clock64(); } while (0)
-#else
-#define WFA_DECL
-#define WFA_SYNC() __syncthreads()
-#define WFA_STORE(slot)
-#define WFA_MARK(slot)
-#endif
+// barrier-wait accounting (make acct; tools/barrier_acct.py)
+SISR_ACCT_BUFFER(sisr_wfacct, 8)
 
 struct WTrunkF32Args {
     const float *x1, *g1, *g2;
@@ -248,21 +235,21 @@ __device__ __forceinline__ void wgrad_trunk_f32_body(const WTrunkF32Args& a, con
         issue(T + t_step, stB);
         if (T < a.total) commit(stA, 0);
         __syncthreads();
-        WFA_DECL;
+        SISR_ACCT_DECL;
         // unrolled by two: each staging set has a fixed name in each half (stB holds tile T + grid in the first)
         int cur = 0;
         while (T < a.total) {
             issue(T + 2 * t_step, stA);
             if (T + t_step < a.total) commit(stB, cur ^ 1);
-            WFA_SYNC();           // the next tile's images are complete; the consumers have finished reading this one
+            SISR_ACCT_SYNC();           // the next tile's images are complete; the consumers have finished reading this one
             T += t_step; cur ^= 1;
             if (T >= a.total) break;
             issue(T + 2 * t_step, stB);
             if (T + t_step < a.total) commit(stA, cur ^ 1);
-            WFA_SYNC();
+            SISR_ACCT_SYNC();
             T += t_step; cur ^= 1;
         }
-        if (wave == 4) WFA_STORE(2);
+        if (wave == 4) SISR_ACCT_STORE(sisr_wfacct, 2);
         __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0): the prefetch loads past the last tile
         if (a.bias_slab != nullptr) *reinterpret_cast<f32x4*>(lds + pt * 16) = bsum;      // the images are free by now
     } else {
@@ -274,10 +261,10 @@ __device__ __forceinline__ void wgrad_trunk_f32_body(const WTrunkF32Args& a, con
             for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
         // operand lane roles (sisr_dev.h): A = x[pixel 2 s + kk][ci = l31], B = dy[pixel 2 s + kk][co = l31]
         const int xoff = kk * WF_PB + (32 * gq + l31) * 4, doff = WF_XBYTES + kk * WF_PB + (32 * h + l31) * 4;
-        WFA_MARK(4);
+        SISR_ACCT_MARK(sisr_wfacct, 4);
         __syncthreads();
-        WFA_MARK(5);
-        WFA_DECL;
+        SISR_ACCT_MARK(sisr_wfacct, 5);
+        SISR_ACCT_DECL;
         int cur = 0;
         // (SPLIT) transposing-read lane roles: 16-lane group grp -> (channel half grp & 1, pixel half grp >> 1 of the 16-pixel K
         // step); inside the group lane 4q + p addresses (pixel row q, channels 4p .. 4p + 3)
@@ -307,7 +294,7 @@ __device__ __forceinline__ void wgrad_trunk_f32_body(const WTrunkF32Args& a, con
                         }
                     }
                 }
-                WFA_SYNC();
+                SISR_ACCT_SYNC();
                 continue;
             }
             const unsigned char* xb = lds + cur * (WF_XBYTES + WF_DBYTES) + xoff;
@@ -332,10 +319,10 @@ __device__ __forceinline__ void wgrad_trunk_f32_body(const WTrunkF32Args& a, con
                     }
                 }
             }
-            WFA_SYNC();
+            SISR_ACCT_SYNC();
         }
-        if (wave == 0) WFA_STORE(0);
-        WFA_MARK(6);
+        if (wave == 0) SISR_ACCT_STORE(sisr_wfacct, 0);
+        SISR_ACCT_MARK(sisr_wfacct, 6);
         // one slab per workgroup: [chunk gq][filter row ky][kx * 33 + ci][64 co]
 #pragma unroll
         for (int t = 0; t < 9; ++t)
@@ -353,7 +340,7 @@ __device__ __forceinline__ void wgrad_trunk_f32_body(const WTrunkF32Args& a, con
             a.bias_slab[(int64_t)t_first * a.slab_stride + 64 * cg + tid] = s;
         }
     }
-    WFA_MARK(7);
+    SISR_ACCT_MARK(sisr_wfacct, 7);
 }
 
 template <int GPRO, bool SPLIT>
@@ -383,15 +370,13 @@ static int wf_grid(const SisrWgradDesc* d) {
 }
 
 extern "C" int sisr_wgrad_trunk_f32_eligible(const SisrWgradDesc* d) {
-    const char* sw = getenv("SISR_TRUNK");                      // A/B switch: SISR_TRUNK=0 keeps the generic kernel
-    if (!d || (sw && sw[0] == '0')) return 0;
-    const char* sw2 = getenv("SISR_TRUNK_WGRAD");
-    if (sw2 && sw2[0] == '0') return 0;
+    if (!d || sisr_switch_off("SISR_TRUNK")) return 0;         // A/B switch: SISR_TRUNK=0 keeps the generic kernel
+    if (sisr_switch_off("SISR_TRUNK_WGRAD")) return 0;
     if (d->Cin != 64 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_y != 1 || d->pad_x != 1) return 0;
     // Cout = 64 (trunk: BatchNorm-backward gradient prologues), or 256 with the gradient stored shuffled and an
     // activation-backward prologue -- the upscale conv
-    const char* swu = getenv("SISR_TRUNK_UP");                 // A/B switch for the upscale conv alone
-    const bool up = !(swu && swu[0] == '0') && d->Cout == 256 && d->g_mode == SISR_X_NHWC_UNSHUFFLE2 && d->CoutPad == 256 &&
+    const bool up_off = sisr_switch_off("SISR_TRUNK_UP");      // A/B switch for the upscale conv alone
+    const bool up = !up_off && d->Cout == 256 && d->g_mode == SISR_X_NHWC_UNSHUFFLE2 && d->CoutPad == 256 &&
                     d->gpro_mode == SISR_PRO_ACT_BWD && (int64_t)d->N * d->H * d->W * 1024 < (1ll << 31);
     if (!up && (d->Cout != 64 || d->g_mode != SISR_X_NHWC || d->CoutPad != 64)) return 0;
     if (d->x_mode != SISR_X_NHWC || d->x_bf16 || d->g_bf16) return 0;
@@ -405,11 +390,6 @@ extern "C" int sisr_wgrad_trunk_f32_eligible(const SisrWgradDesc* d) {
 }
 
 // slabs a launch of this descriptor writes (rows of `slab` at slab_stride)
-extern "C" int sisr_wgrad_thin_eligible(const SisrWgradDesc* d);
-int sisr_wgrad_thin_slabs(const SisrWgradDesc* d);                            // wgrad_thin.hip
-extern "C" int sisr_wgrad_toimage_f32_eligible(const SisrWgradDesc* d);
-int sisr_wgrad_toimage_slabs(const SisrWgradDesc* d);                         // wgrad_toimage.hip
-
 extern "C" int sisr_wgrad_f32_slabs(const SisrWgradDesc* d) {
     if (!d) return SISR_E_BADARG;
     if (sisr_wgrad_trunk_f32_eligible(d)) return wf_grid(d) / (d->Cout == 256 ? 4 : 1);
@@ -420,11 +400,7 @@ extern "C" int sisr_wgrad_f32_slabs(const SisrWgradDesc* d) {
 template <int GPRO, bool SPLIT>
 static int launch_wf_t(const WTrunkF32Args& a, int grid, hipStream_t st) {
     constexpr int lds_bytes = SPLIT ? 2 * (WS_XBYTES + WS_DBYTES) : 2 * (WF_XBYTES + WF_DBYTES);
-    static SisrLdsCap cap;
-    if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&wgrad_trunk_f32_kernel<GPRO, SPLIT>), lds_bytes)) return e;
-    hipLaunchKernelGGL((wgrad_trunk_f32_kernel<GPRO, SPLIT>), dim3(grid), dim3(WF_THREADS), lds_bytes, st, a);
-    SISR_CHECK_LAUNCH();
-    return 0;
+    return sisr_launch<wgrad_trunk_f32_kernel<GPRO, SPLIT>>(dim3(grid), dim3(WF_THREADS), lds_bytes, 0, st, a);
 }
 template <int GPRO>
 static int launch_wf(const WTrunkF32Args& a, bool split, int grid, hipStream_t st) {
@@ -490,17 +466,13 @@ extern "C" int sisr_wgrad_trunk_f32_batch_args(const SisrWgradDesc* descs, int32
 template <int GPRO, bool SPLIT>
 static int launch_wf_table(const WTrunkF32Args* table, int n, int wpl, hipStream_t st) {
     constexpr int lds_bytes = SPLIT ? 2 * (WS_XBYTES + WS_DBYTES) : 2 * (WF_XBYTES + WF_DBYTES);
-    static SisrLdsCap cap;
-    if (int e = sisr_raise_lds_cap(cap, reinterpret_cast<const void*>(&wgrad_trunk_f32_table_kernel<GPRO, SPLIT>), lds_bytes)) return e;
-    hipLaunchKernelGGL((wgrad_trunk_f32_table_kernel<GPRO, SPLIT>), dim3(n * wpl), dim3(WF_THREADS), lds_bytes, st, table, wpl);
-    SISR_CHECK_LAUNCH();
-    return 0;
+    return sisr_launch<wgrad_trunk_f32_table_kernel<GPRO, SPLIT>>(dim3(n * wpl), dim3(WF_THREADS), lds_bytes, 0, st, table, wpl);
 }
 
 extern "C" int sisr_wgrad_trunk_f32_batch(const SisrWgradDesc* descs, const void* args_dev, int32_t n, int32_t wgs_per_layer, void* stream) {
     if (!args_dev || wgs_per_layer <= 0 || (int64_t)n * wgs_per_layer > 65535) return SISR_E_BADARG;
     if (int e = wf_batch_check(descs, n)) return e;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = sisr_stream(stream);
     const WTrunkF32Args* table = static_cast<const WTrunkF32Args*>(args_dev);
     const bool split = descs[0].mfma_split != 0;
     if (descs[0].gpro_mode == SISR_PRO_BNBWD)
