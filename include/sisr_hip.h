@@ -562,6 +562,20 @@ int sisr_bicubic_fwd(const float *x, float *y, int32_t NC, int32_t H, int32_t W,
 int sisr_bicubic_bwd(const float *dy, const float *y_clamped, float *dx, int32_t NC, int32_t H,
                      int32_t W, int32_t Ho, int32_t Wo, void *stream);
 
+/* ---- image-quality metrics: per-image PSNR and SSIM of two NCHW fp32 batches (the reference reports neither: its to-do list,
+ *      README.md:88).  View applied on load: `crop` pixels stripped from every side; C == 3 with luma != 0: the BT.601 full-range
+ *      plane Y = 0.299 R + 0.587 G + 0.114 B instead of the three planes.  PSNR = 10 log10(data_range^2 / mse), +inf for equal
+ *      images; SSIM: 11 x 11 Gaussian window (sigma 1.5), "valid" positions only, C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2,
+ *      mean over planes and positions.  Two launches (tiles -> `work`, then a fixed-order sum in double), no atomics: bit-identical
+ *      from call to call, nothing synchronises with the host. ---------------------------------- */
+/* HOST: floats of workspace for the shapes below; < 0 (SISR_E_UNSUPPORTED / bad argument) when C is not 1 or 3,
+ * crop < 0, or H - 2*crop < 11 or W - 2*crop < 11 */
+int sisr_image_metrics_ws_floats(int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int32_t luma);
+/* a, b: [N][C][H][W] fp32; psnr / ssim: [N] fp32, either may be NULL (then not computed) */
+int sisr_image_metrics(const float *a, const float *b, int32_t N, int32_t C, int32_t H, int32_t W,
+                       int32_t crop, int32_t luma, float data_range, float *work,
+                       float *psnr, float *ssim, void *stream);
+
 /* ---- misc ---------------------------------------------------------------------------------- */
 /* ---- optimizer: fused multi-tensor Adam --------------------------------------------------
  * One launch performs torch.optim.Adam's update (amsgrad=False, maximize=False; config.py:292-294, stepped at

@@ -1,0 +1,111 @@
+"""Image-quality metrics on the device: per-image PSNR and SSIM of two NCHW batches on the gfx950 kernels of
+csrc/metrics.hip, and ``evaluate_generator`` -- a whole validation pass (degrade, super-resolve in eval mode, score).
+
+The reference reports neither number (its to-do list, README.md:88); a host-side SSIM would need a device -> host copy in
+the middle of the training loop.  Here nothing synchronises with the host: the results are fp32 device tensors, bit-identical
+from call to call, and the launches can be captured by ``graph.GraphedStep``.
+
+These are METRICS, not losses: the inputs are detached and nothing here is differentiable.
+
+Definitions (sisr_hip.h): the view ``crop_border`` (pixels stripped from every side) and ``luma`` (C == 3: the BT.601
+full-range plane Y = 0.299 R + 0.587 G + 0.114 B of the normalised values) is applied first;
+PSNR = 10 log10(data_range^2 / mse), +inf for equal images; SSIM is Wang et al.'s with the 11 x 11 Gaussian window
+(sigma 1.5), "valid" window positions only, C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2, averaged over planes and
+positions.  ``data_range`` defaults to 2.0: the project's images are normalised to [-1, 1].
+"""
+import torch
+
+from . import _lib as L
+from .engine import _stream, require_gpu_tensor
+from .utils import lr_from_hr
+
+WINDOW = 11
+
+
+def _validate(a, b, data_range, crop_border):
+    """argument errors come before the device check: they are the caller's, whatever the tensors live on"""
+    for t in (a, b):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError('metrics take two 4-D [N, C, H, W] tensors, got %s'
+                             % (tuple(t.shape) if isinstance(t, torch.Tensor) else type(t),))
+    if a.shape != b.shape:
+        raise ValueError('metrics: the images differ in shape: %s vs %s' % (tuple(a.shape), tuple(b.shape)))
+    n, c, h, w = a.shape
+    if n < 1:
+        raise ValueError('metrics: empty batch')
+    if c not in (1, 3):
+        raise ValueError('metrics: 1 or 3 channels expected, got %d' % c)
+    crop = int(crop_border)
+    if crop != crop_border or crop < 0:
+        raise ValueError('metrics: crop_border must be a non-negative integer, got %r' % (crop_border,))
+    if h - 2 * crop < WINDOW or w - 2 * crop < WINDOW:
+        raise ValueError('metrics: %d x %d pixels remain after cropping %d from every side; the SSIM window needs %d x %d'
+                         % (h - 2 * crop, w - 2 * crop, crop, WINDOW, WINDOW))
+    if not float(data_range) > 0.0:
+        raise ValueError('metrics: data_range must be positive, got %r' % (data_range,))
+    return crop
+
+
+def _native(t, what):
+    """the kernels' form: detached fp32 contiguous device tensor"""
+    t = t.detach().float()
+    require_gpu_tensor(t, what)
+    return t.contiguous()
+
+
+def _run(a, b, data_range, crop_border, luma, want_psnr, want_ssim):
+    crop = _validate(a, b, data_range, crop_border)
+    a, b = _native(a, 'metrics input a'), _native(b, 'metrics input b')
+    if a.device != b.device:
+        raise ValueError('metrics: the images live on different devices: %s vs %s' % (a.device, b.device))
+    n, c, h, w = a.shape
+    lib = L.lib()
+    ws = L.check_count(lib.sisr_image_metrics_ws_floats(n, c, h, w, crop, int(bool(luma))), 'sisr_image_metrics_ws_floats')
+    work = torch.empty(ws, dtype=torch.float32, device=a.device)
+    psnr_t = torch.empty(n, dtype=torch.float32, device=a.device) if want_psnr else None
+    ssim_t = torch.empty(n, dtype=torch.float32, device=a.device) if want_ssim else None
+    L.check(lib.sisr_image_metrics(a.data_ptr(), b.data_ptr(), n, c, h, w, crop, int(bool(luma)), float(data_range),
+                                   work.data_ptr(), None if psnr_t is None else psnr_t.data_ptr(),
+                                   None if ssim_t is None else ssim_t.data_ptr(), _stream()), 'sisr_image_metrics')
+    return psnr_t, ssim_t
+
+
+def psnr(a, b, data_range=2.0, crop_border=0, luma=False):
+    """per-image peak signal-to-noise ratio in dB -> fp32 Tensor[N] on the inputs' device (a metric: inputs are detached)"""
+    return _run(a, b, data_range, crop_border, luma, True, False)[0]
+
+
+def ssim(a, b, data_range=2.0, crop_border=0, luma=False):
+    """per-image structural similarity -> fp32 Tensor[N] on the inputs' device (a metric: inputs are detached)"""
+    return _run(a, b, data_range, crop_border, luma, False, True)[1]
+
+
+def psnr_ssim(a, b, data_range=2.0, crop_border=0, luma=False):
+    """-> (psnr Tensor[N], ssim Tensor[N]) from one launch sequence (a metric: inputs are detached)"""
+    return _run(a, b, data_range, crop_border, luma, True, True)
+
+
+def evaluate_generator(net_g, img_hr, image_size_lr, crop_border=None, luma=False):
+    """One validation pass: ``lr_from_hr(img_hr)`` -> ``net_g`` in eval mode under ``no_grad`` -> ``psnr_ssim(sr, img_hr)``.
+
+    Eval mode means running-statistics BatchNorm and no spectral-norm power iteration, so -- unlike calling the net in train
+    mode, as the reference's ``save_curr_vis`` does -- the pass leaves every buffer of ``net_g`` as it was (BatchNorm running
+    statistics, ``num_batches_tracked``, spectral-norm ``u`` / ``v``).  The training flag of every submodule is restored
+    afterwards, also when the pass raises.  ``crop_border=None`` crops by the scale factor (the SR convention).
+    Returns ``dict(psnr=Tensor[N], ssim=Tensor[N])``."""
+    modes = [(m, m.training) for m in net_g.modules()]
+    try:
+        net_g.eval()
+        with torch.no_grad():
+            lr = lr_from_hr(img_hr, image_size_lr)
+            sr = net_g(lr)
+    finally:
+        for m, was in modes:
+            m.training = was
+    if sr.shape != img_hr.shape:
+        raise ValueError('evaluate_generator: the generator maps %s to %s, the HR batch is %s'
+                         % (tuple(lr.shape), tuple(sr.shape), tuple(img_hr.shape)))
+    if crop_border is None:
+        crop_border = sr.shape[-1] // lr.shape[-1]
+    p, s = psnr_ssim(sr, img_hr, crop_border=crop_border, luma=luma)
+    return dict(psnr=p, ssim=s)
