@@ -576,6 +576,27 @@ int sisr_image_metrics(const float *a, const float *b, int32_t N, int32_t C, int
                        int32_t crop, int32_t luma, float data_range, float *work,
                        float *psnr, float *ssim, void *stream);
 
+/* ---- losses: the feature MSE of train.py:183-186 and the BCE of config.py:107, forward and backward, fp32.
+ *      Fixed-order sums, no atomics: bit-identical from call to call; nothing synchronises with the host.  The upstream gradient
+ *      `g` of the backward entry points is ONE float in DEVICE memory (it is never fetched).  Tensors need only 4-byte alignment:
+ *      16-byte accesses are used when every pointer of a call sits at the same offset inside its 16-byte line. --------------- */
+/* HOST: floats of workspace for a feature MSE over n elements; < 0 for n < 1 (bad argument) or n > 2^40 (too big) */
+int sisr_mse_ws_floats(int64_t n);
+/* loss[0] = weight * mean((a - b)^2) over n contiguous elements.  Two launches: one partial per workgroup of a capped grid
+ * (2048, or SISR_PERSIST_MAX_WG) into `work`, then one workgroup adds them in double */
+int sisr_mse_fwd(const float *a, const float *b, int64_t n, float weight, float *work, float *loss, void *stream);
+/* db = c (b - a), da = -db with c = 2 weight g[0] / n; da / db: [n], either may be NULL (then not written).  One launch */
+int sisr_mse_bwd(const float *a, const float *b, const float *g, int64_t n, float weight, float *da, float *db,
+                 void *stream);
+/* loss[0] = weight * mean_i -(t_i max(log p_i, -100) + (1 - t_i) max(log(1 - p_i), -100)), mean_p[0] = mean_i p_i; either may
+ * be NULL.  t_vec: [n] targets, or NULL for the one target t_scalar.  One workgroup, any n >= 1.  No range check on p: a NaN
+ * or an out-of-range element gives a NaN loss */
+int sisr_bce_fwd(const float *p, const float *t_vec, float t_scalar, int64_t n, float weight, float *loss,
+                 float *mean_p, void *stream);
+/* dp_i = weight g[0] (p_i - t_i) / max(p_i (1 - p_i), 1e-12) / n (torch's formula and epsilon) */
+int sisr_bce_bwd(const float *p, const float *t_vec, float t_scalar, int64_t n, float weight, const float *g,
+                 float *dp, void *stream);
+
 /* ---- misc ---------------------------------------------------------------------------------- */
 /* ---- optimizer: fused multi-tensor Adam --------------------------------------------------
  * One launch performs torch.optim.Adam's update (amsgrad=False, maximize=False; config.py:292-294, stepped at

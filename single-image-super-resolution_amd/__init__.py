@@ -9,7 +9,7 @@ reference's own module names; ``install()`` additionally patches ``utils.lr_from
 from . import _lib  # noqa: F401
 
 
-def install(fused_adam=False):
+def install(fused_adam=False, fused_losses=False):
     """Register this package's model modules under the reference's top-level module names, so the
     reference's ``train.py`` / ``config.py`` import them unchanged, and point ``utils.lr_from_hr`` -- the one hot
     function of the reference's ``utils`` module (utils.py:22-31; called at train.py:46,96, config.py:272) -- at the
@@ -17,12 +17,16 @@ def install(fused_adam=False):
     (``save_and_show``, ``save_curr_vis``, ``SamplerRange`` ... train.py:15,36, config.py:250) stay the reference's;
     only when no ``utils`` module is importable at all (this repository's own tests) is the package's ``utils``
     registered under that name.  ``fused_adam=True`` also points ``torch.optim.Adam`` (what config.py:293-294
-    instantiates) at the fused multi-tensor Adam of ``optim.py``."""
+    instantiates) at the fused multi-tensor Adam of ``optim.py``; ``fused_losses=True`` points ``torch.nn.BCELoss`` (what
+    config.py:107 instantiates) at the fused ``losses.BCELoss``."""
     import importlib
     import sys
     if fused_adam:
         import torch
         torch.optim.Adam = importlib.import_module('.optim', __name__).Adam
+    if fused_losses:
+        import torch
+        torch.nn.BCELoss = importlib.import_module('.losses', __name__).BCELoss
     for name in ('model_generator', 'model_generator_progressive', 'model_discriminator', 'model_content_extractor'):
         sys.modules[name] = importlib.import_module('.' + name, __name__)
     ours = importlib.import_module('.utils', __name__)

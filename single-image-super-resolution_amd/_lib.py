@@ -187,6 +187,11 @@ _SIGS = {
     'sisr_bicubic_bwd': [_f, _f, _f, _i32, _i32, _i32, _i32, _i32, _f],
     'sisr_image_metrics_ws_floats': [_i32, _i32, _i32, _i32, _i32, _i32],
     'sisr_image_metrics': [_f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f, _f, _f, _f],
+    'sisr_mse_ws_floats': [_i64],
+    'sisr_mse_fwd': [_f, _f, _i64, _f32, _f, _f, _f],
+    'sisr_mse_bwd': [_f, _f, _f, _i64, _f32, _f, _f, _f],
+    'sisr_bce_fwd': [_f, _f, _f32, _i64, _f32, _f, _f, _f],
+    'sisr_bce_bwd': [_f, _f, _f32, _i64, _f32, _f, _f, _f],
     'sisr_struct_sizes': [C.POINTER(_i32), _i32],
     'sisr_device_info': [C.POINTER(_i32), C.POINTER(_i32), C.c_char_p, _i32],
     'sisr_mfma_selftest': [_f, _f],

@@ -1,0 +1,170 @@
+"""The losses of an SRGAN iteration on the device: the feature ("content") MSE of train.py:183-186 and the binary cross-entropy
+of config.py:107 as fused gfx950 kernels (csrc/losses.hip), forward and backward, and the three loss functions of
+train.py:128-186 written on top of them with their globals made arguments.
+
+The torch expressions they stand in for, ``torch.mean(torch.pow(a - b, 2))`` and ``nn.BCELoss()(p, label)``, are elementwise
+launches: the MSE moves its two feature tensors (70.8 MB each at B16 / HR 96^2 under ``MaskedVGG(0b01111)``) through HBM at least
+11 times forward + backward and keeps ``a - b`` alive; ``feature_mse`` takes 5 passes (read a and b, read them again, write one
+gradient) and saves nothing but its inputs.  ``bce_loss`` needs no label tensor, returns mean(p) -- the ``D_x`` / ``D_G_z``
+statistics -- from the same launch, and has no device-side range assertion: a NaN in gives a NaN out, never an abort.
+
+Nothing here synchronises with the host: losses and statistics are 0-dim fp32 device tensors, bit-identical from call to call,
+and the launches can be captured by ``graph.GraphedStep``.  Opt-in: ``install(fused_losses=True)`` points ``torch.nn.BCELoss`` at
+``BCELoss``; a trainer rebinds its ``content_loss_g`` / ``adversarial_loss_*`` to the functions below.
+"""
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib as L
+from .engine import _stream, require_gpu_tensor
+
+
+def _check_tensor(t, what):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError('%s: a tensor is expected, got %s' % (what, type(t)))
+    if t.dtype != torch.float32:
+        raise ValueError('%s: fp32 expected, got %s' % (what, t.dtype))
+    if t.numel() < 1:
+        raise ValueError('%s: empty tensor' % what)
+
+
+def _validate_pair(a, b, what):
+    """argument errors come before the device check: they are the caller's, whatever the tensors live on"""
+    _check_tensor(a, what)
+    _check_tensor(b, what)
+    if a.shape != b.shape:
+        raise ValueError('%s: the tensors differ in shape (no broadcasting): %s vs %s' % (what, tuple(a.shape), tuple(b.shape)))
+    if a.device != b.device:
+        raise ValueError('%s: the tensors live on different devices: %s vs %s' % (what, a.device, b.device))
+
+
+def _scalar(dev):
+    return torch.empty((), dtype=torch.float32, device=dev)
+
+
+class _FeatureMSE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, weight):
+        a, b = a.detach().contiguous(), b.detach().contiguous()
+        lib, n = L.lib(), a.numel()
+        work = torch.empty(L.check_count(lib.sisr_mse_ws_floats(n), 'sisr_mse_ws_floats'), dtype=torch.float32, device=a.device)
+        loss = _scalar(a.device)
+        L.check(lib.sisr_mse_fwd(a.data_ptr(), b.data_ptr(), n, weight, work.data_ptr(), loss.data_ptr(), _stream()),
+                'sisr_mse_fwd')
+        ctx.save_for_backward(a, b)            # the inputs themselves (their contiguous form): no intermediate is kept
+        ctx.weight = weight
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        if da is not None or db is not None:
+            L.check(L.lib().sisr_mse_bwd(a.data_ptr(), b.data_ptr(), g.data_ptr(), a.numel(), ctx.weight,
+                                         None if da is None else da.data_ptr(), None if db is None else db.data_ptr(),
+                                         _stream()), 'sisr_mse_bwd')
+        return da, db, None
+
+
+def feature_mse(a, b, weight=1.0):
+    """``weight * torch.mean(torch.pow(a - b, 2))`` -> 0-dim fp32 device tensor; differentiable with respect to ``a``, ``b`` or
+    both (only what requires a gradient is computed).  Any two equal shapes: feature maps, or images under the ``identity()``
+    extractor.  Non-contiguous inputs are made contiguous first."""
+    _validate_pair(a, b, 'feature_mse')
+    require_gpu_tensor(a, 'feature_mse input a')
+    require_gpu_tensor(b, 'feature_mse input b')
+    return _FeatureMSE.apply(a, b, float(weight))
+
+
+class _BCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, t_vec, t_scalar, weight):
+        p = p.detach().contiguous()
+        t_vec = None if t_vec is None else t_vec.detach().contiguous()
+        loss, mean_p = _scalar(p.device), _scalar(p.device)
+        L.check(L.lib().sisr_bce_fwd(p.data_ptr(), None if t_vec is None else t_vec.data_ptr(), t_scalar, p.numel(), weight,
+                                     loss.data_ptr(), mean_p.data_ptr(), _stream()), 'sisr_bce_fwd')
+        ctx.save_for_backward(p, t_vec)
+        ctx.t_scalar, ctx.weight = t_scalar, weight
+        ctx.mark_non_differentiable(mean_p)
+        return loss, mean_p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_mean):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        p, t_vec = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        dp = torch.empty_like(p)
+        L.check(L.lib().sisr_bce_bwd(p.data_ptr(), None if t_vec is None else t_vec.data_ptr(), ctx.t_scalar, p.numel(),
+                                     ctx.weight, g.data_ptr(), dp.data_ptr(), _stream()), 'sisr_bce_bwd')
+        return dp, None, None, None
+
+
+def bce_loss(p, target, weight=1.0, return_mean=False):
+    """``weight * F.binary_cross_entropy(p, target)`` (mean reduction, log terms clamped at -100 as torch does) -> 0-dim fp32
+    device tensor, or ``(loss, mean(p))`` with ``return_mean``.  ``target``: a Python number (one label for every element, as the
+    reference's ``torch.full`` label tensors) or a tensor of ``p``'s shape; no gradient flows to it.  Elements of ``p`` outside
+    [0, 1] or NaN give a NaN loss, not a device-side assertion."""
+    _check_tensor(p, 'bce_loss input')
+    if isinstance(target, torch.Tensor):
+        _validate_pair(p, target, 'bce_loss')
+        t_vec, t_scalar = target, 0.0
+    elif isinstance(target, (int, float)):
+        t_vec, t_scalar = None, float(target)
+    else:
+        raise ValueError('bce_loss: the target is a number or a tensor of the shape of the input, got %s' % type(target))
+    require_gpu_tensor(p, 'bce_loss input')
+    if t_vec is not None:
+        require_gpu_tensor(t_vec, 'bce_loss target')
+    loss, mean_p = _BCE.apply(p, t_vec, t_scalar, float(weight))
+    return (loss, mean_p) if return_mean else loss
+
+
+class BCELoss(torch.nn.Module):
+    """``torch.nn.BCELoss`` as the reference uses it (config.py:107: no rescaling weight, mean reduction) on ``bce_loss``"""
+
+    def __init__(self, weight=None, size_average=None, reduce=None, reduction='mean'):
+        super().__init__()
+        if weight is not None or size_average is not None or reduce is not None or reduction != 'mean':
+            raise NotImplementedError("fused BCELoss: only weight=None, reduction='mean' are implemented "
+                                      '(the reference uses nothing else, config.py:107)')
+
+    def forward(self, input, target):
+        return bce_loss(input, target)
+
+
+# ---- the loss functions of train.py:128-186; the D statistics come back as device tensors (no .item()) ------------------------
+def content_loss_g(content_extractor, real, fake, weight=1.0):
+    """train.py:183-186 -> weight * mean((extractor(real) - extractor(fake))^2)"""
+    return feature_mse(content_extractor(real), content_extractor(fake), weight)
+
+
+def adversarial_loss_g(net_d, fake, real_label=1.0, weight=1.0):
+    """train.py:171-181 -> (D_G_z2, errG), errG already times ``weight`` (train.py:88)"""
+    err, d_g_z2 = bce_loss(net_d(fake).view(-1), real_label, weight, return_mean=True)
+    return d_g_z2, err
+
+
+def adversarial_loss_d(net_d, real, curr_fake, old_fakes, ratio=0.01, real_label=0.9, fake_label=0.0, weight=1.0):
+    """The D-step loss of train.py:128-168 over ``[curr_fake] + sampled old fakes`` (every batch is its own D forward: its own
+    BatchNorm statistics and spectral-norm iteration, as in the reference).  ``old_fakes``: a ``replay.DeviceReplayList`` (sampled
+    through its ``sample``) or a plain list (sampled with ``np.random.choice`` exactly as train.py:144-146: the same draw from the
+    same generator either way).  -> (D_G_z1, D_x, errD), errD already times ``weight`` (train.py:73)"""
+    err, d_x = bce_loss(net_d(real).view(-1), real_label, weight, return_mean=True)
+    if hasattr(old_fakes, 'sample'):
+        sampled = old_fakes.sample(ratio)
+    else:
+        idx = np.random.choice(list(range(len(old_fakes))), int(len(old_fakes) * ratio), replace=False)
+        sampled = [old_fakes[int(i)] for i in idx]
+    d_g_z1 = None
+    for fake in [curr_fake] + sampled:
+        e, m = bce_loss(net_d(fake).view(-1), fake_label, weight, return_mean=True)
+        err = err + e
+        d_g_z1 = m if d_g_z1 is None else d_g_z1 + m
+    return d_g_z1, d_x, err
