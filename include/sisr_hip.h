@@ -613,6 +613,32 @@ int64_t sisr_adam_blocks(int64_t numel);
 int sisr_adam_step(const SisrAdamDesc *table_dev, int32_t n, int64_t total_blocks, double lr, double beta1, double beta2,
                    double eps, double weight_decay, double bias_corr1, double bias_corr2, void *stream);
 
+/* ---- the same step with its per-step scalars in DEVICE memory (capturable: DESIGN.md section 10) --------------
+ * Nothing below takes a step count, a learning rate or a bias correction from the host, so the three launches can be
+ * captured into a HIP graph and still advance on every replay.  Same table and block mapping as above.  Sequence per step:
+ *   [sisr_adam_grad_sumsq]  only with a guard: one double partial of sum g^2 per workgroup into `partials`
+ *                           (sisr_adam_norm_ws_doubles doubles; squares and sums in double, fixed order, no atomics);
+ *   sisr_adam_prepare       one thread per tensor, any n.  With n_partials > 0 it first adds the partials in a fixed order and
+ *                           derives norm, coef = min(1, max_norm / (norm + 1e-6)) (max_norm < 0: coef = 1) and skip =
+ *                           skip_nonfinite && the fp32 norm is not finite; with write_ctrl it stores ctrl[4] = { fp32 norm,
+ *                           fp32 coef, int32 skip, int32 running count of skipped steps }.  Then, unless skip, per tensor i:
+ *                           t = *steps_dev[i] (fp32 count, torch's capturable layout); consts[2i] = lr / (1 - beta1^(t+1)),
+ *                           consts[2i+1] = 1 / sqrt(1 - beta2^(t+1)), both in double and rounded to fp32 once;
+ *                           *steps_dev[i] = t + 1.  lr_dev: ONE device scalar, fp32 or (lr_is_f64) fp64.
+ *                           Several tables that share one norm: run every sum of squares into consecutive ranges of one
+ *                           workspace first, then one prepare per table over the WHOLE range, write_ctrl on the first only.
+ *   sisr_adam_step_dev      the update; g is multiplied by ctrl's coef before weight decay is added (the gradient tensor
+ *                           is only read); when ctrl's skip flag is set the kernel exits before any store.
+ * steps_dev: n device pointers in DEVICE memory; consts: 2 n floats; ctrl: 4 words, written only by the prepare launch.
+ * SISR_E_BADARG before any HIP call for null pointers, n <= 0, total_blocks outside [1, 2^31) and betas outside [0, 1). */
+int64_t sisr_adam_norm_ws_doubles(int64_t total_blocks);
+int sisr_adam_grad_sumsq(const SisrAdamDesc *table_dev, int32_t n, int64_t total_blocks, double *partials, void *stream);
+int sisr_adam_prepare(float *const *steps_dev, int32_t n, const void *lr_dev, int32_t lr_is_f64, double beta1, double beta2,
+                      const double *partials, int64_t n_partials, double max_norm, int32_t skip_nonfinite, int32_t write_ctrl,
+                      float *ctrl, float *consts, void *stream);
+int sisr_adam_step_dev(const SisrAdamDesc *table_dev, int32_t n, int64_t total_blocks, const float *consts, const float *ctrl,
+                       double beta1, double beta2, double eps, double weight_decay, void *stream);
+
 /* sizeof() of the descriptor structs in declaration order (Conv, Wgrad, Weight, WeightGrad,
  * BnBwd, ConvPlan, DeepPlan, WgradDeepPlan) so a binding can verify its mirror of this header; returns the count. */
 int sisr_struct_sizes(int32_t *out, int32_t cap);

@@ -165,6 +165,10 @@ _SIGS = {
     'sisr_add': [_f, _f, _f, _i64, _i32, _f],
     'sisr_adam_blocks': [_i64],
     'sisr_adam_step': [_f, _i32, _i64] + [C.c_double] * 7 + [_f],
+    'sisr_adam_norm_ws_doubles': [_i64],
+    'sisr_adam_grad_sumsq': [_f, _i32, _i64, _f, _f],
+    'sisr_adam_prepare': [_f, _i32, _f, _i32, C.c_double, C.c_double, _f, _i64, C.c_double, _i32, _i32, _f, _f, _f],
+    'sisr_adam_step_dev': [_f, _i32, _i64, _f, _f] + [C.c_double] * 4 + [_f],
     'sisr_nhwc_to_nchw': [_f, _f, _f, _f, _f32, _f, _i64, _i32, _i32, _i32, _i32, _i32, _f],
     'sisr_nchw_to_nhwc': [_f, _i64, _f, _i32, _i32, _i32, _i32, _i32, _f],
     'sisr_nchw_grad_to_nhwc4': [_f, _f, _f, _i32, _i32, _i32, _i32, _i32, _f],
@@ -228,6 +232,7 @@ def lib():
         fn.argtypes = args
         fn.restype = C.c_int
     L.sisr_adam_blocks.restype = C.c_int64
+    L.sisr_adam_norm_ws_doubles.restype = C.c_int64
     L.sisr_wgrad_bf16_slab_lead.restype = C.c_int64
     L.sisr_version.restype = C.c_char_p
     L.sisr_version.argtypes = []

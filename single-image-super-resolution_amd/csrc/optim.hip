@@ -5,20 +5,44 @@
 //     p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // HBM-bound: 4 reads + 3 writes of 4 bytes per parameter.  The descriptor table lives in device memory; a workgroup
 // finds its tensor by a binary search over the per-tensor first-block indices.
+//
+// Two families share the update (adam_update_block):
+//   host state    adam_step_kernel: lr and the bias corrections arrive as launch arguments (sisr_adam_step);
+//   device state  the step count of every tensor, the learning rate and the guards live in device memory, so the launches
+//                 below can sit inside a captured HIP graph and still advance from replay to replay:
+//       adam_sumsq_kernel    (guards only) one double partial of sum g^2 per workgroup, same block mapping as the step;
+//       adam_prepare_kernel  one thread per tensor: partials -> norm / clip coefficient / skip flag, t -> t + 1, and the
+//                            tensor's step_size and 1 / sqrt(1 - beta2^t);
+//       adam_step_dev_kernel the update with those per-tensor constants, g scaled by the clip coefficient, nothing stored
+//                            when the skip flag is set.
+// No atomics, every sum in a fixed order: the same inputs give the same bits.
 #include "sisr_dev.h"
+
+#include <cmath>
 
 #define ADAM_CHUNK (SISR_BLOCK * 16)          // elements per workgroup
 
-__global__ void __launch_bounds__(SISR_BLOCK) adam_step_kernel(const SisrAdamDesc* __restrict__ table, int n, float step_size,
-                                                                float omb1, float beta2, float omb2, float eps, float wd,
-                                                                float inv_sqrt_bc2) {
-    int lo = 0, hi = n - 1;                     // last tensor whose block_start <= blockIdx.x
+// control block of the device-state family: four 32-bit words
+#define ADAM_CTRL_NORM 0                      // fp32  global gradient norm of the last guarded step
+#define ADAM_CTRL_COEF 1                      // fp32  min(1, max_norm / (norm + 1e-6))
+#define ADAM_CTRL_SKIP 2                      // int32 1: the last step was skipped (non-finite norm)
+#define ADAM_CTRL_SKIPPED 3                   // int32 running count of skipped steps
+
+// index of the last tensor whose block_start <= block
+__device__ __forceinline__ int adam_find_tensor(const SisrAdamDesc* __restrict__ table, int n, int64_t block) {
+    int lo = 0, hi = n - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].block_start <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
+        if (table[mid].block_start <= block) lo = mid; else hi = mid - 1;
     }
-    const SisrAdamDesc t = table[lo];
-    const int64_t base = ((int64_t)blockIdx.x - t.block_start) * ADAM_CHUNK;
+    return lo;
+}
+
+// the update of one workgroup's ADAM_CHUNK elements of tensor t, starting at element `base`.  CLIP: g is multiplied by coef
+// before the weight decay is added (the gradient tensor itself is only read)
+template <bool CLIP>
+__device__ __forceinline__ void adam_update_block(const SisrAdamDesc& t, int64_t base, float coef, float step_size, float omb1,
+                                                  float beta2, float omb2, float eps, float wd, float inv_sqrt_bc2) {
     if ((t.numel & 3) == 0) {
         const int64_t n4 = t.numel >> 2;
 #pragma unroll
@@ -29,7 +53,7 @@ __global__ void __launch_bounds__(SISR_BLOCK) adam_step_kernel(const SisrAdamDes
                 f32x4 m = reinterpret_cast<const f32x4*>(t.m)[i], v = reinterpret_cast<const f32x4*>(t.v)[i];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float gg = g[j] + wd * p[j];
+                    const float gg = (CLIP ? g[j] * coef : g[j]) + wd * p[j];
                     m[j] = m[j] + (gg - m[j]) * omb1;
                     v[j] = v[j] * beta2 + omb2 * gg * gg;
                     p[j] -= step_size * (m[j] / (sqrtf(v[j]) * inv_sqrt_bc2 + eps));
@@ -43,7 +67,7 @@ __global__ void __launch_bounds__(SISR_BLOCK) adam_step_kernel(const SisrAdamDes
         for (int k = 0; k < 16; ++k) {
             const int64_t i = base + k * SISR_BLOCK + threadIdx.x;
             if (i < t.numel) {
-                const float gg = t.g[i] + wd * t.p[i];
+                const float gg = (CLIP ? t.g[i] * coef : t.g[i]) + wd * t.p[i];
                 const float m = t.m[i] + (gg - t.m[i]) * omb1;
                 const float v = t.v[i] * beta2 + omb2 * gg * gg;
                 t.m[i] = m; t.v[i] = v;
@@ -51,6 +75,112 @@ __global__ void __launch_bounds__(SISR_BLOCK) adam_step_kernel(const SisrAdamDes
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(SISR_BLOCK) adam_step_kernel(const SisrAdamDesc* __restrict__ table, int n, float step_size,
+                                                                float omb1, float beta2, float omb2, float eps, float wd,
+                                                                float inv_sqrt_bc2) {
+    const SisrAdamDesc t = table[adam_find_tensor(table, n, (int64_t)blockIdx.x)];
+    const int64_t base = ((int64_t)blockIdx.x - t.block_start) * ADAM_CHUNK;
+    adam_update_block<false>(t, base, 1.f, step_size, omb1, beta2, omb2, eps, wd, inv_sqrt_bc2);
+}
+
+// ---- device-state family ------------------------------------------------------------------------------------------------
+
+// part[blockIdx.x] = sum of g^2 over the workgroup's chunk, squared and accumulated in double (|g| ~ 1e19 overflows an fp32
+// square; the kernel waits for HBM either way)
+__global__ void __launch_bounds__(SISR_BLOCK) adam_sumsq_kernel(const SisrAdamDesc* __restrict__ table, int n,
+                                                                 double* __restrict__ part) {
+    __shared__ double red[SISR_BLOCK / 64];
+    const SisrAdamDesc t = table[adam_find_tensor(table, n, (int64_t)blockIdx.x)];
+    const int64_t base = ((int64_t)blockIdx.x - t.block_start) * ADAM_CHUNK;
+    double s = 0.0;
+    if ((t.numel & 3) == 0) {
+        const int64_t n4 = t.numel >> 2;
+        f32x4 g[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t i = (base >> 2) + k * SISR_BLOCK + threadIdx.x;
+            g[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (i < n4) g[k] = reinterpret_cast<const f32x4*>(t.g)[i];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s += (double)g[k][j] * (double)g[k][j];
+    } else {
+        for (int k = 0; k < 16; ++k) {
+            const int64_t i = base + k * SISR_BLOCK + threadIdx.x;
+            if (i < t.numel) { const double g = (double)t.g[i]; s += g * g; }
+        }
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = red[0];
+#pragma unroll
+        for (int w = 1; w < SISR_BLOCK / 64; ++w) r += red[w];
+        part[blockIdx.x] = r;
+    }
+}
+
+// One thread per tensor, ceil(n / 256) workgroups.  With partials (n_part > 0) EVERY workgroup adds all of them in the same
+// fixed order in double (thread t takes t, t + 256, ...; pairwise fold through LDS), so each one holds the same norm bits and
+// no workgroup waits for another; workgroup 0 stores the control block when write_ctrl is set.  max_norm < 0: no clipping.
+// Then per tensor: t = *steps[i]; step_size = lr / (1 - beta1^(t+1)) and 1 / sqrt(1 - beta2^(t+1)) in double, rounded to fp32
+// once (the rule of sisr_adam_step); *steps[i] = t + 1.  A skipped step stores neither.
+__global__ void __launch_bounds__(SISR_BLOCK) adam_prepare_kernel(float* const* __restrict__ steps, int n, const void* __restrict__ lr,
+                                                                   int lr_f64, double beta1, double beta2,
+                                                                   const double* __restrict__ part, int64_t n_part, double max_norm,
+                                                                   int skip_nonfinite, int write_ctrl, float* __restrict__ ctrl,
+                                                                   float* __restrict__ consts) {
+    __shared__ double red[SISR_BLOCK];
+    const int tid = threadIdx.x;
+    float norm_f = 0.f, coef = 1.f;
+    int skip = 0;
+    if (n_part > 0) {
+        double s = 0.0;
+        for (int64_t i = tid; i < n_part; i += SISR_BLOCK) s += part[i];
+        red[tid] = s;
+        __syncthreads();
+        for (int o = SISR_BLOCK / 2; o > 0; o >>= 1) {
+            if (tid < o) red[tid] += red[tid + o];
+            __syncthreads();
+        }
+        const double norm = sqrt(red[0]);
+        norm_f = (float)norm;
+        if (max_norm >= 0.0) {
+            const double c = max_norm / (norm + 1e-6);          // torch.nn.utils.clip_grad_norm_
+            coef = !(c >= 1.0) ? (float)c : 1.f;                // (a NaN norm stays a NaN coefficient, as torch's clamp leaves it)
+        }
+        skip = skip_nonfinite && !isfinite(norm_f);
+    }
+    if (write_ctrl && blockIdx.x == 0 && tid == 0) {
+        int* ictrl = reinterpret_cast<int*>(ctrl);
+        ctrl[ADAM_CTRL_NORM] = norm_f;
+        ctrl[ADAM_CTRL_COEF] = coef;
+        ictrl[ADAM_CTRL_SKIP] = skip;
+        ictrl[ADAM_CTRL_SKIPPED] += skip;
+    }
+    const int i = blockIdx.x * SISR_BLOCK + tid;
+    if (i < n && !skip) {
+        const double t1 = (double)steps[i][0] + 1.0;
+        const double lr_now = lr_f64 ? *reinterpret_cast<const double*>(lr) : (double)*reinterpret_cast<const float*>(lr);
+        consts[2 * i] = (float)(lr_now / (1.0 - pow(beta1, t1)));
+        consts[2 * i + 1] = (float)(1.0 / sqrt(1.0 - pow(beta2, t1)));
+        steps[i][0] = (float)t1;
+    }
+}
+
+__global__ void __launch_bounds__(SISR_BLOCK) adam_step_dev_kernel(const SisrAdamDesc* __restrict__ table, int n,
+                                                                    const float* __restrict__ consts, const float* __restrict__ ctrl,
+                                                                    float omb1, float beta2, float omb2, float eps, float wd) {
+    if (reinterpret_cast<const int*>(ctrl)[ADAM_CTRL_SKIP]) return;          // before any store
+    const int ti = adam_find_tensor(table, n, (int64_t)blockIdx.x);
+    const SisrAdamDesc t = table[ti];
+    const int64_t base = ((int64_t)blockIdx.x - t.block_start) * ADAM_CHUNK;
+    adam_update_block<true>(t, base, ctrl[ADAM_CTRL_COEF], consts[2 * ti], omb1, beta2, omb2, eps, wd, consts[2 * ti + 1]);
 }
 
 extern "C" int64_t sisr_adam_blocks(int64_t numel) { return numel <= 0 ? 0 : (numel + ADAM_CHUNK - 1) / ADAM_CHUNK; }
@@ -64,6 +194,43 @@ extern "C" int sisr_adam_step(const SisrAdamDesc* table_dev, int32_t n, int64_t 
     hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)total_blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream),
                        table_dev, n, (float)(lr / bias_corr1), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
                        (float)eps, (float)weight_decay, (float)(1.0 / sqrt(bias_corr2)));
+    SISR_CHECK_LAUNCH();
+    return 0;
+}
+
+static inline bool adam_blocks_ok(int64_t total_blocks) { return total_blocks > 0 && total_blocks < (1ll << 31); }
+static inline bool adam_beta_ok(double b) { return b >= 0.0 && b < 1.0; }          // (false for a NaN)
+
+extern "C" int64_t sisr_adam_norm_ws_doubles(int64_t total_blocks) {
+    return adam_blocks_ok(total_blocks) ? total_blocks : (int64_t)SISR_E_BADARG;
+}
+
+extern "C" int sisr_adam_grad_sumsq(const SisrAdamDesc* table_dev, int32_t n, int64_t total_blocks, double* partials, void* stream) {
+    if (!table_dev || n <= 0 || !adam_blocks_ok(total_blocks) || !partials) return SISR_E_BADARG;
+    hipLaunchKernelGGL(adam_sumsq_kernel, dim3((unsigned)total_blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream), table_dev, n,
+                       partials);
+    SISR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sisr_adam_prepare(float* const* steps_dev, int32_t n, const void* lr_dev, int32_t lr_is_f64, double beta1, double beta2,
+                                 const double* partials, int64_t n_partials, double max_norm, int32_t skip_nonfinite,
+                                 int32_t write_ctrl, float* ctrl, float* consts, void* stream) {
+    if (!steps_dev || n <= 0 || !lr_dev || !ctrl || !consts || !adam_beta_ok(beta1) || !adam_beta_ok(beta2)) return SISR_E_BADARG;
+    if (n_partials < 0 || n_partials >= (1ll << 31) || (n_partials > 0 && !partials) || max_norm != max_norm) return SISR_E_BADARG;
+    hipLaunchKernelGGL(adam_prepare_kernel, dim3((unsigned)((n + SISR_BLOCK - 1) / SISR_BLOCK)), dim3(SISR_BLOCK), 0,
+                       sisr_stream(stream), steps_dev, n, lr_dev, lr_is_f64, beta1, beta2, partials, n_partials, max_norm,
+                       skip_nonfinite, write_ctrl, ctrl, consts);
+    SISR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sisr_adam_step_dev(const SisrAdamDesc* table_dev, int32_t n, int64_t total_blocks, const float* consts,
+                                  const float* ctrl, double beta1, double beta2, double eps, double weight_decay, void* stream) {
+    if (!table_dev || n <= 0 || !adam_blocks_ok(total_blocks) || !consts || !ctrl || !adam_beta_ok(beta1) || !adam_beta_ok(beta2))
+        return SISR_E_BADARG;
+    hipLaunchKernelGGL(adam_step_dev_kernel, dim3((unsigned)total_blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream), table_dev, n,
+                       consts, ctrl, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay);
     SISR_CHECK_LAUNCH();
     return 0;
 }

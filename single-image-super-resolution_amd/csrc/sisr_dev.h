@@ -106,6 +106,11 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
 
 // block-wide sum for SISR_BLOCK threads; `scratch` >= 4 floats of LDS; result valid in all threads
 __device__ __forceinline__ float block_sum(float v, float* scratch) {

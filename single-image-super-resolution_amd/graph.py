@@ -2,7 +2,13 @@
 a graph they cost no per-launch host time).  The path's launches are capturable by construction: descriptor tables
 travel through pinned staging buffers that outlive the graph (engine._table_to_device), nothing synchronises with
 the host, and every tensor a step produces lives in the graph's private pool -- so the values `fn` returns are
-static tensors that each replay overwrites.  Optimizer steps stay outside (their scalars change every step).
+static tensors that each replay overwrites.  An optimizer step can be captured too when its scalars live on the device:
+``optim.Adam(capturable=True)`` keeps step counts, learning rate and guards there, so a whole single-GPU SRGAN iteration (G
+forward, D step with its Adam step, G step with its Adam step) is one graph.  The host-state ``optim.Adam`` must stay outside
+(its lr and bias corrections are launch arguments: a captured step would replay those of the capture).  A captured step tells
+the capturing ``GraphedStep`` so (``captures_optimizer``): its replays change parameters without any host call, so every
+replay is followed by ``engine.invalidate_weight_caches()`` -- an eager forward after it never reads a weight image packed
+before the step.  A ``GraphedStep`` that captures no optimizer step behaves as before.
 
 Thin by design: capture / replay themselves are ``torch.cuda.CUDAGraph`` (hipGraph underneath).  What this module
 adds is (a) capture in SEGMENTS -- `fn` may call ``segment_boundary()`` to close the running graph and open the next
@@ -90,6 +96,7 @@ class GraphedStep:
     def __init__(self, fn, warmup=2, between=None):
         global _ACTIVE
         self.between = between
+        self.captures_optimizer = False      # set by a capturable optimizer step that runs inside the capture
         # A segment boundary inside a backward pass is reached on autograd's device worker thread, and HIP (ROCm 7.2)
         # only lets the thread that began a capture end it (hipErrorStreamCaptureWrongThread, also in relaxed mode).
         # Segmented captures therefore issue EVERY capture begin / end on that worker thread (_on_worker); plain
@@ -194,4 +201,7 @@ class GraphedStep:
             g.replay()
             if i < last and self.between is not None:
                 self.between(self.tags[i])
+        if self.captures_optimizer:          # the replay rewrote parameters: packed weight images kept by eager forwards are stale
+            from . import engine as E
+            E.invalidate_weight_caches()
         return self.out
