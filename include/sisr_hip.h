@@ -639,6 +639,33 @@ int sisr_adam_prepare(float *const *steps_dev, int32_t n, const void *lr_dev, in
 int sisr_adam_step_dev(const SisrAdamDesc *table_dev, int32_t n, int64_t total_blocks, const float *consts, const float *ctrl,
                        double beta1, double beta2, double eps, double weight_decay, void *stream);
 
+/* ---- exponential moving average of a network's weights: fused, multi-tensor, capturable -----------
+ * The averaged ("shadow") copy of every parameter and fp32 buffer of a network is updated by one launch; the update count and
+ * the decay schedule live in DEVICE memory, so the launches can sit inside a captured HIP graph behind the capturable Adam step
+ * and still advance on every replay.  Table in DEVICE memory, block mapping of SisrAdamDesc (block_start = running sum of
+ * sisr_adam_blocks(numel), total_blocks = that sum).  mode 0 averages, mode 1 copies (BatchNorm running statistics, spectral-norm
+ * u / v).  Tensors need only 4-byte alignment: 16-byte accesses are used when numel % 4 == 0 and both pointers are 16-byte aligned.
+ *   sisr_ema_prepare   ONE thread, the only code that touches the count: n = *count_dev;
+ *                      d = warmup > 0 ? min(decay, (1 + n) / (warmup + n)) : decay in double; ctrl = { fp32 (float)(1 - d),
+ *                      int32 active = 1 }; *count_dev = n + 1.  With skip_flag_dev (the capturable Adam's skip word) non-zero:
+ *                      active = 0 and nothing else is stored.
+ *   sisr_ema_update    mode 0: ema += omd * (src - ema) (an element with src == ema keeps its bits); mode 1: ema = src, bit-copied;
+ *                      src is only read; no store at all when ctrl's active word is 0.
+ *   sisr_ema_swap      exchanges the bits of ema[i] and src[i], whatever the mode.
+ * Plain vector stores, no atomics, nothing read back by the host.  SISR_E_BADARG before any HIP call for null pointers (the skip
+ * flag may be null), n <= 0, total_blocks outside [1, 2^31), decay outside [0, 1) and warmup < 0 (NaNs included). */
+typedef struct SisrEmaDesc {
+    float *ema;                /* the averaged copy (updated in place)                          */
+    float *src;                /* the live tensor (only sisr_ema_swap writes it)                */
+    int64_t numel;
+    int64_t block_start;
+    int32_t mode;              /* 0: average, 1: copy                                           */
+    int32_t pad;
+} SisrEmaDesc;
+int sisr_ema_prepare(int32_t *count_dev, double decay, double warmup, const int32_t *skip_flag_dev, float *ctrl, void *stream);
+int sisr_ema_update(const SisrEmaDesc *table_dev, int32_t n, int64_t total_blocks, const float *ctrl, void *stream);
+int sisr_ema_swap(const SisrEmaDesc *table_dev, int32_t n, int64_t total_blocks, void *stream);
+
 /* sizeof() of the descriptor structs in declaration order (Conv, Wgrad, Weight, WeightGrad,
  * BnBwd, ConvPlan, DeepPlan, WgradDeepPlan) so a binding can verify its mirror of this header; returns the count. */
 int sisr_struct_sizes(int32_t *out, int32_t cap);

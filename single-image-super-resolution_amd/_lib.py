@@ -101,6 +101,10 @@ class AdamDesc(C.Structure):
     _fields_ = [('p', _f), ('m', _f), ('v', _f), ('g', _f), ('numel', _i64), ('block_start', _i64)]
 
 
+class EmaDesc(C.Structure):
+    _fields_ = [('ema', _f), ('src', _f), ('numel', _i64), ('block_start', _i64), ('mode', _i32), ('pad', _i32)]
+
+
 class BnBwdDesc(C.Structure):
     _fields_ = ([(n, _f) for n in ('dy', 'x', 'scale', 'shift', 'mean', 'invstd', 'gamma', 'work',
                                    'qa', 'qb', 'qd', 'dgamma', 'dbeta', 'dslope')] +
@@ -169,6 +173,9 @@ _SIGS = {
     'sisr_adam_grad_sumsq': [_f, _i32, _i64, _f, _f],
     'sisr_adam_prepare': [_f, _i32, _f, _i32, C.c_double, C.c_double, _f, _i64, C.c_double, _i32, _i32, _f, _f, _f],
     'sisr_adam_step_dev': [_f, _i32, _i64, _f, _f] + [C.c_double] * 4 + [_f],
+    'sisr_ema_prepare': [_f, C.c_double, C.c_double, _f, _f, _f],
+    'sisr_ema_update': [_f, _i32, _i64, _f, _f],
+    'sisr_ema_swap': [_f, _i32, _i64, _f],
     'sisr_nhwc_to_nchw': [_f, _f, _f, _f, _f32, _f, _i64, _i32, _i32, _i32, _i32, _i32, _f],
     'sisr_nchw_to_nhwc': [_f, _i64, _f, _i32, _i32, _i32, _i32, _i32, _f],
     'sisr_nchw_grad_to_nhwc4': [_f, _f, _f, _i32, _i32, _i32, _i32, _i32, _f],

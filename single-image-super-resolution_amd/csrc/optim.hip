@@ -16,6 +16,11 @@
 //       adam_step_dev_kernel the update with those per-tensor constants, g scaled by the clip coefficient, nothing stored
 //                            when the skip flag is set.
 // No atomics, every sum in a fixed order: the same inputs give the same bits.
+//
+// The weight EMA is the same kind of kernel on the same block mapping, over SisrEmaDesc tables:
+//       ema_prepare_kernel   one thread: update count -> decay of this update -> control block { 1 - d, active }, count + 1;
+//       ema_update_kernel    shadow += (1 - d) * (live - shadow) (mode 0) or shadow = live (mode 1), nothing when not active;
+//       ema_swap_kernel      exchanges the bits of shadow and live tensor.
 #include "sisr_dev.h"
 
 #include <cmath>
@@ -28,8 +33,9 @@
 #define ADAM_CTRL_SKIP 2                      // int32 1: the last step was skipped (non-finite norm)
 #define ADAM_CTRL_SKIPPED 3                   // int32 running count of skipped steps
 
-// index of the last tensor whose block_start <= block
-__device__ __forceinline__ int adam_find_tensor(const SisrAdamDesc* __restrict__ table, int n, int64_t block) {
+// index of the last tensor whose block_start <= block (SisrAdamDesc or SisrEmaDesc: the same block mapping)
+template <typename Desc>
+__device__ __forceinline__ int adam_find_tensor(const Desc* __restrict__ table, int n, int64_t block) {
     int lo = 0, hi = n - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -231,6 +237,141 @@ extern "C" int sisr_adam_step_dev(const SisrAdamDesc* table_dev, int32_t n, int6
         return SISR_E_BADARG;
     hipLaunchKernelGGL(adam_step_dev_kernel, dim3((unsigned)total_blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream), table_dev, n,
                        consts, ctrl, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay);
+    SISR_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- weight EMA ------------------------------------------------------------------------------------
+
+// control block of the EMA launches: two 32-bit words, written only by ema_prepare_kernel
+#define EMA_CTRL_OMD 0                        // fp32  1 - decay of this update
+#define EMA_CTRL_ACTIVE 1                     // int32 0: the followed optimizer skipped its step, the update stores nothing
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// 16-byte accesses need every element of both tensors on a 16-byte line: a parameter may be a view at an odd element offset
+__device__ __forceinline__ bool ema_vec_ok(const SisrEmaDesc& t) {
+    return (t.numel & 3) == 0 && ((reinterpret_cast<uintptr_t>(t.ema) | reinterpret_cast<uintptr_t>(t.src)) & 15) == 0;
+}
+
+// an element whose live value equals its average keeps its bits (e + omd * 0 would turn a -0 into +0)
+__device__ __forceinline__ float ema_value(float e, float p, float omd) {
+    const float d = p - e;
+    return d == 0.f ? e : e + omd * d;
+}
+
+// One thread; the only code that reads or writes the update count.  d = min(decay, (1 + n) / (warmup + n)) (warmup > 0) in
+// double, 1 - d rounded to fp32 once.  With a skip flag that is set: active = 0, count and 1 - d stay.
+__global__ void __launch_bounds__(64) ema_prepare_kernel(int* __restrict__ count, double decay, double warmup,
+                                                          const int* __restrict__ skip_flag, float* __restrict__ ctrl) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    int* ictrl = reinterpret_cast<int*>(ctrl);
+    if (skip_flag && *skip_flag != 0) { ictrl[EMA_CTRL_ACTIVE] = 0; return; }
+    const int n = *count;
+    double d = decay;
+    if (warmup > 0.0) d = fmin(decay, (1.0 + (double)n) / (warmup + (double)n));
+    ctrl[EMA_CTRL_OMD] = (float)(1.0 - d);
+    ictrl[EMA_CTRL_ACTIVE] = 1;
+    *count = n + 1;
+}
+
+// one workgroup per ADAM_CHUNK elements; all loads of a thread are issued before its first store
+__global__ void __launch_bounds__(SISR_BLOCK) ema_update_kernel(const SisrEmaDesc* __restrict__ table, int n,
+                                                                 const float* __restrict__ ctrl) {
+    if (reinterpret_cast<const int*>(ctrl)[EMA_CTRL_ACTIVE] == 0) return;          // before any store
+    const float omd = ctrl[EMA_CTRL_OMD];
+    const SisrEmaDesc t = table[adam_find_tensor(table, n, (int64_t)blockIdx.x)];
+    const int64_t base = ((int64_t)blockIdx.x - t.block_start) * ADAM_CHUNK;
+    if (ema_vec_ok(t)) {
+        const int64_t n4 = t.numel >> 2;
+        const int64_t i0 = (base >> 2) + threadIdx.x;
+        if (t.mode == 0) {
+            f32x4 e[4], p[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = i0 + k * SISR_BLOCK;
+                if (i < n4) { e[k] = reinterpret_cast<const f32x4*>(t.ema)[i]; p[k] = reinterpret_cast<const f32x4*>(t.src)[i]; }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = i0 + k * SISR_BLOCK;
+                if (i < n4) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) e[k][j] = ema_value(e[k][j], p[k][j], omd);
+                    reinterpret_cast<f32x4*>(t.ema)[i] = e[k];
+                }
+            }
+        } else {
+            u32x4 p[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = i0 + k * SISR_BLOCK;
+                if (i < n4) p[k] = reinterpret_cast<const u32x4*>(t.src)[i];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t i = i0 + k * SISR_BLOCK;
+                if (i < n4) reinterpret_cast<u32x4*>(t.ema)[i] = p[k];
+            }
+        }
+    } else if (t.mode == 0) {
+        for (int k = 0; k < 16; ++k) {
+            const int64_t i = base + k * SISR_BLOCK + threadIdx.x;
+            if (i < t.numel) t.ema[i] = ema_value(t.ema[i], t.src[i], omd);
+        }
+    } else {
+        for (int k = 0; k < 16; ++k) {
+            const int64_t i = base + k * SISR_BLOCK + threadIdx.x;
+            if (i < t.numel) reinterpret_cast<unsigned*>(t.ema)[i] = reinterpret_cast<const unsigned*>(t.src)[i];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(SISR_BLOCK) ema_swap_kernel(const SisrEmaDesc* __restrict__ table, int n) {
+    const SisrEmaDesc t = table[adam_find_tensor(table, n, (int64_t)blockIdx.x)];
+    const int64_t base = ((int64_t)blockIdx.x - t.block_start) * ADAM_CHUNK;
+    if (ema_vec_ok(t)) {
+        const int64_t n4 = t.numel >> 2;
+        const int64_t i0 = (base >> 2) + threadIdx.x;
+        u32x4 e[4], p[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t i = i0 + k * SISR_BLOCK;
+            if (i < n4) { e[k] = reinterpret_cast<const u32x4*>(t.ema)[i]; p[k] = reinterpret_cast<const u32x4*>(t.src)[i]; }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t i = i0 + k * SISR_BLOCK;
+            if (i < n4) { reinterpret_cast<u32x4*>(t.ema)[i] = p[k]; reinterpret_cast<u32x4*>(t.src)[i] = e[k]; }
+        }
+    } else {
+        unsigned* ema = reinterpret_cast<unsigned*>(t.ema);
+        unsigned* src = reinterpret_cast<unsigned*>(t.src);
+        for (int k = 0; k < 16; ++k) {
+            const int64_t i = base + k * SISR_BLOCK + threadIdx.x;
+            if (i < t.numel) { const unsigned e = ema[i], p = src[i]; ema[i] = p; src[i] = e; }
+        }
+    }
+}
+
+extern "C" int sisr_ema_prepare(int32_t* count_dev, double decay, double warmup, const int32_t* skip_flag_dev, float* ctrl,
+                                void* stream) {
+    if (!count_dev || !ctrl || !adam_beta_ok(decay) || !(warmup >= 0.0)) return SISR_E_BADARG;          // (false for a NaN)
+    hipLaunchKernelGGL(ema_prepare_kernel, dim3(1), dim3(64), 0, sisr_stream(stream), count_dev, decay, warmup, skip_flag_dev, ctrl);
+    SISR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sisr_ema_update(const SisrEmaDesc* table_dev, int32_t n, int64_t total_blocks, const float* ctrl, void* stream) {
+    if (!table_dev || n <= 0 || !adam_blocks_ok(total_blocks) || !ctrl) return SISR_E_BADARG;
+    hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)total_blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream), table_dev, n, ctrl);
+    SISR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sisr_ema_swap(const SisrEmaDesc* table_dev, int32_t n, int64_t total_blocks, void* stream) {
+    if (!table_dev || n <= 0 || !adam_blocks_ok(total_blocks)) return SISR_E_BADARG;
+    hipLaunchKernelGGL(ema_swap_kernel, dim3((unsigned)total_blocks), dim3(SISR_BLOCK), 0, sisr_stream(stream), table_dev, n);
     SISR_CHECK_LAUNCH();
     return 0;
 }

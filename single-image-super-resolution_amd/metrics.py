@@ -13,6 +13,8 @@ PSNR = 10 log10(data_range^2 / mse), +inf for equal images; SSIM is Wang et al.'
 (sigma 1.5), "valid" window positions only, C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2, averaged over planes and
 positions.  ``data_range`` defaults to 2.0: the project's images are normalised to [-1, 1].
 """
+import contextlib
+
 import torch
 
 from . import _lib as L
@@ -85,23 +87,28 @@ def psnr_ssim(a, b, data_range=2.0, crop_border=0, luma=False):
     return _run(a, b, data_range, crop_border, luma, True, True)
 
 
-def evaluate_generator(net_g, img_hr, image_size_lr, crop_border=None, luma=False):
+def evaluate_generator(net_g, img_hr, image_size_lr, crop_border=None, luma=False, ema=None):
     """One validation pass: ``lr_from_hr(img_hr)`` -> ``net_g`` in eval mode under ``no_grad`` -> ``psnr_ssim(sr, img_hr)``.
 
     Eval mode means running-statistics BatchNorm and no spectral-norm power iteration, so -- unlike calling the net in train
     mode, as the reference's ``save_curr_vis`` does -- the pass leaves every buffer of ``net_g`` as it was (BatchNorm running
     statistics, ``num_batches_tracked``, spectral-norm ``u`` / ``v``).  The training flag of every submodule is restored
     afterwards, also when the pass raises.  ``crop_border=None`` crops by the scale factor (the SR convention).
+    ``ema`` (an ``ema.WeightEMA`` over ``net_g``): the forward runs inside ``ema.applied()`` -- the AVERAGED weights are scored
+    and the live ones are back in place, bit for bit, afterwards.
     Returns ``dict(psnr=Tensor[N], ssim=Tensor[N])``."""
+    if ema is not None and ema.module is not net_g:
+        raise ValueError('evaluate_generator: ema averages another module than net_g')
     modes = [(m, m.training) for m in net_g.modules()]
-    try:
-        net_g.eval()
-        with torch.no_grad():
-            lr = lr_from_hr(img_hr, image_size_lr)
-            sr = net_g(lr)
-    finally:
-        for m, was in modes:
-            m.training = was
+    with contextlib.nullcontext() if ema is None else ema.applied():
+        try:
+            net_g.eval()
+            with torch.no_grad():
+                lr = lr_from_hr(img_hr, image_size_lr)
+                sr = net_g(lr)
+        finally:
+            for m, was in modes:
+                m.training = was
     if sr.shape != img_hr.shape:
         raise ValueError('evaluate_generator: the generator maps %s to %s, the HR batch is %s'
                          % (tuple(lr.shape), tuple(sr.shape), tuple(img_hr.shape)))

@@ -131,7 +131,7 @@ class Adam(torch.optim.Adam):
         self._dev = {
             'index': {p: i for i, p in enumerate(params)},
             'steps': torch.zeros(len(params), dtype=torch.float32, device=device),
-            'ctrl': ctrl, 'norm': ctrl[0], 'skipped': ctrl.view(torch.int32)[3],
+            'ctrl': ctrl, 'norm': ctrl[0], 'skip': ctrl.view(torch.int32)[2], 'skipped': ctrl.view(torch.int32)[3],
             'consts': [torch.zeros(2 * len(g['params']), dtype=torch.float32, device=device) for g in self.param_groups],
             'partials': torch.zeros(max(1, L.check_count(lib.sisr_adam_norm_ws_doubles(max(1, blocks)), 'sisr_adam_norm_ws_doubles')),
                                     dtype=torch.float64, device=device),
@@ -177,9 +177,15 @@ class Adam(torch.optim.Adam):
         """0-dim int32 device tensor: steps skipped so far because their gradient norm was not finite"""
         return self._readout('skipped')
 
+    @property
+    def skip_flag(self):
+        """0-dim int32 device tensor: 1 while the LAST step was skipped (non-finite norm under ``skip_nonfinite``), else 0 -- the
+        word the step kernel itself tests; a kernel that must follow the optimizer's decision (ema.WeightEMA(follow=...)) reads it"""
+        return self._readout('skip')
+
     def _readout(self, key):
         if not self._capturable:
-            raise RuntimeError('fused Adam: grad_norm / skipped_steps belong to capturable=True')
+            raise RuntimeError('fused Adam: grad_norm / skipped_steps / skip_flag belong to capturable=True')
         if self._dev is None:
             self._allocate(self.param_groups[0]['params'][0].device)
         return self._dev[key]
