@@ -256,4 +256,5 @@ class GradReducer:
             flat, views = ent
             torch._foreach_copy_(views, [g.reshape(-1) for g in small])
             self._allreduce_mean_(flat)
-            torch._foreach_copy_([g.reshape(-1) for g in small], views)
+            # write back THROUGH each gradient's own strides: g.reshape(-1) of a non-contiguous g is a copy, not a view
+            torch._foreach_copy_(small, [v.view(g.shape) for v, g in zip(views, small)])

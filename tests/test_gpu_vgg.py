@@ -54,6 +54,29 @@ def test_masked_vgg_full_width_vs_oracle():
         assert rel_err(x.grad.cpu(), xr.grad) < TOL
 
 
+def test_masked_vgg_odd_maps_vs_oracle():
+    """a 30 x 22 input: the pooled maps are 15 x 11, 7 x 5, 3 x 2 and 1 x 1, so three of the four poolings see an odd map -- the
+    forward pass drops its last row / column and the backward pass must hand that row / column an exactly-zero gradient (the edge
+    kernel of sisr_maxpool2_relu_bwd) at three depths.  Widths / 8 (seeded weights), fp32 build, forward and input gradient."""
+    from oracle import models as om
+    mce = pkg('model_content_extractor')
+    x0 = torch.rand(2, 3, 30, 22, generator=torch.Generator().manual_seed(25)) * 2 - 1
+    for mask in (0b00010, 0b10000, 0b01111):
+        net = mce.MaskedVGG(mask, width_div=8, pretrained=False)
+        state = {k: v.detach().clone() for k, v in net.state_dict().items()}      # the oracle reads the widths off the weights
+        net = net.cuda()
+        x = x0.cuda().requires_grad_(True)
+        f = net(x)
+        xr = x0.clone().requires_grad_(True)
+        fr = om.masked_vgg_forward(state, xr, mask)
+        assert tuple(f.shape) == tuple(fr.shape)
+        assert rel_err(f.detach().cpu(), fr.detach()) < TOL, mask
+        r = torch.rand(fr.shape, generator=torch.Generator().manual_seed(27)) - 0.5
+        (fr * r).sum().backward()
+        (f * r.cuda()).sum().backward()
+        assert rel_err(x.grad.cpu(), xr.grad) < TOL, mask
+
+
 @pytest.mark.parametrize('precision,tol', [('fp32', TOL), ('bf16', 3e-2)])
 @pytest.mark.parametrize('mask', [0b00010, 0b10000])
 def test_masked_vgg_full_size_taps_vs_oracle(mask, precision, tol):
