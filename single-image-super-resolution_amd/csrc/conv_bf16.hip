@@ -589,11 +589,7 @@ extern "C" int sisr_conv2d_plan_bf16(SisrConvDesc* d) {
         cand_lds[mi] = best_lds;
         cand_cost[mi] = (double)((blocks + 511) / 512) * BM * (mi == 0 ? 1.0 : 1.05);
     }
-    int pick = cand_cost[1] < cand_cost[0] ? 1 : 0;
-    if (const char* e = getenv("SISR_BF16_MSUB")) {          // A/B override of the workgroup height
-        const int want = atoi(e) == 2 ? 0 : 1;
-        if (cand_cost[want] < 1e29) pick = want;
-    }
+    const int pick = cand_cost[1] < cand_cost[0] ? 1 : 0;
     if (cand_cost[pick] > 1e29) return SISR_E_TOOBIG;
     p = cand[pick];
     p.n_tiles = p.tiles_y * p.tiles_x * p.n_groups;
@@ -622,11 +618,31 @@ static int launch_conv_bf16(const SisrConvDesc* d, hipStream_t st) {
     return d->y_bf16 ? launch_conv_bf16_t<MSUB, NSUB, TAG, false, true>(d, st) : launch_conv_bf16_t<MSUB, NSUB, TAG, false, false>(d, st);
 }
 
+// the kernel family sisr_conv2d_bf16 hands `d` to (the only place that orders these families)
+static SisrRoute conv_bf16_route(const SisrConvDesc* d) {
+    if (d->deep.enabled && d->wdeep) return SISR_ROUTE_DEEP;                    // planned for conv_deep.hip: runs there or is refused
+    if (sisr_conv2d_toimage_eligible(d)) return SISR_ROUTE_TOIMAGE;             // the generator's last conv (64 -> 3)
+    // the generator's trunk geometry: persistent weights-in-registers kernel
+    return sisr_conv2d_trunk_eligible(d) ? SISR_ROUTE_TRUNK : SISR_ROUTE_GENERIC;
+}
+
+// rows of stat_part / cnt_part (or bnb_part) a launch of this descriptor writes: the trunk kernel writes one per
+// workgroup, the generic kernels (and the last conv's, which has neither epilogue) one per tile (plan.n_tiles)
+extern "C" int sisr_conv2d_bf16_parts(const SisrConvDesc* d) {
+    if (!d) return SISR_E_BADARG;
+    switch (conv_bf16_route(d)) {
+        case SISR_ROUTE_DEEP: return sisr_conv2d_deep_parts(d);
+        case SISR_ROUTE_TRUNK: return sisr_conv2d_trunk_grid(d);
+        default: return d->plan.n_tiles;
+    }
+}
+
 extern "C" int sisr_conv2d_bf16(const SisrConvDesc* d, void* stream) {
     if (!d || !d->x1 || !d->y) return SISR_E_BADARG;
+    const SisrRoute route = conv_bf16_route(d);
     // the split-K implicit-GEMM family (conv_deep.hip): a descriptor planned for it carries that family's weight image and
     // NOT the generic one, so it either runs there or is refused -- never silently on another kernel
-    if (d->deep.enabled && d->wdeep) {
+    if (route == SISR_ROUTE_DEEP) {
         if (!sisr_conv2d_deep_eligible(d)) return SISR_E_UNSUPPORTED;
         return sisr_conv2d_deep_launch(d, sisr_stream(stream));
     }
@@ -648,11 +664,8 @@ extern "C" int sisr_conv2d_bf16(const SisrConvDesc* d, void* stream) {
     if (p.CK != BF_CK || p.PS != BF_PS || p.n_tiles <= 0 || p.lds_bytes <= 0 || p.lds_bytes > 160 * 1024)
         return SISR_E_BADARG;
     hipStream_t st = sisr_stream(stream);
-    if (sisr_conv2d_toimage_eligible(d)) return sisr_conv2d_toimage_launch(d, st);      // the generator's last conv (64 -> 3)
-    if (sisr_conv2d_trunk_eligible(d)) {                // the generator's trunk geometry: persistent weights-in-registers kernel
-        if (d->stat_part && !d->cnt_part) return SISR_E_BADARG;
-        return sisr_conv2d_trunk_launch(d, st);
-    }
+    if (route == SISR_ROUTE_TOIMAGE) return sisr_conv2d_toimage_launch(d, st);
+    if (route == SISR_ROUTE_TRUNK) return sisr_conv2d_trunk_launch(d, st);
     if (d->pro_mode == SISR_PRO_RES_AFFINE) return SISR_E_UNSUPPORTED;      // persistent trunk kernels only
     // TAG only names the symbol (same code): 1 = the generator's trunk geometry in its forward role (BatchNorm
     // statistics epilogue) -- the launch bench.py's roofline probe times --, 2 = the trunk geometry in its other

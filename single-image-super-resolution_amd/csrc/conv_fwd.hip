@@ -409,6 +409,28 @@ static int launch_conv(const SisrConvDesc* d, hipStream_t st) {
     return sisr_launch<conv_mfma_f32_kernel<MSUB, NSUB, TAG>>(grid, dim3(SISR_BLOCK), d->plan.lds_bytes, SISR_LDS_BASE_DEFAULT, st, *d);
 }
 
+// the kernel family sisr_conv2d_f32 hands `d` to (the only place that orders these families)
+static SisrRoute conv_f32_route(const SisrConvDesc* d) {
+    if (sisr_conv2d_trunk_f32_eligible(d)) return SISR_ROUTE_TRUNK;
+    if (sisr_conv2d_thin_eligible(d)) return SISR_ROUTE_THIN;                   // bf16 build: 9x9 over a 3-channel image
+    return sisr_conv2d_toimage_f32_eligible(d) ? SISR_ROUTE_TOIMAGE : SISR_ROUTE_GENERIC;      // the generator's last conv (64 -> 3)
+}
+
+// rows of stat_part / cnt_part a launch of this descriptor writes: one per pixel-tile stream on the persistent kernel, one per
+// tile on the generic one (the thin and last-conv kernels have no statistics epilogue; they answer as the generic kernel)
+extern "C" int sisr_conv2d_f32_parts(const SisrConvDesc* d) {
+    if (!d) return SISR_E_BADARG;
+    return conv_f32_route(d) == SISR_ROUTE_TRUNK ? sisr_conv2d_trunk_f32_streams(d) : d->plan.n_tiles;
+}
+
+// rows of bnb_part (one per workgroup) a launch of this descriptor writes: the persistent kernel in its data-gradient role (2) has
+// that epilogue; 0: the kernel it goes to does not take it
+extern "C" int sisr_conv2d_f32_bnb_parts(const SisrConvDesc* d) {
+    if (!d) return SISR_E_BADARG;
+    const bool takes = conv_f32_route(d) == SISR_ROUTE_TRUNK && sisr_conv2d_trunk_f32_eligible(d) == 2;
+    return takes ? 2 * sisr_conv2d_trunk_f32_streams(d) : 0;
+}
+
 extern "C" int sisr_conv2d_f32(const SisrConvDesc* d, void* stream) {
     // fused BatchNorm-backward partials: bf16 kernels and the persistent fp32 trunk kernel only
     if (d && d->bnb_part && sisr_conv2d_trunk_f32_eligible(d) != 2) return SISR_E_UNSUPPORTED;
@@ -421,9 +443,10 @@ extern "C" int sisr_conv2d_f32(const SisrConvDesc* d, void* stream) {
     const SisrConvPlan& p = d->plan;
     if (p.n_tiles <= 0 || p.lds_bytes <= 0 || p.lds_bytes > 160 * 1024) return SISR_E_BADARG;
     hipStream_t st = sisr_stream(stream);
-    if (sisr_conv2d_trunk_f32_eligible(d)) return sisr_conv2d_trunk_f32_launch(d, st);
-    if (sisr_conv2d_thin_eligible(d)) return sisr_conv2d_thin_launch(d, st);    // bf16 build: 9x9 over a 3-channel image
-    if (sisr_conv2d_toimage_f32_eligible(d)) return sisr_conv2d_toimage_launch(d, st);     // the generator's last conv (64 -> 3)
+    const SisrRoute route = conv_f32_route(d);
+    if (route == SISR_ROUTE_TRUNK) return sisr_conv2d_trunk_f32_launch(d, st);
+    if (route == SISR_ROUTE_THIN) return sisr_conv2d_thin_launch(d, st);
+    if (route == SISR_ROUTE_TOIMAGE) return sisr_conv2d_toimage_launch(d, st);
     if (d->pro_mode == SISR_PRO_RES_AFFINE) return SISR_E_UNSUPPORTED;      // persistent trunk kernels only
     const bool trunk = d->Cin == 64 && d->Cout == 64 && d->KH == 3 && d->KW == 3 && d->stride == 1;
     if (p.msub == 2 && p.nsub == 2) return trunk ? launch_conv<2, 2, 1>(d, st) : launch_conv<2, 2, 0>(d, st);

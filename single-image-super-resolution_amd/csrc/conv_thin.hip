@@ -215,7 +215,6 @@ extern "C" int sisr_conv2d_thin_eligible(const SisrConvDesc* d) {
 }
 
 int sisr_conv2d_thin_launch(const SisrConvDesc* d, hipStream_t st) {
-    const int cus = sisr_cu_slots();
     const bool tanhb = d->pro_mode == SISR_PRO_TANH_BWD;
     if (tanhb && !d->x2) return SISR_E_BADARG;
     ThinArgs a;
@@ -224,10 +223,7 @@ int sisr_conv2d_thin_launch(const SisrConvDesc* d, hipStream_t st) {
     a.tiles_x = d->W / TN_T;
     a.per_img = a.tiles_x * (d->H / TN_T);
     a.total = a.per_img * d->N;
-    // equal shares: every workgroup walks ceil(total / cus) tiles
-    const int rounds = (a.total + cus - 1) / cus;
-    a.rounds = rounds;
-    const dim3 grid((a.total + rounds - 1) / rounds), block(256);
+    const dim3 grid(sisr_equal_shares(a.total, sisr_cu_slots(), &a.rounds)), block(256);     // every workgroup walks a.rounds tiles
     if (d->KH == 9) {
         if (tanhb) hipLaunchKernelGGL((conv_thin_kernel<9, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((conv_thin_kernel<9, false>), grid, block, 0, st, a);

@@ -21,9 +21,7 @@
 // output, H % 8 == 0, W % 16 == 0, plain output mode.  Everything else runs on the generic kernels.
 #include "sisr_dev.h"
 
-#include <algorithm>
 #include <type_traits>
-#include <cstdlib>
 
 #include "sisr_bf16_stage.h"
 #include "sisr_instr.h"
@@ -803,56 +801,22 @@ __global__ void __launch_bounds__(TK_THREADS, 2) conv_trunk_bwd_kernel(const Tru
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-static int trunk_groups(const SisrConvDesc* d) { return d->Cout == 256 ? 4 : 1; }
-static int trunk_grid(const SisrConvDesc* d) {
-    const int total = d->N * (d->H / TK_TH) * (d->W / TK_TW);
-    const int cus = sisr_cu_slots();
-    int n_cu = cus;
-    // equal shares: ceil(total / rounds) workgroups, rounds = ceil(total / (CUs x workgroups per CU))
-    int per_cu = 1;
-    if (const char* e = getenv("SISR_TRUNK_WG_PER_CU")) per_cu = std::max(1, std::min(2, atoi(e)));
-    n_cu *= per_cu;
-    const int G = trunk_groups(d);                 // cout groups: each tile stream is served by G workgroups
-    n_cu = std::max(1, n_cu / G);
-    const int rounds = (total + n_cu - 1) / n_cu;
-    return G * ((total + rounds - 1) / rounds);
+#include "sisr_trunk_host.h"
+static const SisrTrunkKind TK_KIND = {TK_TH, TK_TW, true, 128};
+
+// workgroups of a launch = rows of stat_part / cnt_part (or bnb_part) it writes: G cout groups (4 for the upscale conv) serve each
+// tile stream
+int sisr_conv2d_trunk_grid(const SisrConvDesc* d) {
+    const int G = d->Cout == 256 ? 4 : 1;
+    return G * sisr_equal_shares(d->N * (d->H / TK_TH) * (d->W / TK_TW), sisr_cu_slots() / G);
 }
 
-// 1 when this descriptor (geometry + storage flags + fusions requested) can run on the trunk kernel
+// this descriptor (geometry + storage flags + fusions requested) can run on the trunk kernel: 1 forward role, 2 data-gradient role
 extern "C" int sisr_conv2d_trunk_eligible(const SisrConvDesc* d) {
     if (!d || sisr_switch_off("SISR_TRUNK")) return 0;         // A/B switch: SISR_TRUNK=0 keeps the generic kernel
-    if (d->Cin != 64 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_y != 1 || d->pad_x != 1) return 0;
-    // Cout = 64 (trunk), or 256 stored through PixelShuffle(2) -- the upscale conv, forward role without statistics
-    const bool up_off = sisr_switch_off("SISR_TRUNK_UP");      // A/B switch for the upscale conv alone
-    const bool up = !up_off && d->Cout == 256 && d->y_mode == SISR_Y_NHWC_SHUFFLE2 && d->plan.CoutPad == 256 && !d->stat_part && !d->res &&
-                    !d->bnb_part && d->pro_mode != SISR_PRO_RES_AFFINE && !d->fin_stat &&
-                    (d->pro_mode == SISR_PRO_NONE || d->pro_mode == SISR_PRO_ACT || d->pro_mode == SISR_PRO_AFFINE_ACT);
-    if (!up && (d->Cout != 64 || d->y_mode != SISR_Y_NHWC)) return 0;
-    if (d->x_mode != SISR_X_NHWC || !d->x_bf16 || !d->y_bf16) return 0;
-    if (d->Ho != d->H || d->Wo != d->W || (d->H % TK_TH) || (d->W % TK_TW)) return 0;
-    if (!up && (d->y_sy != 1 || d->y_sx != 1 || d->y_oy || d->y_ox || d->y_H != d->Ho || d->y_W != d->Wo)) return 0;
-    if (up && (int64_t)d->N * d->H * d->W * 512 >= (1ll << 31)) return 0;
-    if (d->epi_act != SISR_EPI_NONE) return 0;
-    if ((int64_t)d->N * d->H * d->W * 128 >= (1ll << 31)) return 0;
-    if (d->N * (d->H / TK_TH) * (d->W / TK_TW) >= 65536) return 0;
-    const bool fwd_pro = d->pro_mode == SISR_PRO_NONE || d->pro_mode == SISR_PRO_ACT || d->pro_mode == SISR_PRO_AFFINE_ACT ||
-                         (d->pro_mode == SISR_PRO_RES_AFFINE && d->x2 && d->x_out && ((d->pa && d->pd) || d->fin_stat));
-    if (d->fin_stat && !((d->pro_mode == SISR_PRO_AFFINE_ACT || d->pro_mode == SISR_PRO_RES_AFFINE) && d->fin_cnt && d->fin_gamma &&
-                         d->fin_beta && d->fin_rm && d->fin_rv && d->fin_k && d->fin_rows > 0))
-        return 0;
-    if (fwd_pro && !d->res && !d->bnb_part) return 1;           // forward role
-    const bool bwd_pro = d->pro_mode == SISR_PRO_BNBWD || d->pro_mode == SISR_PRO_BNACT_BWD;
-    if (bwd_pro && !d->stat_part && !d->bias && (!d->res || d->res_bf16) && (!d->bnb_part || d->bnbx_bf16)) return 2;   // data-gradient role
-    return 0;
-}
-
-// rows of stat_part / cnt_part (or bnb_part) a launch of this descriptor writes: the trunk kernel writes one per
-// workgroup, the generic kernels one per tile (plan.n_tiles)
-extern "C" int sisr_conv2d_bf16_parts(const SisrConvDesc* d) {
-    if (!d) return SISR_E_BADARG;
-    if (d->deep.enabled && d->wdeep) return sisr_conv2d_deep_parts(d);
-    if (sisr_conv2d_trunk_eligible(d)) return trunk_grid(d);
-    return d->plan.n_tiles;
+    const int role = sisr_trunk_conv_role(d, TK_KIND);
+    if (role == 2 && !((!d->res || d->res_bf16) && (!d->bnb_part || d->bnbx_bf16))) return 0;
+    return role;
 }
 
 template <int PRO>
@@ -867,24 +831,13 @@ static int launch_trunk_bwd(const TrunkArgs& a, int grid, bool images, hipStream
     return sisr_launch<conv_trunk_bwd_kernel<PRO>>(dim3(grid), dim3(TK_THREADS), lds_bytes, 0, st, a);
 }
 
-// called by sisr_conv2d_bf16 for eligible descriptors
+// called by sisr_conv2d_bf16 for descriptors routed here
 int sisr_conv2d_trunk_launch(const SisrConvDesc* d, hipStream_t st) {
     TrunkArgs a;
-    a.fin.stat = d->fin_stat; a.fin.cnt = d->fin_cnt; a.fin.gamma = d->fin_gamma; a.fin.beta = d->fin_beta;
-    a.fin.rm = d->fin_rm; a.fin.rv = d->fin_rv; a.fin.k = d->fin_k; a.fin.rows = d->fin_rows; a.fin.momentum = d->fin_momentum; a.fin.eps = d->fin_eps;
-    a.x1 = d->x1; a.x2 = d->x2; a.x_out = d->x_out; a.pa = d->pa; a.pb = d->pb; a.pd = d->pd; a.ps = d->ps; a.pt = d->pt;
-    a.slope_p = d->pro_slope_p; a.slope = d->pro_slope;
-    a.wpk = d->wpk; a.bias = d->bias;
-    a.wln = (d->plan.variant & 1) ? static_cast<const char*>(static_cast<const void*>(d->wpk)) + (size_t)(d->Cout == 256 ? 256 : 64) * 1152 : nullptr; a.y = d->y; a.stat_part = d->stat_part; a.cnt_part = d->cnt_part;
-    a.N = d->N; a.H = d->H; a.W = d->W;
-    a.tiles_x = d->W / TK_TW; a.per_img = (d->H / TK_TH) * a.tiles_x; a.total = d->N * a.per_img;
-    a.m_tiles_x = fdiv_magic(a.tiles_x); a.m_per_img = fdiv_magic(a.per_img);
-    a.pro = d->pro_mode;
-    a.glog = d->Cout == 256 ? 2 : 0; a.cout_pad = d->Cout == 256 ? 256 : 64; a.shuffle = d->y_mode == SISR_Y_NHWC_SHUFFLE2 ? 1 : 0;
-    a.res = d->res; a.bnb_x = d->bnb_x; a.bnb_scale = d->bnb_scale; a.bnb_shift = d->bnb_shift; a.bnb_mean = d->bnb_mean;
-    a.bnb_invstd = d->bnb_invstd; a.bnb_slope_p = d->bnb_slope_p; a.bnb_slope = d->bnb_slope; a.bnb_act = d->bnb_act;
-    a.bnb_part = d->bnb_part;
-    const int grid = trunk_grid(d);
+    sisr_trunk_conv_args(a, d, TK_KIND);
+    a.wln = (d->plan.variant & 1) ? static_cast<const char*>(static_cast<const void*>(d->wpk)) + (size_t)a.cout_pad * 1152 : nullptr;
+    a.pro = d->pro_mode; a.glog = d->Cout == 256 ? 2 : 0;
+    const int grid = sisr_conv2d_trunk_grid(d);
     if (d->pro_mode == SISR_PRO_BNBWD) return launch_trunk_bwd<SISR_PRO_BNBWD>(a, grid, d->res || d->bnb_part, st);
     if (d->pro_mode == SISR_PRO_BNACT_BWD) return launch_trunk_bwd<SISR_PRO_BNACT_BWD>(a, grid, d->res || d->bnb_part, st);
     switch (d->pro_mode) {

@@ -26,8 +26,6 @@
 
 typedef unsigned cf_u32x4 __attribute__((ext_vector_type(4)));
 
-#include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 #define CF_TH 8
@@ -578,62 +576,32 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-static int cf_streams(const SisrConvDesc* d) {
-    const int total = d->N * (d->H / CF_TH) * (d->W / CF_TW);
-    const int cus = sisr_cu_slots();
-    const int slots = std::max(1, cus / (d->Cout == 256 ? 8 : 2));     // one workgroup per block of 32 couts and pixel-tile stream
-    const int rounds = (total + slots - 1) / slots;
-    return (total + rounds - 1) / rounds;       // equal shares
+#include "sisr_trunk_host.h"
+static const SisrTrunkKind CF_KIND = {CF_TH, CF_TW, false, 256};
+
+// pixel-tile streams of a launch: one workgroup per stream and block of 32 couts (2 blocks, 8 for the upscale conv)
+int sisr_conv2d_trunk_f32_streams(const SisrConvDesc* d) {
+    return sisr_equal_shares(d->N * (d->H / CF_TH) * (d->W / CF_TW), sisr_cu_slots() / (d->Cout == 256 ? 8 : 2));
 }
 
 // 1: forward role, 2: data-gradient role, 0: not this kernel's geometry / fusions
 extern "C" int sisr_conv2d_trunk_f32_eligible(const SisrConvDesc* d) {
     if (!d || sisr_switch_off("SISR_TRUNK")) return 0;         // A/B switch: SISR_TRUNK=0 keeps the generic kernel
     if (sisr_switch_off("SISR_TRUNK_F32CONV")) return 0;
-    const bool up_off = sisr_switch_off("SISR_TRUNK_UP");      // A/B switch for the upscale conv alone
     // the upscale conv's data gradient: 256 -> 64 over the un-shuffling view of the gradient, activation-backward prologue: four
     // launches of the data-gradient role, one per PixelShuffle phase (see CTrunkF32Args.xsc)
-    if (!up_off && d->Cin == 256 && d->Cout == 64 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_y == 1 && d->pad_x == 1 &&
+    if (!sisr_switch_off("SISR_TRUNK_UP") && d->Cin == 256 && d->Cout == 64 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_y == 1 && d->pad_x == 1 &&
         d->x_mode == SISR_X_NHWC_UNSHUFFLE2 && d->pro_mode == SISR_PRO_ACT_BWD && d->x2 && d->y_mode == SISR_Y_NHWC && !d->x_bf16 && !d->y_bf16 &&
         !d->res_bf16 && d->Ho == d->H && d->Wo == d->W && !(d->H % CF_TH) && !(d->W % CF_TW) && d->y_sy == 1 && d->y_sx == 1 && !d->y_oy && !d->y_ox &&
         d->y_H == d->Ho && d->y_W == d->Wo && d->epi_act == SISR_EPI_NONE && d->plan.CK == 32 && d->plan.PS == CF_PS && d->plan.KROWP == CF_KROWP &&
         d->plan.CoutPad == 64 && d->plan.n_chunk == 8 && (int64_t)d->N * d->H * d->W * 1024 < (1ll << 31) &&
         d->N * (d->H / CF_TH) * (d->W / CF_TW) < 65536 && !d->stat_part && !d->bias && !d->bnb_part && !d->fin_stat)
         return 2;
-    if (d->Cin != 64 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_y != 1 || d->pad_x != 1) return 0;
-    // Cout = 64 (trunk), or 256 stored through PixelShuffle(2) -- the upscale conv, forward role without statistics
-    const bool up = !up_off && d->Cout == 256 && d->y_mode == SISR_Y_NHWC_SHUFFLE2 && d->plan.CoutPad == 256 && !d->stat_part &&
-                    !d->res && !d->bnb_part && !d->fin_stat &&
-                    (d->pro_mode == SISR_PRO_NONE || d->pro_mode == SISR_PRO_ACT || d->pro_mode == SISR_PRO_AFFINE_ACT);
-    if (!up && (d->Cout != 64 || d->y_mode != SISR_Y_NHWC || d->plan.CoutPad != 64)) return 0;
-    if (d->x_mode != SISR_X_NHWC || d->x_bf16 || d->y_bf16 || d->res_bf16) return 0;
-    if (d->Ho != d->H || d->Wo != d->W || (d->H % CF_TH) || (d->W % CF_TW)) return 0;
-    if (!up && (d->y_sy != 1 || d->y_sx != 1 || d->y_oy || d->y_ox || d->y_H != d->Ho || d->y_W != d->Wo)) return 0;
-    if (d->epi_act != SISR_EPI_NONE) return 0;
-    if (d->plan.CK != 32 || d->plan.PS != CF_PS || d->plan.KROWP != CF_KROWP || d->plan.n_chunk != 2) return 0;
-    if ((int64_t)d->N * d->H * d->W * 256 * (up ? 4 : 1) >= (1ll << 31)) return 0;
-    if (d->N * (d->H / CF_TH) * (d->W / CF_TW) >= 65536) return 0;
-    const bool fwd_pro = d->pro_mode == SISR_PRO_NONE || d->pro_mode == SISR_PRO_ACT || d->pro_mode == SISR_PRO_AFFINE_ACT ||
-                         (d->pro_mode == SISR_PRO_RES_AFFINE && d->x2 && d->x_out && ((d->pa && d->pd) || d->fin_stat));
-    if (d->fin_stat && !((d->pro_mode == SISR_PRO_AFFINE_ACT || d->pro_mode == SISR_PRO_RES_AFFINE) && d->fin_cnt && d->fin_gamma &&
-                         d->fin_beta && d->fin_rm && d->fin_rv && d->fin_k && d->fin_rows > 0))
-        return 0;
-    if (fwd_pro && !d->res && !d->bnb_part) return 1;
-    const bool bwd_pro = d->pro_mode == SISR_PRO_BNBWD || d->pro_mode == SISR_PRO_BNACT_BWD;
-    if (bwd_pro && !d->stat_part && !d->bias && (!d->bnb_part || (d->bnb_x && !d->bnbx_bf16))) return 2;
-    return 0;
-}
-
-// rows of stat_part / cnt_part a launch of this descriptor writes
-extern "C" int sisr_conv2d_f32_parts(const SisrConvDesc* d) {
-    if (!d) return SISR_E_BADARG;
-    return sisr_conv2d_trunk_f32_eligible(d) ? cf_streams(d) : d->plan.n_tiles;
-}
-
-// rows of bnb_part (one per workgroup) a data-gradient launch of this descriptor writes; 0: this kernel does not take it
-extern "C" int sisr_conv2d_f32_bnb_parts(const SisrConvDesc* d) {
-    if (!d) return SISR_E_BADARG;
-    return sisr_conv2d_trunk_f32_eligible(d) == 2 ? 2 * cf_streams(d) : 0;
+    if (d->plan.CK != 32 || d->plan.PS != CF_PS || d->plan.KROWP != CF_KROWP || d->plan.n_chunk != 2 || d->plan.CoutPad != d->Cout) return 0;
+    if (d->res_bf16) return 0;
+    const int role = sisr_trunk_conv_role(d, CF_KIND);
+    if (role == 2 && d->bnb_part && !(d->bnb_x && !d->bnbx_bf16)) return 0;
+    return role;
 }
 
 template <int PRO, bool SPLIT>
@@ -646,25 +614,14 @@ static int launch_cf(const CTrunkF32Args& a, bool split, hipStream_t st) {
     return split ? launch_cf_t<PRO, true>(a, st) : launch_cf_t<PRO, false>(a, st);
 }
 
-// called by sisr_conv2d_f32 for eligible descriptors
+// called by sisr_conv2d_f32 for descriptors routed here
 int sisr_conv2d_trunk_f32_launch(const SisrConvDesc* d, hipStream_t st) {
-    if (operand_needs_x2(d->pro_mode) && !d->x2) return SISR_E_BADARG;
     CTrunkF32Args a{};
-    a.fin.stat = d->fin_stat; a.fin.cnt = d->fin_cnt; a.fin.gamma = d->fin_gamma; a.fin.beta = d->fin_beta;
-    a.fin.rm = d->fin_rm; a.fin.rv = d->fin_rv; a.fin.k = d->fin_k; a.fin.rows = d->fin_rows; a.fin.momentum = d->fin_momentum; a.fin.eps = d->fin_eps;
-    a.x1 = d->x1; a.x2 = d->x2; a.x_out = d->x_out; a.pa = d->pa; a.pb = d->pb; a.pd = d->pd; a.ps = d->ps; a.pt = d->pt;
-    a.slope_p = d->pro_slope_p; a.slope = d->pro_slope;
-    a.wpk = d->wpk; a.bias = d->bias; a.res = d->res; a.y = d->y; a.stat_part = d->stat_part; a.cnt_part = d->cnt_part;
+    sisr_trunk_conv_args(a, d, CF_KIND);
     // the LDS-order image behind the standard one, when the caller packed it in the mode this launch computes in (trunk layers only)
     const int img_mode = (d->plan.variant >> 1) & 3;
     a.wimg = (d->Cin == 64 && d->Cout == 64 && img_mode == (d->mfma_split ? 2 : 1)) ? static_cast<const void*>(d->wpk + d->plan.wpk_elems) : nullptr;
-    a.N = d->N; a.H = d->H; a.W = d->W;
-    a.tiles_x = d->W / CF_TW; a.per_img = (d->H / CF_TH) * a.tiles_x; a.total = d->N * a.per_img;
-    a.streams = cf_streams(d);
-    a.glog = d->Cout == 256 ? 3 : 1; a.cout_pad = d->Cout == 256 ? 256 : 64; a.shuffle = d->y_mode == SISR_Y_NHWC_SHUFFLE2 ? 1 : 0;
-    a.bnb_x = d->bnb_x; a.bnb_scale = d->bnb_scale; a.bnb_shift = d->bnb_shift; a.bnb_mean = d->bnb_mean; a.bnb_invstd = d->bnb_invstd;
-    a.bnb_slope_p = d->bnb_slope_p; a.bnb_slope = d->bnb_slope; a.bnb_act = d->bnb_act; a.bnb_part = d->bnb_part;
-    a.m_tiles_x = fdiv_magic(a.tiles_x); a.m_per_img = fdiv_magic(a.per_img);
+    a.streams = sisr_conv2d_trunk_f32_streams(d); a.glog = d->Cout == 256 ? 3 : 1;
     a.xsc = 1; a.xph = 0;
     if (d->Cin == 256) {
         // [8 chunks][3 filter rows][64 couts][KROWP]: phase ph owns chunks 2 ph, 2 ph + 1

@@ -259,6 +259,24 @@ static int launch_wgrad(const SisrWgradDesc* d, hipStream_t st) {
     return sisr_launch<wgrad_mfma_f32_kernel<NACC>>(grid, dim3(SISR_BLOCK), d->lds_bytes, SISR_LDS_BASE_DEFAULT, st, *d);
 }
 
+// the kernel family sisr_conv2d_wgrad_f32 hands `d` to (the only place that orders these families)
+static SisrRoute wgrad_f32_route(const SisrWgradDesc* d) {
+    if (sisr_wgrad_trunk_f32_eligible(d)) return SISR_ROUTE_TRUNK;
+    if (sisr_wgrad_thin_eligible(d)) return SISR_ROUTE_THIN;                    // bf16 build: the first conv (3-channel image)
+    return sisr_wgrad_toimage_f32_eligible(d) ? SISR_ROUTE_TOIMAGE : SISR_ROUTE_GENERIC;       // the last conv (64 -> 3), fp32 tensors
+}
+
+// slabs a launch of this descriptor writes (rows of `slab` at slab_stride)
+extern "C" int sisr_wgrad_f32_slabs(const SisrWgradDesc* d) {
+    if (!d) return SISR_E_BADARG;
+    switch (wgrad_f32_route(d)) {
+        case SISR_ROUTE_TRUNK: return sisr_wgrad_trunk_f32_slabs(d);
+        case SISR_ROUTE_THIN: return sisr_wgrad_thin_slabs(d);
+        case SISR_ROUTE_TOIMAGE: return sisr_wgrad_toimage_slabs(d);
+        default: return d->n_slabs;
+    }
+}
+
 extern "C" int sisr_conv2d_wgrad_f32(const SisrWgradDesc* d, void* stream) {
     if (!d || !d->x1 || !d->g1 || !d->slab) return SISR_E_BADARG;
     if (operand_needs_x2(d->pro_mode) && !d->x2) return SISR_E_BADARG;
@@ -267,9 +285,10 @@ extern "C" int sisr_conv2d_wgrad_f32(const SisrWgradDesc* d, void* stream) {
     if (d->grid_x <= 0 || d->lds_bytes <= 0 || d->lds_bytes > 160 * 1024 || d->KH * d->NT > WG_NACC)
         return SISR_E_BADARG;
     hipStream_t st = sisr_stream(stream);
-    if (sisr_wgrad_trunk_f32_eligible(d)) return sisr_wgrad_trunk_f32_launch(d, st);
-    if (sisr_wgrad_thin_eligible(d)) return sisr_wgrad_thin_launch(d, st);      // bf16 build: the first conv (3-channel image)
-    if (sisr_wgrad_toimage_f32_eligible(d)) return sisr_wgrad_toimage_f32_launch(d, st);    // the last conv (64 -> 3), fp32 tensors
+    const SisrRoute route = wgrad_f32_route(d);
+    if (route == SISR_ROUTE_TRUNK) return sisr_wgrad_trunk_f32_launch(d, st);
+    if (route == SISR_ROUTE_THIN) return sisr_wgrad_thin_launch(d, st);
+    if (route == SISR_ROUTE_TOIMAGE) return sisr_wgrad_toimage_f32_launch(d, st);
     switch (d->KH * d->NT) {
         case 1: return launch_wgrad<1>(d, st);
         case 2: return launch_wgrad<2>(d, st);

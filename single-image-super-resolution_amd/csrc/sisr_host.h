@@ -28,6 +28,14 @@ int sisr_device_index();                   // misc.hip: current device id, clamp
 // misc.hip: workgroup slots a persistent kernel may fill = CUs of the CURRENT device.  SISR_PERSIST_MAX_WG=<n> caps it
 // (test knob: a small cap makes a small input walk many tiles per workgroup, the schedule of the full-size launches)
 int sisr_cu_slots();
+// equal shares: workgroups of a persistent kernel that walks `total` tiles on `slots` workgroup slots.  Every workgroup walks
+// rounds = ceil(total / slots) tiles, so ceil(total / rounds) of them cover the tiles with no slot idle for a whole round.
+static inline int sisr_equal_shares(int total, int slots, int* rounds_out = nullptr) {
+    if (slots < 1) slots = 1;
+    const int rounds = (total + slots - 1) / slots;
+    if (rounds_out) *rounds_out = rounds;
+    return (total + rounds - 1) / rounds;
+}
 struct SisrLdsCap { int v[SISR_MAX_DEVICES]; };
 // raise hipFuncAttributeMaxDynamicSharedMemorySize of `fn` on the current device when `bytes` exceeds what was set
 // (`base`: the cap a kernel starts with -- 64 KB without the attribute, 0 forces the first call to set it)
@@ -52,16 +60,25 @@ static int sisr_launch(dim3 grid, dim3 block, int lds, int lds_base, hipStream_t
     return 0;
 }
 
-// ---- host entry points called across files: sisr_conv2d_f32 / _bf16 and sisr_conv2d_wgrad_f32 / _bf16 hand an eligible
-// descriptor (the public sisr_*_eligible) to the specialised kernel's file ---------------------------------------------
+// ---- the kernel family a descriptor goes to.  Each of the four dispatchers (sisr_conv2d_bf16 / _f32, sisr_conv2d_wgrad_bf16 / _f32)
+// has ONE route function next to it that holds the ordered chain of the public sisr_*_eligible calls; the dispatcher and the sizing
+// entry points its callers allocate from switch on that route, so no buffer is sized for another kernel than the one that runs ----
+enum SisrRoute { SISR_ROUTE_GENERIC, SISR_ROUTE_DEEP, SISR_ROUTE_TOIMAGE, SISR_ROUTE_TRUNK, SISR_ROUTE_THIN };
+
+// ---- host entry points called across files: the dispatchers hand a routed descriptor to the specialised kernel's file, and ask it
+// for the grid its launch will have ------------------------------------------------------------------------------------------------
 int sisr_conv2d_trunk_launch(const SisrConvDesc* d, hipStream_t st);          // conv_trunk.hip
+int sisr_conv2d_trunk_grid(const SisrConvDesc* d);                            // conv_trunk.hip: workgroups
 int sisr_conv2d_trunk_f32_launch(const SisrConvDesc* d, hipStream_t st);      // conv_trunk_f32.hip
+int sisr_conv2d_trunk_f32_streams(const SisrConvDesc* d);                     // conv_trunk_f32.hip: pixel-tile streams
 int sisr_conv2d_thin_launch(const SisrConvDesc* d, hipStream_t st);           // conv_thin.hip
 int sisr_conv2d_toimage_launch(const SisrConvDesc* d, hipStream_t st);        // conv_toimage.hip
 int sisr_conv2d_deep_launch(const SisrConvDesc* d, hipStream_t st);           // conv_deep.hip
 int sisr_conv2d_deep_parts(const SisrConvDesc* d);                            // conv_deep.hip
 int sisr_wgrad_trunk_launch(const SisrWgradDesc* d, hipStream_t st);          // wgrad_trunk.hip
+int sisr_wgrad_trunk_slabs(const SisrWgradDesc* d);                           // wgrad_trunk.hip
 int sisr_wgrad_trunk_f32_launch(const SisrWgradDesc* d, hipStream_t st);      // wgrad_trunk_f32.hip
+int sisr_wgrad_trunk_f32_slabs(const SisrWgradDesc* d);                       // wgrad_trunk_f32.hip
 int sisr_wgrad_thin_launch(const SisrWgradDesc* d, hipStream_t st);           // wgrad_thin.hip
 int sisr_wgrad_thin_slabs(const SisrWgradDesc* d);                            // wgrad_thin.hip
 int sisr_wgrad_toimage_launch(const SisrWgradDesc* d, hipStream_t st);        // wgrad_toimage.hip

@@ -252,6 +252,35 @@ static int launch_wgrad_bf16(const SisrWgradDesc* d, hipStream_t st) {
     return sisr_launch<wgrad_mfma_bf16_kernel<TPW>>(grid, dim3(SISR_BLOCK), d->lds_bytes, SISR_LDS_BASE_DEFAULT, st, *d);
 }
 
+// the kernel family sisr_conv2d_wgrad_bf16 hands `d` to (the only place that orders these families)
+static SisrRoute wgrad_bf16_route(const SisrWgradDesc* d) {
+    if (sisr_wgrad_trunk_eligible(d)) return SISR_ROUTE_TRUNK;
+    if (sisr_wgrad_toimage_eligible(d)) return SISR_ROUTE_TOIMAGE;              // the generator's last conv (64 -> 3)
+    return sisr_wgrad_deep_eligible(d) ? SISR_ROUTE_DEEP : SISR_ROUTE_GENERIC;  // 3x3, channels in 64s
+}
+
+// slabs a launch of this descriptor writes (rows of `slab` at slab_stride): one per workgroup
+extern "C" int sisr_wgrad_bf16_slabs(const SisrWgradDesc* d) {
+    if (!d) return SISR_E_BADARG;
+    switch (wgrad_bf16_route(d)) {
+        case SISR_ROUTE_TRUNK: return sisr_wgrad_trunk_slabs(d);
+        case SISR_ROUTE_TOIMAGE: return sisr_wgrad_toimage_slabs(d);
+        case SISR_ROUTE_DEEP: return d->deep.n_pb;
+        default: return d->n_slabs;
+    }
+}
+
+// leading elements of every slab row that the launch of `d` stores as bf16 (pass it to sisr_slab_reduce_f32 /
+// sisr_bn_bwd_finalize_slab); 0: fp32 slabs
+extern "C" int64_t sisr_wgrad_bf16_slab_lead(const SisrWgradDesc* d) {
+    if (!d) return 0;
+    switch (wgrad_bf16_route(d)) {
+        case SISR_ROUTE_TRUNK: return !sisr_switch_off("SISR_SLAB_BF16") ? (int64_t)d->slab_elems : 0;
+        case SISR_ROUTE_DEEP: return d->deep.slab_bf16 ? (int64_t)d->slab_elems : 0;
+        default: return 0;
+    }
+}
+
 extern "C" int sisr_conv2d_wgrad_bf16(const SisrWgradDesc* d, void* stream) {
     if (!d || !d->x1 || !d->g1 || !d->slab) return SISR_E_BADARG;
     if (operand_needs_x2(d->pro_mode) && !d->x2) return SISR_E_BADARG;
@@ -259,9 +288,10 @@ extern "C" int sisr_conv2d_wgrad_bf16(const SisrWgradDesc* d, void* stream) {
     if (d->slab_stride < d->slab_elems || d->CK != BF_CK || d->PS != BF_PS) return SISR_E_BADARG;
     if (d->grid_x <= 0 || d->lds_bytes <= 0 || d->lds_bytes > 160 * 1024) return SISR_E_BADARG;
     hipStream_t st = sisr_stream(stream);
-    if (sisr_wgrad_trunk_eligible(d)) return sisr_wgrad_trunk_launch(d, st);
-    if (sisr_wgrad_toimage_eligible(d)) return sisr_wgrad_toimage_launch(d, st);    // the generator's last conv (64 -> 3)
-    if (sisr_wgrad_deep_eligible(d)) return sisr_wgrad_deep_launch(d, st);          // 3x3, channels in 64s
+    const SisrRoute route = wgrad_bf16_route(d);
+    if (route == SISR_ROUTE_TRUNK) return sisr_wgrad_trunk_launch(d, st);
+    if (route == SISR_ROUTE_TOIMAGE) return sisr_wgrad_toimage_launch(d, st);
+    if (route == SISR_ROUTE_DEEP) return sisr_wgrad_deep_launch(d, st);
     const int np = 4 / d->NJ, ntap = d->KH * d->KW;
     switch ((ntap + np - 1) / np) {                        // taps per wave
         case 1: return launch_wgrad_bf16<1>(d, st);

@@ -283,8 +283,6 @@ __global__ void __launch_bounds__(256, 1) wgrad_thin_kernel(const WThinArgs a) {
     }
 }
 
-static int wn_cus() { return sisr_cu_slots(); }
-
 // 9: the generator's first conv, 3: the discriminator's, 0: not taken
 static int wn_ks(const SisrWgradDesc* d) {
     if (sisr_switch_off("SISR_THIN") || !d) return 0;           // A/B switch: SISR_THIN=0 keeps the generic kernel
@@ -301,13 +299,7 @@ static int wn_ks(const SisrWgradDesc* d) {
 }
 extern "C" int sisr_wgrad_thin_eligible(const SisrWgradDesc* d) { return wn_ks(d) != 0; }
 
-static int wn_grid(const SisrWgradDesc* d) {
-    const int total = d->N * (d->H / WN_TH) * (d->W / WN_TW), cus = wn_cus();
-    const int rounds = (total + cus - 1) / cus;             // equal shares: every workgroup walks `rounds` tiles
-    return (total + rounds - 1) / rounds;
-}
-
-int sisr_wgrad_thin_slabs(const SisrWgradDesc* d) { return wn_grid(d); }
+int sisr_wgrad_thin_slabs(const SisrWgradDesc* d) { return sisr_equal_shares(d->N * (d->H / WN_TH) * (d->W / WN_TW), sisr_cu_slots()); }
 
 int sisr_wgrad_thin_launch(const SisrWgradDesc* d, hipStream_t st) {
     constexpr int lds_bytes = WN_XBYTES + WN_DBYTES;
@@ -323,7 +315,7 @@ int sisr_wgrad_thin_launch(const SisrWgradDesc* d, hipStream_t st) {
     a.per_img = a.tiles_x * (d->H / WN_TH);
     a.total = a.per_img * d->N;
     a.slab_stride = d->slab_stride;
-    const dim3 grid(wn_grid(d)), block(256);
+    const dim3 grid(sisr_wgrad_thin_slabs(d)), block(256);
     if (ks == 9) {
         if (actb) return sisr_launch<wgrad_thin_kernel<true, 9>>(grid, block, lds_bytes, 0, st, a);
         return sisr_launch<wgrad_thin_kernel<false, 9>>(grid, block, lds_bytes, 0, st, a);

@@ -199,8 +199,6 @@ __global__ void __launch_bounds__(256, 1) wgrad_toimage_kernel(const WToImageArg
     }
 }
 
-static int wi_cus() { return sisr_cu_slots(); }
-
 extern "C" int sisr_wgrad_toimage_eligible(const SisrWgradDesc* d) {
     if (sisr_switch_off("SISR_THIN") || !d) return 0;           // A/B switch: SISR_THIN=0 keeps the generic kernel
     if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_y != 1 || d->pad_x != 1) return 0;
@@ -213,13 +211,7 @@ extern "C" int sisr_wgrad_toimage_eligible(const SisrWgradDesc* d) {
     return 1;
 }
 
-static int wi_grid(const SisrWgradDesc* d) {
-    const int total = d->N * (d->H / WI_TH) * (d->W / WI_TW), cus = wi_cus();
-    const int rounds = (total + cus - 1) / cus;             // equal shares: every workgroup walks `rounds` tiles
-    return (total + rounds - 1) / rounds;
-}
-
-int sisr_wgrad_toimage_slabs(const SisrWgradDesc* d) { return wi_grid(d); }
+int sisr_wgrad_toimage_slabs(const SisrWgradDesc* d) { return sisr_equal_shares(d->N * (d->H / WI_TH) * (d->W / WI_TW), sisr_cu_slots()); }
 
 template <bool ACT, bool TANHB>
 static int wi_launch(const WToImageArgs& a, int grid, hipStream_t st) {
@@ -238,7 +230,7 @@ int sisr_wgrad_toimage_launch(const SisrWgradDesc* d, hipStream_t st) {
     a.per_img = a.tiles_x * (d->H / WI_TH);
     a.total = a.per_img * d->N;
     a.slab_stride = d->slab_stride;
-    const int grid = wi_grid(d);
+    const int grid = sisr_wgrad_toimage_slabs(d);
     if (act) return tanhb ? wi_launch<true, true>(a, grid, st) : wi_launch<true, false>(a, grid, st);
     return tanhb ? wi_launch<false, true>(a, grid, st) : wi_launch<false, false>(a, grid, st);
 }
@@ -428,7 +420,7 @@ int sisr_wgrad_toimage_f32_launch(const SisrWgradDesc* d, hipStream_t st) {
     a.total = a.per_img * d->N;
     a.CK = d->CK; a.PS = d->PS; a.KROWP = d->KROWP; a.CoutPad = d->CoutPad; a.slab_elems = d->slab_elems;
     a.slab_stride = d->slab_stride;
-    const int grid = wi_grid(d);
+    const int grid = sisr_wgrad_toimage_slabs(d);
     if (act) return tanhb ? wj_launch<true, true>(a, grid, st) : wj_launch<true, false>(a, grid, st);
     return tanhb ? wj_launch<false, true>(a, grid, st) : wj_launch<false, false>(a, grid, st);
 }

@@ -24,10 +24,7 @@
 #include "sisr_bf16_stage.h"
 #include "sisr_instr.h"
 
-#include <algorithm>
-#include <cstring>
 #include <type_traits>
-#include <cstdlib>
 
 #define WT_TH 8
 #define WT_TW 16
@@ -367,54 +364,17 @@ __global__ void __launch_bounds__(WT_THREADS, 2) wgrad_trunk_table_kernel(const 
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-static int wtrunk_grid(const SisrWgradDesc* d) {
-    const int total = d->N * (d->H / WT_TH) * (d->W / WT_TW);
-    const int cus = sisr_cu_slots();
-    const int G = d->Cout == 256 ? 4 : 1;       // cout groups: each tile stream is served by G workgroups
-    const int slots = std::max(1, cus / G);
-    const int rounds = (total + slots - 1) / slots;
-    return G * ((total + rounds - 1) / rounds);  // equal shares
-}
+#include "sisr_trunk_host.h"
+static const SisrTrunkKind WT_KIND = {WT_TH, WT_TW, true, 128};
 
 extern "C" int sisr_wgrad_trunk_eligible(const SisrWgradDesc* d) {
     if (!d || sisr_switch_off("SISR_TRUNK")) return 0;         // A/B switch: SISR_TRUNK=0 keeps the generic kernel
-    if (sisr_switch_off("SISR_TRUNK_WGRAD")) return 0;
-    if (d->Cin != 64 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_y != 1 || d->pad_x != 1) return 0;
-    // Cout = 64 (trunk: BatchNorm-backward gradient prologues), or 256 with the gradient stored shuffled and an
-    // activation-backward prologue -- the upscale conv
-    const bool up_off = sisr_switch_off("SISR_TRUNK_UP");      // A/B switch for the upscale conv alone
-    const bool up = !up_off && d->Cout == 256 && d->g_mode == SISR_X_NHWC_UNSHUFFLE2 && d->CoutPad == 256 &&
-                    d->gpro_mode == SISR_PRO_ACT_BWD && (int64_t)d->N * d->H * d->W * 512 < (1ll << 31);
-    if (!up && (d->Cout != 64 || d->g_mode != SISR_X_NHWC || d->CoutPad != 64)) return 0;
-    if (d->x_mode != SISR_X_NHWC || !d->x_bf16 || !d->g_bf16) return 0;
-    if (d->Ho != d->H || d->Wo != d->W || (d->H % WT_TH) || (d->W % WT_TW)) return 0;
     if (d->n_chunk != 2 || d->KROWP != 9 * 32) return 0;
-    if ((int64_t)d->N * d->H * d->W * 128 >= (1ll << 31)) return 0;
-    if (d->N * (d->H / WT_TH) * (d->W / WT_TW) >= 65536) return 0;
-    const bool xp = d->pro_mode == SISR_PRO_NONE || d->pro_mode == SISR_PRO_ACT || d->pro_mode == SISR_PRO_AFFINE_ACT;
-    const bool gp = up || d->gpro_mode == SISR_PRO_BNBWD || d->gpro_mode == SISR_PRO_BNACT_BWD;
-    return xp && gp ? 1 : 0;
+    return sisr_trunk_wgrad_ok(d, WT_KIND) ? 1 : 0;
 }
 
-// The persistent kernel writes the gradient part of its slabs as bf16 (231 slabs x 147 KB written and re-read per layer were
-// two thirds of the finishing launch; a partial sum rounded to bf16 costs up to ~2e-3 relative on a cancelling total, inside this
-// build's error budget -- its tensors are bf16).  SISR_SLAB_BF16=0 keeps fp32 slabs (A/B).
-// leading elements of every slab row that the launch of `d` stores as bf16 (pass it to sisr_slab_reduce_f32 /
-// sisr_bn_bwd_finalize_slab); 0: fp32 slabs
-extern "C" int64_t sisr_wgrad_bf16_slab_lead(const SisrWgradDesc* d) {
-    if (!d) return 0;
-    if (sisr_wgrad_trunk_eligible(d)) return !sisr_switch_off("SISR_SLAB_BF16") ? (int64_t)d->slab_elems : 0;
-    if (sisr_wgrad_toimage_eligible(d)) return 0;
-    return sisr_wgrad_deep_eligible(d) && d->deep.slab_bf16 ? (int64_t)d->slab_elems : 0;
-}
-
-// slabs a launch of this descriptor writes (rows of `slab` at slab_stride): one per workgroup
-extern "C" int sisr_wgrad_bf16_slabs(const SisrWgradDesc* d) {
-    if (!d) return SISR_E_BADARG;
-    if (sisr_wgrad_trunk_eligible(d)) return wtrunk_grid(d) / (d->Cout == 256 ? 4 : 1);
-    if (sisr_wgrad_toimage_eligible(d)) return sisr_wgrad_toimage_slabs(d);
-    return sisr_wgrad_deep_eligible(d) ? d->deep.n_pb : d->n_slabs;
-}
+// slabs a launch of this descriptor writes (rows of `slab` at slab_stride): one per tile stream
+int sisr_wgrad_trunk_slabs(const SisrWgradDesc* d) { return sisr_trunk_wgrad_grid(d, WT_KIND) / (d->Cout == 256 ? 4 : 1); }
 
 template <int GPRO>
 static int launch_wtrunk(const WTrunkArgs& a, int grid, hipStream_t st) {
@@ -422,62 +382,32 @@ static int launch_wtrunk(const WTrunkArgs& a, int grid, hipStream_t st) {
     return sisr_launch<wgrad_trunk_kernel<GPRO>>(dim3(grid), dim3(WT_THREADS), lds_bytes, 0, st, a);
 }
 
-static WTrunkArgs wtrunk_args(const SisrWgradDesc* d);
+// The persistent kernel writes the gradient part of its slabs as bf16 (231 slabs x 147 KB written and re-read per layer were
+// two thirds of the finishing launch; a partial sum rounded to bf16 costs up to ~2e-3 relative on a cancelling total, inside this
+// build's error budget -- its tensors are bf16).  SISR_SLAB_BF16=0 keeps fp32 slabs (A/B; sisr_wgrad_bf16_slab_lead reads it too).
+static WTrunkArgs wtrunk_args(const SisrWgradDesc* d) {
+    WTrunkArgs a = sisr_trunk_wgrad_args<WTrunkArgs>(d, WT_KIND);
+    a.slab_bf16 = !sisr_switch_off("SISR_SLAB_BF16") ? 1 : 0;
+    return a;
+}
 
-// called by sisr_conv2d_wgrad_bf16 for eligible descriptors
+// called by sisr_conv2d_wgrad_bf16 for descriptors routed here
 int sisr_wgrad_trunk_launch(const SisrWgradDesc* d, hipStream_t st) {
-    if (operand_needs_x2(d->gpro_mode) && !d->g2) return SISR_E_BADARG;
-    if (d->pro_mode == SISR_PRO_AFFINE_ACT && (!d->pa || !d->pd)) return SISR_E_BADARG;
-    if (d->gpro_mode != SISR_PRO_ACT_BWD && (!d->qa || !d->qb || !d->qd || (d->gpro_mode == SISR_PRO_BNACT_BWD && (!d->qs || !d->qt))))
-        return SISR_E_BADARG;
+    if (!sisr_trunk_wgrad_operands(d)) return SISR_E_BADARG;
     const WTrunkArgs a = wtrunk_args(d);
-    const int grid = wtrunk_grid(d);
+    const int grid = sisr_trunk_wgrad_grid(d, WT_KIND);
     if (d->gpro_mode == SISR_PRO_ACT_BWD) return launch_wtrunk<SISR_PRO_ACT_BWD>(a, grid, st);
     if (d->gpro_mode == SISR_PRO_BNBWD) return launch_wtrunk<SISR_PRO_BNBWD>(a, grid, st);
     return launch_wtrunk<SISR_PRO_BNACT_BWD>(a, grid, st);
 }
 
-static WTrunkArgs wtrunk_args(const SisrWgradDesc* d) {
-    WTrunkArgs a;
-    a.x1 = d->x1; a.g1 = d->g1; a.g2 = d->g2;
-    a.pa = d->pa; a.pd = d->pd; a.xslope_p = d->pro_slope_p; a.xslope = d->pro_slope;
-    a.qa = d->qa; a.qb = d->qb; a.qd = d->qd; a.qs = d->qs; a.qt = d->qt;
-    a.gslope_p = d->gpro_slope_p; a.gslope = d->gpro_slope;
-    a.slab = d->slab; a.bias_slab = d->bias_slab; a.slab_stride = d->slab_stride;
-    a.N = d->N; a.H = d->H; a.W = d->W;
-    a.tiles_x = d->W / WT_TW; a.per_img = (d->H / WT_TH) * a.tiles_x; a.total = d->N * a.per_img;
-    a.m_tiles_x = fdiv_magic(a.tiles_x); a.m_per_img = fdiv_magic(a.per_img);
-    a.xpro = d->pro_mode;
-    a.glog = d->Cout == 256 ? 2 : 0; a.cout_pad = d->Cout == 256 ? 256 : 64; a.gshuffle = d->g_mode == SISR_X_NHWC_UNSHUFFLE2 ? 1 : 0;
-    a.slab_bf16 = !sisr_switch_off("SISR_SLAB_BF16") ? 1 : 0;
-    return a;
-}
-
 // ---- a batch of trunk layers (Cout = 64, one gradient-prologue kind): see wgrad_trunk_table_kernel ---------------------------------
 extern "C" int sisr_wgrad_trunk_batch_arg_bytes(void) { return (int)sizeof(WTrunkArgs); }
 
-static int wtrunk_batch_check(const SisrWgradDesc* descs, int n) {
-    if (!descs || n <= 0 || n > 4096) return SISR_E_BADARG;
-    for (int i = 0; i < n; ++i) {
-        const SisrWgradDesc* d = descs + i;
-        if (!sisr_wgrad_trunk_eligible(d) || d->Cout != 64 || d->gpro_mode != descs[0].gpro_mode) return SISR_E_BADARG;
-        if (!d->x1 || !d->g1 || !d->g2 || !d->slab || d->slab_stride < d->slab_elems) return SISR_E_BADARG;
-        if (d->pro_mode == SISR_PRO_AFFINE_ACT && (!d->pa || !d->pd)) return SISR_E_BADARG;
-        if (!d->qa || !d->qb || !d->qd || (d->gpro_mode == SISR_PRO_BNACT_BWD && (!d->qs || !d->qt))) return SISR_E_BADARG;
-    }
-    return 0;
-}
+static int wtrunk_batch_check(const SisrWgradDesc* descs, int n) { return sisr_trunk_wgrad_batch_check(descs, n, sisr_wgrad_trunk_eligible, false); }
 
-// fills args_host (n * sisr_wgrad_trunk_batch_arg_bytes() bytes) with the kernel's view of the n descriptors; the caller copies it to
-// device memory and passes that copy to sisr_wgrad_trunk_batch (the same staging route as every descriptor table of this library)
 extern "C" int sisr_wgrad_trunk_batch_args(const SisrWgradDesc* descs, int32_t n, void* args_host) {
-    if (!args_host) return SISR_E_BADARG;
-    if (int e = wtrunk_batch_check(descs, n)) return e;
-    for (int i = 0; i < n; ++i) {
-        const WTrunkArgs a = wtrunk_args(descs + i);
-        std::memcpy(static_cast<unsigned char*>(args_host) + (size_t)i * sizeof(WTrunkArgs), &a, sizeof(WTrunkArgs));
-    }
-    return 0;
+    return sisr_trunk_wgrad_batch_args<WTrunkArgs>(descs, n, args_host, wtrunk_batch_check, wtrunk_args);
 }
 
 // wgs_per_layer workgroups (= slabs, rows of each descriptor's `slab`) serve every layer; grid = n * wgs_per_layer

@@ -20,9 +20,6 @@
 #include "sisr_bf16_stage.h"
 #include "sisr_instr.h"
 
-#include <algorithm>
-#include <cstring>
-#include <cstdlib>
 #include <type_traits>
 
 #define WF_TH 4
@@ -360,42 +357,17 @@ __global__ void __launch_bounds__(WF_THREADS, 2) wgrad_trunk_f32_table_kernel(co
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-static int wf_grid(const SisrWgradDesc* d) {
-    const int total = d->N * (d->H / WF_TH) * (d->W / WF_TW);
-    const int cus = sisr_cu_slots();
-    const int G = d->Cout == 256 ? 4 : 1;       // cout groups: each tile stream is served by G workgroups
-    const int slots = std::max(1, cus / G);
-    const int rounds = (total + slots - 1) / slots;
-    return G * ((total + rounds - 1) / rounds);  // equal shares
-}
+#include "sisr_trunk_host.h"
+static const SisrTrunkKind WF_KIND = {WF_TH, WF_TW, false, 256};
 
 extern "C" int sisr_wgrad_trunk_f32_eligible(const SisrWgradDesc* d) {
     if (!d || sisr_switch_off("SISR_TRUNK")) return 0;         // A/B switch: SISR_TRUNK=0 keeps the generic kernel
-    if (sisr_switch_off("SISR_TRUNK_WGRAD")) return 0;
-    if (d->Cin != 64 || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_y != 1 || d->pad_x != 1) return 0;
-    // Cout = 64 (trunk: BatchNorm-backward gradient prologues), or 256 with the gradient stored shuffled and an
-    // activation-backward prologue -- the upscale conv
-    const bool up_off = sisr_switch_off("SISR_TRUNK_UP");      // A/B switch for the upscale conv alone
-    const bool up = !up_off && d->Cout == 256 && d->g_mode == SISR_X_NHWC_UNSHUFFLE2 && d->CoutPad == 256 &&
-                    d->gpro_mode == SISR_PRO_ACT_BWD && (int64_t)d->N * d->H * d->W * 1024 < (1ll << 31);
-    if (!up && (d->Cout != 64 || d->g_mode != SISR_X_NHWC || d->CoutPad != 64)) return 0;
-    if (d->x_mode != SISR_X_NHWC || d->x_bf16 || d->g_bf16) return 0;
-    if (d->Ho != d->H || d->Wo != d->W || (d->H % WF_TH) || (d->W % WF_TW)) return 0;
     if (d->CK != 32 || d->PS != WF_PS || d->KROWP != WF_KROWP || d->n_chunk != 2) return 0;
-    if ((int64_t)d->N * d->H * d->W * 256 >= (1ll << 31)) return 0;
-    if (d->N * (d->H / WF_TH) * (d->W / WF_TW) >= 65536) return 0;
-    const bool xp = d->pro_mode == SISR_PRO_NONE || d->pro_mode == SISR_PRO_ACT || d->pro_mode == SISR_PRO_AFFINE_ACT;
-    const bool gp = up || d->gpro_mode == SISR_PRO_BNBWD || d->gpro_mode == SISR_PRO_BNACT_BWD;
-    return xp && gp ? 1 : 0;
+    return sisr_trunk_wgrad_ok(d, WF_KIND) ? 1 : 0;
 }
 
-// slabs a launch of this descriptor writes (rows of `slab` at slab_stride)
-extern "C" int sisr_wgrad_f32_slabs(const SisrWgradDesc* d) {
-    if (!d) return SISR_E_BADARG;
-    if (sisr_wgrad_trunk_f32_eligible(d)) return wf_grid(d) / (d->Cout == 256 ? 4 : 1);
-    if (sisr_wgrad_thin_eligible(d)) return sisr_wgrad_thin_slabs(d);
-    return sisr_wgrad_toimage_f32_eligible(d) ? sisr_wgrad_toimage_slabs(d) : d->n_slabs;
-}
+// slabs a launch of this descriptor writes (rows of `slab` at slab_stride): one per tile stream
+int sisr_wgrad_trunk_f32_slabs(const SisrWgradDesc* d) { return sisr_trunk_wgrad_grid(d, WF_KIND) / (d->Cout == 256 ? 4 : 1); }
 
 template <int GPRO, bool SPLIT>
 static int launch_wf_t(const WTrunkF32Args& a, int grid, hipStream_t st) {
@@ -407,60 +379,25 @@ static int launch_wf(const WTrunkF32Args& a, bool split, int grid, hipStream_t s
     return split ? launch_wf_t<GPRO, true>(a, grid, st) : launch_wf_t<GPRO, false>(a, grid, st);
 }
 
-static WTrunkF32Args wf_args(const SisrWgradDesc* d);
+static WTrunkF32Args wf_args(const SisrWgradDesc* d) { return sisr_trunk_wgrad_args<WTrunkF32Args>(d, WF_KIND); }
 
-// called by sisr_conv2d_wgrad_f32 for eligible descriptors
+// called by sisr_conv2d_wgrad_f32 for descriptors routed here
 int sisr_wgrad_trunk_f32_launch(const SisrWgradDesc* d, hipStream_t st) {
-    if (operand_needs_x2(d->gpro_mode) && !d->g2) return SISR_E_BADARG;
-    if (d->pro_mode == SISR_PRO_AFFINE_ACT && (!d->pa || !d->pd)) return SISR_E_BADARG;
-    if (d->gpro_mode != SISR_PRO_ACT_BWD && (!d->qa || !d->qb || !d->qd || (d->gpro_mode == SISR_PRO_BNACT_BWD && (!d->qs || !d->qt))))
-        return SISR_E_BADARG;
+    if (!sisr_trunk_wgrad_operands(d)) return SISR_E_BADARG;
     const WTrunkF32Args a = wf_args(d);
-    const int grid = wf_grid(d);
+    const int grid = sisr_trunk_wgrad_grid(d, WF_KIND);
     if (d->gpro_mode == SISR_PRO_ACT_BWD) return launch_wf<SISR_PRO_ACT_BWD>(a, d->mfma_split != 0, grid, st);
     if (d->gpro_mode == SISR_PRO_BNBWD) return launch_wf<SISR_PRO_BNBWD>(a, d->mfma_split != 0, grid, st);
     return launch_wf<SISR_PRO_BNACT_BWD>(a, d->mfma_split != 0, grid, st);
 }
 
-static WTrunkF32Args wf_args(const SisrWgradDesc* d) {
-    WTrunkF32Args a{};
-    a.x1 = d->x1; a.g1 = d->g1; a.g2 = d->g2;
-    a.pa = d->pa; a.pd = d->pd; a.xslope_p = d->pro_slope_p; a.xslope = d->pro_slope;
-    a.qa = d->qa; a.qb = d->qb; a.qd = d->qd; a.qs = d->qs; a.qt = d->qt;
-    a.gslope_p = d->gpro_slope_p; a.gslope = d->gpro_slope;
-    a.slab = d->slab; a.bias_slab = d->bias_slab; a.slab_stride = d->slab_stride;
-    a.N = d->N; a.H = d->H; a.W = d->W;
-    a.tiles_x = d->W / WF_TW; a.per_img = (d->H / WF_TH) * a.tiles_x; a.total = d->N * a.per_img;
-    a.m_tiles_x = fdiv_magic(a.tiles_x); a.m_per_img = fdiv_magic(a.per_img);
-    a.xpro = d->pro_mode;
-    a.glog = d->Cout == 256 ? 2 : 0; a.cout_pad = d->Cout == 256 ? 256 : 64; a.gshuffle = d->g_mode == SISR_X_NHWC_UNSHUFFLE2 ? 1 : 0;
-    return a;
-}
-
 // ---- a batch of trunk layers (Cout = 64, one gradient-prologue kind, one mfma_split setting) --------------------------------------
 extern "C" int sisr_wgrad_trunk_f32_batch_arg_bytes(void) { return (int)sizeof(WTrunkF32Args); }
 
-static int wf_batch_check(const SisrWgradDesc* descs, int n) {
-    if (!descs || n <= 0 || n > 4096) return SISR_E_BADARG;
-    for (int i = 0; i < n; ++i) {
-        const SisrWgradDesc* d = descs + i;
-        if (!sisr_wgrad_trunk_f32_eligible(d) || d->Cout != 64 || d->gpro_mode != descs[0].gpro_mode) return SISR_E_BADARG;
-        if ((d->mfma_split != 0) != (descs[0].mfma_split != 0)) return SISR_E_BADARG;
-        if (!d->x1 || !d->g1 || !d->g2 || !d->slab || d->slab_stride < d->slab_elems) return SISR_E_BADARG;
-        if (d->pro_mode == SISR_PRO_AFFINE_ACT && (!d->pa || !d->pd)) return SISR_E_BADARG;
-        if (!d->qa || !d->qb || !d->qd || (d->gpro_mode == SISR_PRO_BNACT_BWD && (!d->qs || !d->qt))) return SISR_E_BADARG;
-    }
-    return 0;
-}
+static int wf_batch_check(const SisrWgradDesc* descs, int n) { return sisr_trunk_wgrad_batch_check(descs, n, sisr_wgrad_trunk_f32_eligible, true); }
 
 extern "C" int sisr_wgrad_trunk_f32_batch_args(const SisrWgradDesc* descs, int32_t n, void* args_host) {
-    if (!args_host) return SISR_E_BADARG;
-    if (int e = wf_batch_check(descs, n)) return e;
-    for (int i = 0; i < n; ++i) {
-        const WTrunkF32Args a = wf_args(descs + i);
-        std::memcpy(static_cast<unsigned char*>(args_host) + (size_t)i * sizeof(WTrunkF32Args), &a, sizeof(WTrunkF32Args));
-    }
-    return 0;
+    return sisr_trunk_wgrad_batch_args<WTrunkF32Args>(descs, n, args_host, wf_batch_check, wf_args);
 }
 
 template <int GPRO, bool SPLIT>

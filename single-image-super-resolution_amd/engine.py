@@ -101,6 +101,24 @@ class Kind(enum.IntEnum):
         return self in (Kind.DEEP, Kind.DEEP_S2X4)
 
 
+# the library's entry points per tensor family, keyed by Kind.bf16: every call site asks this table.  (The two families size the
+# BatchNorm-backward rows through different calls; the fp32 kernels' slabs are never bf16, so that family has no slab_lead.)
+Family = namedtuple('Family', 'conv parts bnb_parts trunk_eligible wgrad slabs slab_lead batch_arg_bytes batch_args batch')
+_FAMILY = {
+    False: Family('sisr_conv2d_f32', 'sisr_conv2d_f32_parts', 'sisr_conv2d_f32_bnb_parts', 'sisr_conv2d_trunk_f32_eligible',
+                  'sisr_conv2d_wgrad_f32', 'sisr_wgrad_f32_slabs', None,
+                  'sisr_wgrad_trunk_f32_batch_arg_bytes', 'sisr_wgrad_trunk_f32_batch_args', 'sisr_wgrad_trunk_f32_batch'),
+    True: Family('sisr_conv2d_bf16', 'sisr_conv2d_bf16_parts', 'sisr_conv2d_bf16_parts', 'sisr_conv2d_trunk_eligible',
+                 'sisr_conv2d_wgrad_bf16', 'sisr_wgrad_bf16_slabs', 'sisr_wgrad_bf16_slab_lead',
+                 'sisr_wgrad_trunk_batch_arg_bytes', 'sisr_wgrad_trunk_batch_args', 'sisr_wgrad_trunk_batch'),
+}
+
+
+def _entry(bf16, what):
+    """the library function behind entry point `what` (a field of Family) in the tensor family of a Kind.bf16"""
+    return getattr(L.lib(), getattr(_FAMILY[bool(bf16)], what))
+
+
 class Operand:
     """x1 (and x2) + prologue: see SISR_PRO_* in include/sisr_hip.h.  dims = logical (N,H,W,C)."""
     __slots__ = ('x1', 'x2', 'pa', 'pb', 'pd', 'ps', 'pt', 'mode', 'pro', 'slope', 'dims', 'x_out', 'fin')
@@ -646,13 +664,12 @@ def _bind(d, kind, prep, op, image, bias, res, out):
 
 
 def _launch_conv(d, kind, what):
-    name = 'sisr_conv2d_bf16' if kind.bf16 else 'sisr_conv2d_f32'
-    L.check(getattr(L.lib(), name)(C.byref(d), _stream()), '%s(%s)' % (name, what))
+    fn = _entry(kind.bf16, 'conv')
+    L.check(fn(C.byref(d), _stream()), '%s(%s)' % (fn.__name__, what))
 
 
 def conv_forward(prep, op, bias=None, y_mode=None, epi=L.EPI_NONE, stats=False, res=None, out=None):
     """Launch the forward conv of `prep` on lazy operand `op`.  Returns (y, stat_part, cnt_part)."""
-    lib = L.lib()
     f, kind = _copy_struct(prep.plans[0]), prep.kinds[0]
     gm = prep.ref.geom
     if y_mode is not None:
@@ -664,12 +681,11 @@ def conv_forward(prep, op, bias=None, y_mode=None, epi=L.EPI_NONE, stats=False, 
     f.epi_act = epi
     f.mfma_split = mfma_split()
     f.plan.variant = int(prep.lanes[0]) | (2 * prep.ldsimg[0])           # bit 0: lane-order bf16 image; bits 1-2: LDS-order fp32 image (mode)
-    trunk_eligible = lib.sisr_conv2d_trunk_eligible if kind.bf16 else lib.sisr_conv2d_trunk_f32_eligible
     fin = op.fin
     if fin is not None and not fin.done:
         # deferred BatchNorm finalisation: by this conv when it runs on a persistent trunk kernel, else stand-alone first
         fin.fill(f)
-        if _on('SISR_FUSE_BNFIN') and not kind.deep and trunk_eligible(C.byref(f)) == 1:
+        if _on('SISR_FUSE_BNFIN') and not kind.deep and _entry(kind.bf16, 'trunk_eligible')(C.byref(f)) == 1:
             fin.done = True
         else:
             f.fin_stat = None
@@ -680,7 +696,7 @@ def conv_forward(prep, op, bias=None, y_mode=None, epi=L.EPI_NONE, stats=False, 
         # count depends on which kernel takes the descriptor, and that depends on the fusions requested (the upscale
         # variant of the trunk kernel has no statistics epilogue): ask with the statistics pointers already non-null
         f.stat_part = f.cnt_part = f.y
-        rows = (lib.sisr_conv2d_bf16_parts if kind.bf16 else lib.sisr_conv2d_f32_parts)(C.byref(f))
+        rows = _entry(kind.bf16, 'parts')(C.byref(f))
         sp = torch.empty((rows, 2, gm.cout), dtype=torch.float32, device=dev)
         cp = torch.empty((rows,), dtype=torch.float32, device=dev)
         f.stat_part, f.cnt_part = sp.data_ptr(), cp.data_ptr()
@@ -696,11 +712,10 @@ def trunk_takes_skip_sum(prep, res, t):
     f = _copy_struct(prep.plans[0])
     if (f.N, f.H, f.W, f.Cin) != tuple(res.shape):
         return False
-    lib = L.lib()
     f.x1 = f.x2 = f.x_out = f.pa = f.pd = f.wpk = f.y = res.data_ptr()         # (non-null placeholders: eligibility only)
     f.pro_mode = L.PRO_RES_AFFINE
     f.x_bf16 = f.y_bf16 = _bf(res)
-    return (lib.sisr_conv2d_trunk_eligible if prep.kinds[0].bf16 else lib.sisr_conv2d_trunk_f32_eligible)(C.byref(f)) == 1
+    return _entry(prep.kinds[0].bf16, 'trunk_eligible')(C.byref(f)) == 1
 
 
 def can_fuse_bn_backward(prep):
@@ -712,11 +727,12 @@ def can_fuse_bn_backward(prep):
     if kind.deep:                                 # conv_deep.hip: any number of cout tiles
         return True
     if kind == Kind.F32:
-        # fp32 build: only the persistent trunk kernel (conv_trunk_f32.hip) has that epilogue; conv_dgrad() falls back
-        # to the plain launch (and returns no partial rows) when the filled descriptor turns out not to be eligible
-        gm = prep.ref.geom
-        return (gm.cin == 64 and gm.cout == 64 and gm.k == 3 and gm.stride == 1 and d.H % 8 == 0 and d.W % 16 == 0
-                and _on('SISR_TRUNK') and _on('SISR_TRUNK_F32CONV'))
+        # fp32 build: only the persistent trunk kernel (conv_trunk_f32.hip) has that epilogue: ask the library with a probe.
+        # conv_dgrad() falls back to the plain launch (and returns no partial rows) when the filled descriptor is not eligible
+        p = _copy_struct(d)
+        p.x1 = p.x2 = p.wpk = p.y = p.bnb_x = p.bnb_part = 1                        # (non-null placeholders: eligibility only)
+        p.pro_mode = L.PRO_BNBWD
+        return _entry(False, 'bnb_parts')(C.byref(p)) > 0
     return d.plan.variant == 0 and d.plan.CoutPad == d.plan.nsub * 32        # generic bf16 kernel: one cout tile
 
 
@@ -725,14 +741,13 @@ def _attach_bnb(descs, bnb, out):
     arriving at BatchNorm(x), bnb = (x, consts, slope | None).  -> the partial rows for bn_backward(part=...), one block of rows
     per descriptor in the order given -- or None where the kernel that takes the descriptor has no such epilogue (the fusion
     is taken back then)"""
-    lib = L.lib()
     x, consts, slope = bnb
     assert tuple(x.shape) == tuple(out.shape)
     rows = []
     for d, kind in descs:
         d.bnb_x, d.bnbx_bf16 = x.data_ptr(), _bf(x)
         d.bnb_part = d.y                            # (any non-null value: the row count depends on the fusions requested)
-        rows.append((lib.sisr_conv2d_bf16_parts if kind.bf16 else lib.sisr_conv2d_f32_bnb_parts)(C.byref(d)))
+        rows.append(_entry(kind.bf16, 'bnb_parts')(C.byref(d)))
     if sum(rows) <= 0:                              # fp32 build, descriptor not taken by the persistent kernel: no fusion
         for d, _ in descs:
             d.bnb_x, d.bnb_part = None, None
@@ -847,6 +862,15 @@ class PendingSlabs:
                                                C.addressof(leads), n, _stream()), 'sisr_slab_reduce_multi')
 
 
+def _bind_slabs(g, n_slabs, dev, bf16):
+    """the [n_slabs, slab_stride] slab tensor of weight-gradient descriptor g, bound to it (a row: one workgroup's gradient part, then
+    its bias row) -> (slab, leading elements of every row that the launch of g stores as bf16: the persistent and the deep bf16 kernels)"""
+    slab = torch.empty((n_slabs, g.slab_stride), dtype=torch.float32, device=dev)
+    g.slab = slab.data_ptr()
+    g.bias_slab = slab.data_ptr() + 4 * g.slab_elems
+    return slab, int(_entry(True, 'slab_lead')(C.byref(g))) if bf16 else 0
+
+
 def conv_wgrad(prep, x_op, dy_op, defer=None):
     """Weight + bias gradient in packed layout: returns the reduced [slab_elems + CoutPad] buffer.
     defer (PendingSlabs or None): leave the slab reduction to a later launch (see PendingSlabs)."""
@@ -874,15 +898,12 @@ def conv_wgrad(prep, x_op, dy_op, defer=None):
     x_op.fill(g)
     dy_op.fill(g, g=True)
     g.mfma_split = mfma_split()
-    n_slabs = (lib.sisr_wgrad_bf16_slabs if bf16 else lib.sisr_wgrad_f32_slabs)(C.byref(g))
+    n_slabs = _entry(bf16, 'slabs')(C.byref(g))
     if bf16 and g.deep.enabled and lib.sisr_wgrad_deep_eligible(C.byref(g)):
         _count('wgrad_deep')
-    lead = int(lib.sisr_wgrad_bf16_slab_lead(C.byref(g))) if bf16 else 0     # the persistent bf16 kernel's slabs are bf16
-    slab = torch.empty((n_slabs, stride), dtype=torch.float32, device=dev)
-    g.slab = slab.data_ptr()
-    g.bias_slab = slab.data_ptr() + 4 * g.slab_elems
-    name = 'sisr_conv2d_wgrad_bf16' if bf16 else 'sisr_conv2d_wgrad_f32'
-    L.check(getattr(lib, name)(C.byref(g), _stream()), name)
+    slab, lead = _bind_slabs(g, n_slabs, dev, bf16)
+    fn = _entry(bf16, 'wgrad')
+    L.check(fn(C.byref(g), _stream()), fn.__name__)
     red = torch.empty((stride,), dtype=torch.float32, device=dev)
     if defer is not None and _on('SISR_FUSE_SLABRED'):
         defer.jobs.append((slab, red, n_slabs, stride, lead))
@@ -977,11 +998,8 @@ class WgradDeepBatch:
                 n_slabs = g.deep.n_pb
                 g.deep.batch_first_wg = first_wg
                 first_wg += g.deep.n_cib * g.deep.n_cob * n_slabs
-                slab = torch.empty((n_slabs, g.slab_stride), dtype=torch.float32, device=red.device)
-                g.slab = slab.data_ptr()
-                g.bias_slab = slab.data_ptr() + 4 * g.slab_elems
+                slab, lead = _bind_slabs(g, n_slabs, red.device, True)
                 table[i] = g
-                lead = int(lib.sisr_wgrad_bf16_slab_lead(C.byref(g)))
                 pending.jobs.append((slab, red, n_slabs, g.slab_stride, lead))
             dev = _table_to_device(table, group[0][4].device)
             L.check(lib.sisr_wgrad_deep_batch(table, dev.data_ptr(), len(group), _stream()), 'sisr_wgrad_deep_batch')
@@ -991,32 +1009,25 @@ class WgradDeepBatch:
     def _run_trunk(self, pending):
         if not self.trunk:
             return
-        lib = L.lib()
         items, self.trunk = self.trunk, []
         groups = {}
         for it in items:
             groups.setdefault(_trunk_batch_key(it[0], it[1]), []).append(it)
         for (is_bf16, _), group in groups.items():
             n = len(group)
-            f_bytes, f_args, f_run, f_lead = ((lib.sisr_wgrad_trunk_batch_arg_bytes, lib.sisr_wgrad_trunk_batch_args, lib.sisr_wgrad_trunk_batch,
-                                               lambda gg: int(lib.sisr_wgrad_bf16_slab_lead(C.byref(gg)))) if is_bf16 else
-                                              (lib.sisr_wgrad_trunk_f32_batch_arg_bytes, lib.sisr_wgrad_trunk_f32_batch_args,
-                                               lib.sisr_wgrad_trunk_f32_batch, lambda gg: 0))
-            nbytes = f_bytes()
             # 256 workgroup slots over the layers: every workgroup walks its share of ONE layer's tiles back to back (17 layers of 1,152
             # tiles: 15 workgroups x 77; alone, a layer is 231 workgroups x 5 with a tenth of the chip idle)
             wpl = max(1, min(256 // n, 231))
             table = (L.WgradDesc * n)()
             for i, (prep, g, x_op, dy_op, red) in enumerate(group):
-                slab = torch.empty((wpl, g.slab_stride), dtype=torch.float32, device=red.device)
-                g.slab = slab.data_ptr()
-                g.bias_slab = slab.data_ptr() + 4 * g.slab_elems
+                slab, lead = _bind_slabs(g, wpl, red.device, is_bf16)
                 table[i] = g
-                pending.jobs.append((slab, red, wpl, g.slab_stride, f_lead(g)))
-            args = (C.c_char * (n * nbytes))()
-            L.check(f_args(table, n, C.addressof(args)), 'sisr_wgrad_trunk(_f32)_batch_args')
+                pending.jobs.append((slab, red, wpl, g.slab_stride, lead))
+            args = (C.c_char * (n * _entry(is_bf16, 'batch_arg_bytes')()))()
+            f_args, f_run = _entry(is_bf16, 'batch_args'), _entry(is_bf16, 'batch')
+            L.check(f_args(table, n, C.addressof(args)), f_args.__name__)
             dev = _table_to_device(args, group[0][4].device)
-            L.check(f_run(table, dev.data_ptr(), n, wpl, _stream()), 'sisr_wgrad_trunk(_f32)_batch')
+            L.check(f_run(table, dev.data_ptr(), n, wpl, _stream()), f_run.__name__)
             _count('wgrad_trunk_batch')
 
 
