@@ -22,14 +22,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_helpers import pkg
+from gpu_helpers import BF16, F32, GUARD, SENT, Buf, _bits, assert_within, pkg, run2
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
-SENT = -1536.0                      # exact in fp32 and bf16, never produced by the seeded inputs
-GUARD = 64                          # elements on each side (keeps the body 128-byte aligned in both formats)
-F32, BF16 = torch.float32, torch.bfloat16
 DT = {0: F32, 1: BF16}
 BADARG, UNSUPPORTED = -1, -3
 
@@ -47,67 +44,12 @@ def _gen(seed):
     return torch.Generator().manual_seed(seed)
 
 
-def _bits(t):
-    return t.view(torch.int32 if t.dtype == F32 else torch.int16)
-
-
-class Buf:
-    """an output of `numel` elements between two sentinel guards; `fill`: what the body holds before every launch"""
-
-    def __init__(self, numel, dtype=F32, fill=SENT):
-        self.numel, self.fill = numel, fill
-        self.whole = torch.empty(numel + 2 * GUARD, dtype=dtype, device='cuda')
-        self.body = self.whole[GUARD:GUARD + numel]
-        self.reset()
-
-    def reset(self):
-        self.whole.fill_(SENT)
-        if self.fill != SENT:
-            self.body.fill_(self.fill)
-
-    def ptr(self, offset=0):
-        return self.body.data_ptr() + offset * self.body.element_size()
-
-    def guards_intact(self):
-        lo, hi = self.whole[:GUARD], self.whole[GUARD + self.numel:]
-        return bool((lo == SENT).all()) and bool((hi == SENT).all())
-
-    def cpu(self):
-        return self.body.cpu()
-
-
-def run2(call, outs):
-    """launch twice from the same pre-fill: status 0, guards intact, identical bits; leaves the second run's results in place"""
-    first = None
-    for rep in range(2):
-        for o in outs:
-            o.reset()
-        status = call()
-        torch.cuda.synchronize()
-        assert status == 0, status
-        for k, o in enumerate(outs):
-            assert o.guards_intact(), 'guard of output %d changed' % k
-        if rep == 0:
-            first = [o.body.clone() for o in outs]
-    for a, o in zip(first, outs):
-        assert torch.equal(_bits(a), _bits(o.body)), 'two runs differ'
-
-
 def dev(t, dtype=F32):
     return t.to(dtype).contiguous().cuda()
 
 
 def lrelu64(v, slope):
     return torch.where(v > 0, v, v * float(np.float32(slope)))
-
-
-def assert_within(got, ref64, bound, what=''):
-    """element by element; prints the worst ratio before asserting"""
-    err = (got.double() - ref64).abs()
-    ratio = float((err / bound.clamp_min(1e-300)).max()) if err.numel() else 0.0
-    worst = float(err.max()) if err.numel() else 0.0
-    print('%s: max err %.3e, max err/bound %.3f' % (what, worst, ratio))
-    assert bool((err <= bound).all()), (what, worst, ratio)
 
 
 # ---- transposes ---------------------------------------------------------------------------------------------------------------
