@@ -18,7 +18,9 @@
 //     lane half kk multiplies channels 16 kk + s at step s, so its 16 A values (and its 16 B values) are four
 //     ds_read_b128 instead of sixteen ds_read_b32 -- a quarter of the LDS instructions per MFMA;
 //   * 1152 pixel tiles x 2 cout halves = exactly 9 units per CU at the benchmark size (no partial round);
-//   * role-specific loops with matching barrier counts (see conv_trunk.hip).
+//   * role-specific loops with matching barrier counts (see conv_trunk.hip): the producers' per stage, the consumers' per tile
+//     with its two stages as straight-line code, tile coordinates advanced incrementally, and the epilogue's addresses as one
+//     lane register + the instruction's scalar offset and immediate.
 // The two workgroups of a cout pair walk the same pixel tiles and share one statistics row: each writes its 32 channels.
 #include "sisr_dev.h"
 #include "sisr_bf16_stage.h"
@@ -357,7 +359,7 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
         const __amdgpu_buffer_rsrc_t ry = cf_rsrc(a.y, a.shuffle ? 4u * tbytes : tbytes), rr = cf_rsrc(a.res != nullptr ? a.res : a.y, tbytes);
         f32x16 acc;
         f32x16 rv, xv;                                        // residual / BatchNorm-input values of the tile (requested a stage early)
-        const bool has_x = a.bnb_part != nullptr;
+        const bool has_x = (PRO == SISR_PRO_BNBWD || PRO == SISR_PRO_BNACT_BWD) && a.bnb_part != nullptr;
         const __amdgpu_buffer_rsrc_t rxb = cf_rsrc(has_x ? a.bnb_x : a.y, tbytes);
         float b_sc = 0.f, b_sf = 0.f, b_mu = 0.f, b_is = 0.f, b_slope = 1.f;
         float rs1 = 0.f, rs2 = 0.f, rsl = 0.f;                // running sums of this lane's channel: g, g * xhat, slope term
@@ -368,38 +370,30 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
         fill_weights();
         __syncthreads();
         __syncthreads();
-        for (int j = 0; j < n_stages; ++j) {
-            const int q = j & 1;
-            CFT(4 + 6 * j);
-            int n, ty, tx;
-            tile_coords(stream + (j >> 1) * a.streams, n, ty, tx);
-            // (shuffled store: pixel (y, x) of phase (i, j) lands on (2 y + i, 2 x + j) of the [N][2H][2W][64] tensor)
-            const unsigned obase = a.shuffle ? (unsigned)((((n * 2 * a.H + 2 * (ty * CF_TH + 2 * wave) + (ph >> 1)) * 2 * a.W + 2 * tx * CF_TW + (ph & 1)) * 64 + co) * 4)
-                                             : (unsigned)((((n * a.H + ty * CF_TH + 2 * wave) * a.W + tx * CF_TW) * 64 + co) * 4);
-            const int orow = a.shuffle ? 4 * a.W * 256 : a.W * 256, ocol = a.shuffle ? 512 : 256;       // bytes per tile row / column of the store
-            if (q == 0) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[i] = bv;
-            } else {
-                // the skip gradient and the BatchNorm input of this tile, in accumulator layout: in flight behind the second
-                // half's MFMAs
-                if (a.res != nullptr) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int p = mfma_row(i, lane);
-                        rv[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, obase + (unsigned)(((p >> 4) * a.W + (p & 15)) * 256), 0, 0));
-                    }
-                }
-                if (has_x) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int p = mfma_row(i, lane);
-                        xv[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxb, obase + (unsigned)(((p >> 4) * a.W + (p & 15)) * 256), 0, 0));
-                    }
-                }
-            }
-            const unsigned char* ab = halo0 + (j & 1) * CF_HALO_BYTES + abase;
-            const unsigned char* bb = lds + q * CF_WCHUNK_BYTES + bbase;
+        // what the epilogue does is fixed for the launch -- by the role where the descriptor leaves no choice (the forward role has no
+        // skip gradient and no BatchNorm-backward rows; the data-gradient roles no statistics and no PixelShuffle store),
+        // by a wave-uniform flag otherwise: decided here, not at every stage
+        constexpr bool BWD = TWO && !SUM;
+        const bool has_res = BWD && a.res != nullptr;
+        const bool x_act = has_x && a.bnb_act != 0;
+        const bool do_stat = !BWD && a.stat_part != nullptr;
+        const bool shuf = !TWO && a.shuffle != 0;
+        // addresses of the tile's values in accumulator layout (register i of a lane = pixel row i >> 3, column
+        // 8 ((i >> 2) & 1) + 4 kk + (i & 3) of the wave's two tile rows): the lane's part (channel, 4 kk columns) is one register
+        // for the whole launch, the tile's and the register's part is wave-uniform -- scalar offset + immediate of the instruction
+        const int vl_plain = co * 4 + kk * 4 * 256, vl_shuf = co * 4 + kk * 4 * 512;
+        // this workgroup's tiles: stream, stream + streams, ..: (n, ty, tx) advance by a fixed (dn, dty, dtx) with carries
+        const int tiles_y = fdiv(a.per_img, a.m_tiles_x);
+        const int dn = fdiv(a.streams, a.m_per_img), drem = a.streams - dn * a.per_img;
+        const int dty = fdiv(drem, a.m_tiles_x), dtx = drem - dty * a.tiles_x;
+        int n, ty, tx;
+        tile_coords(stream, n, ty, tx);
+        // the MFMAs of stage (tile, Q): halo buffer Q, weight chunk Q.  The first operand reads go out at once, `mid` (what else the
+        // stage has to start: the accumulator's initial value, the loads of the epilogue's operands) behind them
+        auto mma = [&](auto q_c, auto&& mid) {
+            constexpr int Q = decltype(q_c)::value;
+            const unsigned char* ab = halo0 + Q * CF_HALO_BYTES + abase;
+            const unsigned char* bb = lds + Q * CF_WCHUNK_BYTES + bbase;
             // software pipeline over the 18 half-taps (8 MFMAs each): the operands of half-tap u + 2 are requested before the
             // MFMAs of half-tap u, so a whole half-tap (512 cycles) of reads is always in flight (left alone the compiler
             // requests a pair of operands right before the MFMAs that need them; groups of 8 reads keep the wait expressible in
@@ -420,6 +414,7 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
                 };
                 fetch_s(0);
                 fetch_s(1);
+                mid();
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int t = 0; t < 9; ++t) {
@@ -433,81 +428,136 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
                     __builtin_amdgcn_sched_barrier(0);
                 }
             } else {
-            f32x4 af[18][2], bf[18][2];                     // half-tap u: steps s0 .. s0 + 7 = two 16-byte reads per operand
-            // (one accumulation chain: a second one over the odd K steps, folded in before the epilogue, was tried and not kept; so
-            // was a raised wave priority for the producers)
-            auto fetch = [&](int u) {
-                const int t = u >> 1, s0 = 8 * (u & 1);
+                f32x4 af[18][2], bf[18][2];                     // half-tap u: steps s0 .. s0 + 7 = two 16-byte reads per operand
+                // (one accumulation chain: a second one over the odd K steps, folded in before the epilogue, was tried and not kept; so
+                // was a raised wave priority for the producers)
+                auto fetch = [&](int u) {
+                    const int t = u >> 1, s0 = 8 * (u & 1);
 #pragma unroll
-                for (int v = 0; v < 2; ++v) {
-                    af[u][v] = *reinterpret_cast<const f32x4*>(ab + (((t / 3) * CF_IW + (t % 3)) * CF_PSF + s0 + 4 * v) * 4);
-                    bf[u][v] = *reinterpret_cast<const f32x4*>(bb + ((t * 32) * CF_WROW + s0 + 4 * v) * 4);
-                }
-            };
-            fetch(0);
-            fetch(1);
-            __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-#pragma unroll
-            for (int u = 0; u < 18; ++u) {
-                if (u + 2 < 18) fetch(u + 2);
-#pragma unroll
-                for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u][s >> 2][s & 3], bf[u][s >> 2][s & 3], acc, 0, 0, 0);
-                if (u + 2 < 18) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-            }
-            }
-            CFT(6 + 6 * j);
-            if (q == 1) {
-                // ---- epilogue of the tile: skip gradient, statistics, stores (128 contiguous bytes per pixel and half wave) ---
-                if (a.res != nullptr) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) acc[i] += rv[i];
-                }
-                if (has_x) {                                           // (two straight-line versions, not a branch per element)
-                    if (a.bnb_act) {
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            float gv = acc[i];
-                            const float z = b_sc * xv[i] + b_sf;
-                            const bool neg = !(z > 0.f);
-                            rsl += neg ? gv * z : 0.f;
-                            gv = neg ? gv * b_slope : gv;
-                            rs1 += gv;
-                            rs2 += gv * ((xv[i] - b_mu) * b_is);
-                        }
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            rs1 += acc[i];
-                            rs2 += acc[i] * ((xv[i] - b_mu) * b_is);
-                        }
+                    for (int v = 0; v < 2; ++v) {
+                        af[u][v] = *reinterpret_cast<const f32x4*>(ab + (((t / 3) * CF_IW + (t % 3)) * CF_PSF + s0 + 4 * v) * 4);
+                        bf[u][v] = *reinterpret_cast<const f32x4*>(bb + ((t * 32) * CF_WROW + s0 + 4 * v) * 4);
                     }
-                }
-                if (a.stat_part != nullptr) {
-                    if (st_n == 0) {                                    // shift = mean of the first tile's values of this lane
-                        float s = 0.f;
+                };
+                fetch(0);
+                fetch(1);
+                __builtin_amdgcn_sched_barrier(0);
+                mid();
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                        for (int i = 0; i < 16; ++i) s += acc[i];
-                        st_shift = s * (1.f / 16.f);
-                    }
+                for (int u = 0; u < 18; ++u) {
+                    if (u + 2 < 18) fetch(u + 2);
+#pragma unroll
+                    for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u][s >> 2][s & 3], bf[u][s >> 2][s & 3], acc, 0, 0, 0);
+                    if (u + 2 < 18) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+                }
+            }
+        };
+        // the tile's 16 values per lane, from / to a tensor whose tile column is OCOL bytes and whose tile row is `orow` bytes on,
+        // tile origin (this wave's rows) at byte `sb`: no address arithmetic between the instructions
+        auto each_value = [&](auto ocol_c, unsigned sb, int orow, auto&& f) {
+            constexpr int OCOL = decltype(ocol_c)::value;
+            constexpr bool FAR = 11 * OCOL > 4095;             // column 8 .. 11 does not fit the 12-bit immediate: a scalar offset of its own
+            const unsigned s0 = sb, s1 = sb + (unsigned)orow, s0f = s0 + 8u * OCOL, s1f = s1 + 8u * OCOL;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const bool hi = (i >> 2) & 1;
+                const unsigned so = (i >> 3) ? (FAR && hi ? s1f : s1) : (FAR && hi ? s0f : s0);
+                f(i, (unsigned)(((FAR ? 0 : 8 * hi) + (i & 3)) * OCOL), so);
+            }
+        };
+        using OcolPlain = std::integral_constant<int, 256>;
+        using OcolShuf = std::integral_constant<int, 512>;
+        for (int t = 0; t < n_mine; ++t) {
+            const unsigned sb = (unsigned)(((n * a.H + ty * CF_TH + 2 * wave) * a.W + tx * CF_TW) * 256);
+            // (opaque per tile: lane part + constant stays an instruction's immediate, not sixteen registers computed ahead of the loop)
+            int vlp = vl_plain, vls = vl_shuf;
+            asm volatile("" : "+v"(vlp), "+v"(vls));
+            // ---- first channel half ---------------------------------------------------------------------------------------------
+            CFT(4 + 12 * t);
+            mma(std::integral_constant<int, 0>{}, [&]() {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] = bv;
+            });
+            CFT(6 + 12 * t);
+            CFT(8 + 12 * t);
+            __syncthreads();
+            CFT(9 + 12 * t);
+            // ---- second channel half: the skip gradient and the BatchNorm input of this tile, in accumulator layout, are in flight
+            // behind its MFMAs ----------------------------------------------------------------------------------------------------
+            CFT(10 + 12 * t);
+            mma(std::integral_constant<int, 1>{}, [&]() {
+                if (has_res)
+                    each_value(OcolPlain{}, sb, a.W * 256, [&](int i, unsigned imm, unsigned so) {
+                        rv[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, (unsigned)vlp + imm, so, 0));
+                    });
+                if (has_x)
+                    each_value(OcolPlain{}, sb, a.W * 256, [&](int i, unsigned imm, unsigned so) {
+                        xv[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxb, (unsigned)vlp + imm, so, 0));
+                    });
+            });
+            CFT(12 + 12 * t);
+            // ---- epilogue of the tile: skip gradient, statistics, stores (128 contiguous bytes per pixel and half wave) ---------------
+            if (has_res) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] += rv[i];
+            }
+            if (has_x) {                                           // (two straight-line versions, not a branch per element)
+                if (x_act) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        const float dv = acc[i] - st_shift;
-                        st_s1 += dv;
-                        st_s2 += dv * dv;
+                        float gv = acc[i];
+                        const float z = b_sc * xv[i] + b_sf;
+                        const bool neg = !(z > 0.f);
+                        rsl += neg ? gv * z : 0.f;
+                        gv = neg ? gv * b_slope : gv;
+                        rs1 += gv;
+                        rs2 += gv * ((xv[i] - b_mu) * b_is);
                     }
-                    st_n += 16;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        rs1 += acc[i];
+                        rs2 += acc[i] * ((xv[i] - b_mu) * b_is);
+                    }
+                }
+            }
+            if (do_stat) {
+                if (st_n == 0) {                                    // shift = mean of the first tile's values of this lane
+                    float s = 0.f;
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) s += acc[i];
+                    st_shift = s * (1.f / 16.f);
                 }
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int p = mfma_row(i, lane);
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)acc[i]), ry,
-                                                          obase + (unsigned)((p >> 4) * orow + (p & 15) * ocol), 0, 0);
+                    const float dv = acc[i] - st_shift;
+                    st_s1 += dv;
+                    st_s2 += dv * dv;
                 }
+                st_n += 16;
             }
-            CFT(8 + 6 * j);
+            if (shuf) {
+                // (shuffled store: pixel (y, x) of phase (i, j) lands on (2 y + i, 2 x + j) of the [N][2H][2W][64] tensor)
+                const unsigned sbs = (unsigned)(((n * 2 * a.H + 2 * (ty * CF_TH + 2 * wave) + (ph >> 1)) * 2 * a.W + 2 * tx * CF_TW + (ph & 1)) * 256);
+                each_value(OcolShuf{}, sbs, 4 * a.W * 256, [&](int i, unsigned imm, unsigned so) {
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)acc[i]), ry, (unsigned)vls + imm, so, 0);
+                });
+            } else {
+                each_value(OcolPlain{}, sb, a.W * 256, [&](int i, unsigned imm, unsigned so) {
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)acc[i]), ry, (unsigned)vlp + imm, so, 0);
+                });
+            }
+            CFT(14 + 12 * t);
             __syncthreads();
-            CFT(9 + 6 * j);
+            CFT(15 + 12 * t);
+            // the next tile of this stream
+            tx += dtx;
+            if (tx >= a.tiles_x) { tx -= a.tiles_x; ++ty; }
+            ty += dty;
+            if (ty >= tiles_y) { ty -= tiles_y; ++n; }
+            n += dn;
         }
         CFT(3);
 
