@@ -563,6 +563,34 @@ int sisr_bicubic_fwd(const float *x, float *y, int32_t NC, int32_t H, int32_t W,
 int sisr_bicubic_bwd(const float *dy, const float *y_clamped, float *dx, int32_t NC, int32_t H,
                      int32_t W, int32_t Ho, int32_t Wo, void *stream);
 
+/* ---- device-resident patch source: the decoded dataset [M][H0][W0][C] uint8 lives in device memory and
+ *      every batch is sampled from it there: image, crop window and flips / transposition per sample.  Random numbers:
+ *      Philox4x32-10 (Salmon et al., SC'11) with key = (seed low, seed high) and counter = (t low, t high, b, rank) for step t,
+ *      sample b of the batch and data-parallel rank `rank`.  From its four words r0..r3, with mulhi32(a, n) = (a * n) >> 32:
+ *          index = mulhi32(r0, M)   y0 = mulhi32(r1, H0 - h + 1)   x0 = mulhi32(r2, W0 - w + 1)   ops = r3 & ops_mask
+ *      (no rejection loop: a value's probability is off by at most range / 2^32).  ops bit 0: horizontal flip, bit 1: vertical
+ *      flip, bit 2: transposition (h == w only), applied in that order.  order 0 = random (i.i.d. with replacement) as above;
+ *      order 1 = sequential, the reference's sampler with drop_last: index = ((t mod nb) * world + rank) * B + b with
+ *      nb = M / (B * world), offsets and ops still drawn.
+ *      SISR_E_BADARG before any HIP call for null pointers, sizes < 1, a window larger than the image, rank outside [0, world),
+ *      ops_mask outside [0, 7] or with bit 2 while h != w, an unknown order and sequential order with nb == 0. ------------- */
+/* One workgroup: t = *step_dev; draws_dev[b] = { index, y0, x0, ops } for every b < B; *step_dev = t + 1 (an ordinary store by
+ * one thread behind a barrier).  The count lives in device memory, so a captured launch advances on every replay. */
+int sisr_patch_draw(int64_t *step_dev, uint64_t seed, int32_t rank, int32_t world, int32_t order, int32_t B, int32_t M,
+                    int32_t H0, int32_t W0, int32_t h, int32_t w, int32_t ops_mask,
+                    int32_t *draws_dev /* [B][4]: index, y0, x0, ops */, void *stream);
+/* HOST: the same arithmetic (one __host__ __device__ function) for step t >= 0 into host memory; no GPU involved */
+int sisr_patch_draws_host(int64_t t, uint64_t seed, int32_t rank, int32_t world, int32_t order, int32_t B, int32_t M,
+                          int32_t H0, int32_t W0, int32_t h, int32_t w, int32_t ops_mask, int32_t *draws_host);
+/* Sample b = data[index, y0 : y0 + h, x0 : x0 + w, :] after hflip, vflip, transposition as its row of draws_dev says.
+ * dst_kind 0: [B][C][h][w] fp32, ((float)u8 / 255.0f - mean) / stdv (ToTensor + Normalize, the expressions of
+ * sisr_resize_u8_normalize); dst_kind 1: [B][h][w][C] uint8 (that entry point's input layout).  1 <= C <= 4.  The kernel clamps
+ * index, y0, x0 into range and ignores bit 2 while h != w, so no table can make it touch memory outside data / dst.  One
+ * workgroup per 32 x 32 window tile and sample, staged through LDS so that global reads and writes are both coalesced for all
+ * eight operations.  SISR_E_TOOBIG for B or h / 32 above 65535. */
+int sisr_patch_gather(const unsigned char *data, int32_t M, int32_t H0, int32_t W0, int32_t C, const int32_t *draws_dev,
+                      int32_t B, int32_t h, int32_t w, float mean, float stdv, void *dst, int32_t dst_kind, void *stream);
+
 /* ---- image-quality metrics: per-image PSNR and SSIM of two NCHW fp32 batches (the reference reports neither: its to-do list,
  *      README.md:88).  View applied on load: `crop` pixels stripped from every side; C == 3 with luma != 0: the BT.601 full-range
  *      plane Y = 0.299 R + 0.587 G + 0.114 B instead of the three planes.  PSNR = 10 log10(data_range^2 / mse), +inf for equal

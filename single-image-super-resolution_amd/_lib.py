@@ -194,6 +194,9 @@ _SIGS = {
     'sisr_fc_wgrad_rows': [_f, _f, _f32, _f, _i32, _i32, _i32, _f],
     'sisr_resize_coeffs': [_i32, _i32, _f, _f],
     'sisr_resize_u8_normalize': [_f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f, _i32, _f, _f, _i32, _f32, _f32, _f],
+    'sisr_patch_draw': [_f, C.c_uint64] + [_i32] * 10 + [_f, _f],
+    'sisr_patch_draws_host': [_i64, C.c_uint64] + [_i32] * 10 + [_f],
+    'sisr_patch_gather': [_f, _i32, _i32, _i32, _i32, _f, _i32, _i32, _i32, _f32, _f32, _f, _i32, _f],
     'sisr_bicubic_fwd': [_f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _f],
     'sisr_bicubic_bwd': [_f, _f, _f, _i32, _i32, _i32, _i32, _i32, _f],
     'sisr_image_metrics_ws_floats': [_i32, _i32, _i32, _i32, _i32, _i32],

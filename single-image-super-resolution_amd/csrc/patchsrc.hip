@@ -1,0 +1,175 @@
+// patchsrc.hip -- device-resident patch source: the decoded dataset [M][H0][W0][C] uint8 stays in HBM and
+// every iteration's batch is sampled from it on the device -- which image, which crop window, which of the eight flips /
+// transpositions -- so a captured iteration needs no host gather and no host-to-device copy.
+//   patch_draw_kernel    one workgroup: step count t (device memory) -> draw table [B][4] = { index, y0, x0, ops }, t -> t + 1;
+//   patch_gather_kernel  one workgroup per 32 x 32 window tile and sample: rows of the window -> LDS -> the flipped / transposed
+//                        tile of the destination, normalised fp32 NCHW (ToTensor + Normalize) or uint8 NHWC.
+// The random numbers are Philox4x32-10 (Salmon et al., SC'11) keyed by the seed and counted by (t, b, rank): one text for host
+// and device (sisr_patch_draws_host is the same arithmetic without a GPU).  No atomics, plain vector stores, nothing read back.
+#include "sisr_dev.h"
+
+#include <algorithm>
+
+// ---- Philox4x32-10 -------------------------------------------------------------------------------------------------------------
+__host__ __device__ __forceinline__ uint32_t patch_mulhi32(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
+
+__host__ __device__ __forceinline__ void philox4x32_10(const uint32_t ctr[4], uint32_t k0, uint32_t k1, uint32_t out[4]) {
+    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3];
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = patch_mulhi32(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = patch_mulhi32(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+#define PATCH_ORDER_RANDOM 0
+#define PATCH_ORDER_SEQUENTIAL 1
+
+struct PatchDrawArgs {
+    uint64_t seed;
+    int rank, world, order, B, M, H0, W0, h, w, ops_mask;
+};
+
+// row b of the draw table of step t.  Multiply-high maps a 32-bit word onto [0, range): no rejection loop, bias <= range / 2^32
+__host__ __device__ __forceinline__ void patch_draw_row(const PatchDrawArgs& a, int64_t t, int b, int32_t* row) {
+    const uint32_t ctr[4] = {(uint32_t)((uint64_t)t & 0xFFFFFFFFu), (uint32_t)((uint64_t)t >> 32), (uint32_t)b, (uint32_t)a.rank};
+    uint32_t r[4];
+    philox4x32_10(ctr, (uint32_t)(a.seed & 0xFFFFFFFFu), (uint32_t)(a.seed >> 32), r);
+    int32_t index;
+    if (a.order == PATCH_ORDER_SEQUENTIAL) {       // SamplerRange(0, M) with drop_last, restarting each epoch
+        const int64_t nb = (int64_t)a.M / ((int64_t)a.B * a.world);
+        index = (int32_t)(((t % nb) * a.world + a.rank) * a.B + b);
+    } else {
+        index = (int32_t)patch_mulhi32(r[0], (uint32_t)a.M);
+    }
+    row[0] = index;
+    row[1] = (int32_t)patch_mulhi32(r[1], (uint32_t)(a.H0 - a.h + 1));
+    row[2] = (int32_t)patch_mulhi32(r[2], (uint32_t)(a.W0 - a.w + 1));
+    row[3] = (int32_t)(r[3] & (uint32_t)a.ops_mask);
+}
+
+static bool patch_draw_args_ok(const PatchDrawArgs& a) {
+    if (a.B <= 0 || a.M <= 0 || a.H0 <= 0 || a.W0 <= 0 || a.h <= 0 || a.w <= 0 || a.h > a.H0 || a.w > a.W0) return false;
+    if (a.world <= 0 || a.rank < 0 || a.rank >= a.world) return false;
+    if (a.ops_mask < 0 || a.ops_mask > 7 || ((a.ops_mask & 4) && a.h != a.w)) return false;
+    if (a.order == PATCH_ORDER_SEQUENTIAL) return (int64_t)a.M / ((int64_t)a.B * a.world) >= 1;      // an epoch of no batch: refused
+    return a.order == PATCH_ORDER_RANDOM;
+}
+
+// One workgroup.  Every thread reads the count before the barrier, one thread stores count + 1 behind it: the only code that
+// touches the count, so a captured draw advances on every replay (as ema_prepare_kernel, optim.hip).
+__global__ void __launch_bounds__(SISR_BLOCK) patch_draw_kernel(int64_t* __restrict__ step, PatchDrawArgs a, int32_t* __restrict__ draws) {
+    const int64_t t = *step;
+    __syncthreads();
+    if (threadIdx.x == 0) *step = t + 1;
+    for (int b = threadIdx.x; b < a.B; b += SISR_BLOCK) {
+        int32_t row[4];
+        patch_draw_row(a, t, b, row);
+        draws[4 * b + 0] = row[0]; draws[4 * b + 1] = row[1]; draws[4 * b + 2] = row[2]; draws[4 * b + 3] = row[3];
+    }
+}
+
+// ---- gather ----------------------------------------------------------------------------------------------------------------------
+// Tile: PG_T x PG_T window pixels.  A window row is w * C contiguous bytes at an arbitrary byte offset and the destination is
+// planar, so neither side can be both read and written in its own order by one thread mapping: the tile's rows are copied to LDS
+// byte for byte (consecutive lanes on consecutive source bytes) and read back in DESTINATION order (consecutive lanes on
+// consecutive destination elements), whichever of the eight operations applies.  LDS pitch PG_PITCH = 132 bytes = 33 dwords: a
+// transposed read walks DOWN a tile column, one row per lane, and 33 is odd, so the 32 lanes of a half-wave fall on 32 different
+// banks; an untransposed read walks along a row (stride C bytes: lanes share dwords or take neighbouring ones).
+#define PG_T 32
+#define PG_PITCH (PG_T * 4 + 4)
+
+template <int KIND>
+__global__ void __launch_bounds__(SISR_BLOCK) patch_gather_kernel(const unsigned char* __restrict__ data, int M, int H0, int W0, int C,
+                                                                   const int32_t* __restrict__ draws, int h, int w, float mean,
+                                                                   float stdv, void* __restrict__ dst) {
+    __shared__ unsigned char tile[PG_T * PG_PITCH];
+    const int b = blockIdx.z;
+    // a table can never make the kernel read outside `data` or write outside `dst`: every entry is clamped into range
+    const int index = min(max(draws[4 * b + 0], 0), M - 1);
+    const int y0 = min(max(draws[4 * b + 1], 0), H0 - h);
+    const int x0 = min(max(draws[4 * b + 2], 0), W0 - w);
+    int ops = draws[4 * b + 3] & 7;
+    if (h != w) ops &= 3;
+    const bool fh = ops & 1, fv = ops & 2, tr = ops & 4;
+    const int ty0 = blockIdx.y * PG_T, tx0 = blockIdx.x * PG_T;          // tile origin inside the window
+    const int th = min(PG_T, h - ty0), tw = min(PG_T, w - tx0);          // ragged last tiles
+    const int rowbytes = tw * C;
+    const unsigned char* src = data + (((int64_t)index * H0 + y0 + ty0) * W0 + x0 + tx0) * C;
+    const int64_t src_pitch = (int64_t)W0 * C;
+    for (int i = threadIdx.x; i < th * rowbytes; i += SISR_BLOCK) {
+        const int r = i / rowbytes, j = i - r * rowbytes;
+        tile[r * PG_PITCH + j] = src[r * src_pitch + j];
+    }
+    __syncthreads();
+    // the tile after hflip, vflip: rows [yb, yb + th), columns [xb, xb + tw) of the flipped window; after the transposition
+    // its rows are the flipped window's columns
+    const int yb = fv ? h - ty0 - th : ty0, xb = fh ? w - tx0 - tw : tx0;
+    const int OH = tr ? w : h, OW = tr ? h : w;
+    const int on = tr ? tw : th, om = tr ? th : tw;                      // rows, columns of the destination tile
+    const int oy0 = tr ? xb : yb, ox0 = tr ? yb : xb;
+    if (KIND == 0) {
+        float* out = reinterpret_cast<float*>(dst) + (int64_t)b * C * OH * OW;
+        const int q = threadIdx.x & (PG_T - 1);
+        if (q < om) {
+            for (int r = threadIdx.x / PG_T; r < on; r += SISR_BLOCK / PG_T) {
+                const int ly = tr ? q : r, lx = tr ? r : q;
+                const int lsy = fv ? th - 1 - ly : ly, lsx = fh ? tw - 1 - lx : lx;
+                const unsigned char* px = tile + lsy * PG_PITCH + lsx * C;
+                float* o = out + (int64_t)(oy0 + r) * OW + ox0 + q;
+                for (int c = 0; c < C; ++c) {
+                    const float t = (float)px[c] / 255.0f;                   // ToTensor (correctly rounded division)
+                    o[(int64_t)c * OH * OW] = (t - mean) / stdv;             // Normalize: the expressions of resize_u8_normalize_kernel
+                }
+            }
+        }
+    } else {
+        unsigned char* out = reinterpret_cast<unsigned char*>(dst) + (int64_t)b * OH * OW * C;
+        const int orow = om * C;
+        for (int i = threadIdx.x; i < on * orow; i += SISR_BLOCK) {
+            const int r = i / orow, jb = i - r * orow;
+            const int q = jb / C, c = jb - q * C;
+            const int ly = tr ? q : r, lx = tr ? r : q;
+            const int lsy = fv ? th - 1 - ly : ly, lsx = fh ? tw - 1 - lx : lx;
+            out[((int64_t)(oy0 + r) * OW + ox0) * C + jb] = tile[lsy * PG_PITCH + lsx * C + c];
+        }
+    }
+}
+
+// ---- entry points ----------------------------------------------------------------------------------------------------------------
+extern "C" int sisr_patch_draws_host(int64_t t, uint64_t seed, int32_t rank, int32_t world, int32_t order, int32_t B, int32_t M,
+                                     int32_t H0, int32_t W0, int32_t h, int32_t w, int32_t ops_mask, int32_t* draws_host) {
+    const PatchDrawArgs a = {seed, rank, world, order, B, M, H0, W0, h, w, ops_mask};
+    if (!draws_host || t < 0 || !patch_draw_args_ok(a)) return SISR_E_BADARG;
+    for (int b = 0; b < B; ++b) patch_draw_row(a, t, b, draws_host + 4 * (int64_t)b);
+    return 0;
+}
+
+extern "C" int sisr_patch_draw(int64_t* step_dev, uint64_t seed, int32_t rank, int32_t world, int32_t order, int32_t B, int32_t M,
+                               int32_t H0, int32_t W0, int32_t h, int32_t w, int32_t ops_mask, int32_t* draws_dev, void* stream) {
+    const PatchDrawArgs a = {seed, rank, world, order, B, M, H0, W0, h, w, ops_mask};
+    if (!step_dev || !draws_dev || !patch_draw_args_ok(a)) return SISR_E_BADARG;
+    hipLaunchKernelGGL(patch_draw_kernel, dim3(1), dim3(SISR_BLOCK), 0, sisr_stream(stream), step_dev, a, draws_dev);
+    SISR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int sisr_patch_gather(const unsigned char* data, int32_t M, int32_t H0, int32_t W0, int32_t C, const int32_t* draws_dev,
+                                 int32_t B, int32_t h, int32_t w, float mean, float stdv, void* dst, int32_t dst_kind, void* stream) {
+    if (!data || !draws_dev || !dst || M <= 0 || H0 <= 0 || W0 <= 0 || C < 1 || C > 4 || B <= 0 || h <= 0 || w <= 0 || h > H0 ||
+        w > W0 || (dst_kind != 0 && dst_kind != 1) || (dst_kind == 0 && !(stdv != 0.f)))
+        return SISR_E_BADARG;
+    const int tiles_x = (w + PG_T - 1) / PG_T, tiles_y = (h + PG_T - 1) / PG_T;
+    if (B > 65535 || tiles_y > 65535) return SISR_E_TOOBIG;
+    const dim3 grid(tiles_x, tiles_y, B);
+    if (dst_kind == 0)
+        hipLaunchKernelGGL(patch_gather_kernel<0>, grid, dim3(SISR_BLOCK), 0, sisr_stream(stream), data, M, H0, W0, C, draws_dev, h,
+                           w, mean, stdv, dst);
+    else
+        hipLaunchKernelGGL(patch_gather_kernel<1>, grid, dim3(SISR_BLOCK), 0, sisr_stream(stream), data, M, H0, W0, C, draws_dev, h,
+                           w, mean, stdv, dst);
+    SISR_CHECK_LAUNCH();
+    return 0;
+}
