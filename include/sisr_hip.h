@@ -62,8 +62,8 @@ typedef struct SisrConvPlan {
     int32_t lds_bytes;
     int32_t wpk_elems;              /* elements in the packed weight buffer                  */
     int32_t variant;                /* bf16 family, bit 0: the weight buffer carries the LANE-ORDER image of the persistent trunk
-                                       kernels behind the standard one (SisrWeightDesc.bf_f_lanes / bf_d_lanes); fp32 family, bits 1-2:
-                                       the LDS-order image behind the standard one (SisrWeightDesc.f_ldsimg / d_ldsimg: 2 = fp32
+                                       kernels behind the standard one (SISR_WIMG_BF16, extra); fp32 family, bits 1-2:
+                                       the LDS-order image behind the standard one (SISR_WIMG_F32, extra: 2 = fp32
                                        values, 4 = split pairs; used only when it matches mfma_split); set by the caller on the
                                        descriptor it launches, 0 after planning                                  */
     /* bf16 family: reciprocals m = ceil(2^32 / d) (0 for d = 1) so that n / d = umulhi(n, m) for n, d < 2^16 --
@@ -144,7 +144,7 @@ typedef struct SisrConvDesc {
      * fp32 operand (hi*hi + hi*lo + lo*hi, fp32 accumulate; operands good to 2^-17 relative); 0 = exact fp32 matrix instruction */
     int32_t mfma_split;
     SisrConvPlan plan;
-    /* conv_deep.hip (see SisrDeepPlan): `wdeep` = the weight image in that family's layout (SisrWeightDesc.wdp_fwd / wdp_dgrad),
+    /* conv_deep.hip (see SisrDeepPlan): `wdeep` = the weight image in that family's layout (SISR_WIMG_DEEP),
      * `deep_ws` = the caller's split workspace (deep.ws_bytes; may be NULL when deep.split == 1), `epi_scale_p` = device scalar the
      * accumulators are multiplied by before the bias (1 / sigma of a spectrally normalised weight packed un-normalised) or NULL */
     const void *wdeep;
@@ -154,7 +154,7 @@ typedef struct SisrConvDesc {
      * classes c = 2 py + px: the descriptor describes the class convolution with the MOST taps (KH = KW = 2, stride 1, pad 0, over
      * dy; Ho x Wo = the class grid H/2 x W/2; y_sy = y_sx = 2, y_H x y_W = the gradient's size); class c has deep_ckh[c] tap rows,
      * writes output pixel (2 a + py, 2 b + px) and reads its weights from wdeep_c[c] -- always in the KW = 2 row format, a class
-     * with one tap per row carries zeros for the second (SisrWeightDesc.wdp_cls_kw = 2).  Partial rows (bnb_part) and split
+     * with one tap per row carries zeros for the second (SISR_WIMG_DEEP with extra = 2).  Partial rows (bnb_part) and split
      * workspace tiles are class-major. */
     const void *wdeep_c[4];
     int32_t deep_ckh[4];
@@ -221,7 +221,7 @@ typedef struct SisrWgradDesc {
 int sisr_wgrad_plan(SisrWgradDesc *d, int32_t max_pixel_blocks);
 /* bf16 matrix-core variants (v_mfma_f32_32x32x16_bf16, fp32 accumulate; activations fp32 or bf16 in HBM -- see the
  * *_bf16 storage flags -- converted while staged into LDS).  Same descriptors; `wpk` points at the bf16 image written by
- * sisr_weights_prepare (wbf_fwd / wbf_dgrad).  Requirements: Cin % 32 == 0, KH*KW <= 9, NHWC
+ * sisr_weights_prepare (SISR_WIMG_BF16).  Requirements: Cin % 32 == 0, KH*KW <= 9, NHWC
  * operands; SISR_E_UNSUPPORTED otherwise (callers keep the fp32 kernels for those layers). */
 int sisr_conv2d_plan_bf16(SisrConvDesc *d);
 int sisr_conv2d_bf16(const SisrConvDesc *d, void *stream);
@@ -327,60 +327,70 @@ int64_t sisr_wgrad_bf16_slab_lead(const SisrWgradDesc *d);
 /* ---- weights: spectral norm power iteration + packing (legacy torch.nn.utils.spectral_norm
  *      hook, model_generator.py:3; model_discriminator.py:2), multi-tensor: one launch serves
  *      every convolution of a network.  The descriptor TABLE lives in device memory. ---------- */
+/* One packed image of a weight.  Every image is the same gather under one tap map: element (out, in, r', s') holds forward tap
+ * (R0y + Sy r', R0x + Sx s') of W_orig (times 1 / sigma), and zero where that tap lies outside the weight:
+ *   (R0, S) = (0, +1)       the forward conv                                                 transposed = 0
+ *             (K - 1, -1)   the stride-1 data gradient (a conv over dy with flipped taps)    transposed = 1
+ *             (c_R0, -2)    one output-parity class c = (py, px) of a stride-2 convolution's data gradient, itself a stride-1 conv
+ *                           over dy with KH x KW taps                                        transposed = 1
+ * transposed = 0: out = packed cout (SisrWeightDesc.shuffle2), in = cin; 1: out = cin, in = packed cout.  Out / in channels beyond
+ * the weight's are zero.  `format` names the storage order: */
+enum {
+    /* fp32 [chunk of CK in][r'][out, CoutPad][krow, KROWP], krow = s' * PS + (in - chunk * CK); the slots in >= CK of a tap, the krow
+     * slots behind the taps and the rows out >= the channel count are zero.  extra != 0 (trunk geometry: Cin = Cout = 64, 3x3): also
+     * write, right behind the image (SISR_WLDS_WORDS more 32-bit words), the weights in the persistent fp32-tensor conv kernel's LDS
+     * order -- [out half][chunk][tap][out 32][32 + 4 words] -- so that its weight fill is a plain 16-byte copy.  1: fp32 values; 2:
+     * split build -- words 0..15 of a row the RNE bf16 heads of in-channels (2m, 2m + 1), words 16..31 the bf16 of what the heads
+     * leave; words 32..35 zero */
+    SISR_WIMG_F32 = 0,
+    /* bf16 images for the bf16-MFMA kernels: [chunk of CK = 32 in][out, CoutPad][tap * CK + (in - chunk * CK)], n_chunk = in-channels
+     * / CK.  extra != 0 (trunk geometry: 64 in-channels, 3x3, CoutPad % 64 == 0): also write, right behind the image (same size
+     * again), the image in the order the persistent trunk kernels load it -- [32-out block][tap][k slice j: 16 in-channels][lane =
+     * kk * 32 + out] x 8 bf16 (in-channels (j >> 1) * 32 + (j & 1) * 16 + 8 kk ..) -- so that a wave's 16-byte loads are contiguous
+     * (1 KB per instruction instead of 64 pieces 576 bytes apart: 1.1 us of every launch) */
+    SISR_WIMG_BF16 = 1,
+    /* conv_deep.hip images (3x3 weights, channels in 32s; written by sisr_weights_pack_deep): bf16 [chunk of 32 in][r'][out, CoutPad]
+     * [extra * 32 + 8], element s' * 32 + (in - chunk * 32), n_chunk = in-channels / 32, CoutPad = the out-channel count; the taps
+     * s' >= KW of a row and its 8 padding elements are zero.  extra = taps per row: KW, or 2 where the four classes of a stride-2
+     * data gradient run as one launch and every class image is written in the KW = 2 row format.  SisrWeightDesc.wdp_scaled = 0
+     * packs W_orig itself (the kernels then apply 1 / sigma in their epilogue: SisrConvDesc.epi_scale_p), 1 packs W_orig / sigma */
+    SISR_WIMG_DEEP = 2
+};
+typedef struct SisrWeightImage {
+    void   *dst;               /* NULL: not written                                             */
+    int32_t format;            /* SISR_WIMG_*                                                   */
+    int32_t transposed;        /* 0: out = packed cout, in = cin;  1: out = cin, in = packed cout */
+    int32_t KH, KW;            /* taps of the image                                             */
+    int32_t R0y, Sy, R0x, Sx;  /* image tap (r', s') = forward tap (R0y + Sy r', R0x + Sx s')   */
+    int32_t CK, PS, KROWP, n_chunk, CoutPad;   /* the consumer's plan (SisrConvPlan); see the formats */
+    int32_t extra;             /* F32: LDS-order copy mode 0/1/2; BF16: lane-order copy 0/1; DEEP: taps per row */
+} SisrWeightImage;
+#define SISR_WLDS_WORDS (2 * 2 * 9 * 32 * 36)
+#define SISR_WEIGHT_IMAGES 5
+
 typedef struct SisrWeightDesc {
     const float *w_orig;      /* OIHW [Cout][Cin][KH][KW]                                     */
     float *u, *v;             /* spectral-norm buffers (updated in place when training) or NULL */
     float *u_used, *v_used;   /* copies of the u/v that define sigma (for backward) or NULL   */
     float *sigma;             /* [2] out: sigma (1.0 when u == NULL), 1 / sigma                */
     float *sn_work;           /* power-iteration scratch, >= ceil(Cout/16)*Cin*KH*KW + Cout floats (u != NULL) */
-    float *wpk_fwd;           /* packed W/sigma for the forward conv, or NULL                 */
-    float *wpk_dgrad;         /* packed flipped/transposed W/sigma for the data gradient, or NULL */
     int32_t Cout, Cin, KH, KW;
     int32_t training;         /* run the power iteration                                      */
     int32_t shuffle2;         /* conv feeds PixelShuffle(2): pack couts in (i,j)-major order  */
-    /* forward packing */
-    int32_t f_CK, f_PS, f_KROWP, f_n_chunk, f_CoutPad;
-    /* data-gradient packing (roles of Cin/Cout swapped) */
-    int32_t d_CK, d_PS, d_KROWP, d_n_chunk, d_CoutPad;
-    /* stride-2 convs: the data gradient splits by output parity class c = (py, px) into four
-     * stride-1 convs over dy with KH'xKW' taps; tap (r', s') of class c uses the forward tap
-     * (c_R0y - 2 r', c_R0x - 2 s').  Packed like wpk_dgrad, one buffer per class (or NULL). */
-    float *wpk_dcls[4];
-    int32_t c_KH[4], c_KW[4], c_R0y[4], c_R0x[4];
-    int32_t c_CK[4], c_PS[4], c_KROWP[4], c_n_chunk[4], c_CoutPad[4];
-    /* bf16 images for the bf16-MFMA kernels: [chunk of CK in-channels][cout][tap*CK + ci] (or NULL) */
-    void *wbf_fwd, *wbf_dgrad;
-    int32_t bf_f_CoutPad, bf_d_CoutPad;
-    int32_t bf_f_CK, bf_d_CK;   /* in-channel chunk of the bf16 images (32) */
-    void *wbf_dcls[4];          /* bf16 images of the stride-2 parity classes (chunks of 32), or NULL: then wpk_dcls */
-    int32_t bf_c_CoutPad[4];
-    /* trunk geometry (Cin = 64, 3x3, CoutPad % 64 == 0): also write, right behind wbf_fwd / wbf_dgrad (same size again), the image
-     * in the order the persistent trunk kernels load it -- [32-cout block][tap][k slice j: 16 in-channels][lane = kk * 32 + cout]
-     * x 8 bf16 (in-channels (j >> 1) * 32 + (j & 1) * 16 + 8 kk ..) -- so that a wave's 16-byte loads are contiguous (1 KB per
-     * instruction instead of 64 pieces 576 bytes apart: 1.1 us of every launch) */
-    int32_t bf_f_lanes, bf_d_lanes;
-    /* fp32 images, trunk geometry (Cin = Cout = 64, 3x3): also write, right behind wpk_fwd / wpk_dgrad (SISR_WLDS_WORDS more
-     * 32-bit words), the weights in the persistent fp32-tensor conv kernel's LDS order -- [cout half][chunk][tap][cout 32][32 + 4
-     * words] -- so that its weight fill is a plain 16-byte copy.  1: fp32 values; 2: split build -- words 0..15 of a row the RNE
-     * bf16 heads of in-channels (2m, 2m + 1), words 16..31 the bf16 of what the heads leave; 0: none */
-    int32_t f_ldsimg, d_ldsimg;
-    /* conv_deep.hip images (or NULL): [32-channel chunk][tap row][cout][KW * 32 + 8] bf16, element kx * 32 + ci; the data-gradient
-     * image has the roles of the channels swapped and the taps flipped; wdp_dcls = the four output-parity classes of a stride-2
-     * convolution's data gradient (taps c_KH x c_KW, tap (r', s') = forward tap (c_R0y - 2 r', c_R0x - 2 s')).  wdp_scaled = 0 packs
-     * W_orig itself (the kernels then apply 1 / sigma in their epilogue: SisrConvDesc.epi_scale_p), 1 packs W_orig / sigma */
-    void *wdp_fwd, *wdp_dgrad;
-    void *wdp_dcls[4];
-    int32_t wdp_scaled;
-    int32_t wdp_cls_kw;       /* 0: a class image has c_KW taps per row; 2: every class image is written in the KW = 2 row format */
+    int32_t wdp_scaled;       /* SISR_WIMG_DEEP images hold W_orig / sigma instead of W_orig  */
+    /* [0]: the forward conv; [1]: the stride-1 data gradient, or [1 + c]: parity class c = 2 py + px of a stride-2 one */
+    SisrWeightImage img[SISR_WEIGHT_IMAGES];
 } SisrWeightDesc;
-#define SISR_WLDS_WORDS (2 * 2 * 9 * 32 * 36)
+/* bytes sisr_weights_pack / sisr_weights_pack_deep write at img->dst (the copy `extra` asks for included; dst itself is not read),
+ * or a negative status for a record no kernel packs (host only) */
+int64_t sisr_weight_image_bytes(const SisrWeightImage *img);
 
 /* max_rows / max_cols: largest Cout and Cin*KH*KW over the table (the launch grids are sized from them) */
 int sisr_weights_prepare(const SisrWeightDesc *table_dev, int32_t n, int32_t max_rows, int32_t max_cols,
                          void *stream);
 
 /* sisr_weights_prepare = sisr_weights_sn (power iteration: u, v, sigma; sigma[1] = 1 / sigma) + sisr_weights_pack (every image but
- * the wdp_* ones).  sisr_weights_pack_deep writes the conv_deep.hip images (wdp_fwd / wdp_dgrad / wdp_dcls, 3x3 weights) from one
+ * the SISR_WIMG_DEEP ones).  sisr_weights_pack_deep writes the conv_deep.hip images (SISR_WIMG_DEEP, 3x3 weights) from one
  * coalesced read of each 32 x 32-channel tile; max_cout / max_cin: largest channel counts over the table.  A caller that keeps
  * un-normalised images (wdp_scaled = 0) across the forwards between two optimizer steps runs sisr_weights_sn alone. */
 int sisr_weights_sn(const SisrWeightDesc *table_dev, int32_t n, int32_t max_rows, int32_t max_cols, void *stream);

@@ -75,19 +75,19 @@ class WgradDesc(C.Structure):
                 [('slab_stride', _i64), ('deep', WgradDeepPlan)])
 
 
+WIMG_F32, WIMG_BF16, WIMG_DEEP = range(3)
+WEIGHT_IMAGES = 5
+
+
+class WeightImage(C.Structure):
+    _fields_ = [('dst', _f)] + [(n, _i32) for n in ('format', 'transposed', 'KH', 'KW', 'R0y', 'Sy', 'R0x', 'Sx',
+                                                    'CK', 'PS', 'KROWP', 'n_chunk', 'CoutPad', 'extra')]
+
+
 class WeightDesc(C.Structure):
-    _fields_ = ([(n, _f) for n in ('w_orig', 'u', 'v', 'u_used', 'v_used', 'sigma', 'sn_work', 'wpk_fwd', 'wpk_dgrad')] +
-                [(n, _i32) for n in ('Cout', 'Cin', 'KH', 'KW', 'training', 'shuffle2',
-                                     'f_CK', 'f_PS', 'f_KROWP', 'f_n_chunk', 'f_CoutPad',
-                                     'd_CK', 'd_PS', 'd_KROWP', 'd_n_chunk', 'd_CoutPad')] +
-                [('wpk_dcls', _f * 4)] +
-                [(n, _i32 * 4) for n in ('c_KH', 'c_KW', 'c_R0y', 'c_R0x', 'c_CK', 'c_PS', 'c_KROWP',
-                                         'c_n_chunk', 'c_CoutPad')] +
-                [('wbf_fwd', _f), ('wbf_dgrad', _f), ('bf_f_CoutPad', _i32), ('bf_d_CoutPad', _i32),
-                 ('bf_f_CK', _i32), ('bf_d_CK', _i32), ('wbf_dcls', _f * 4), ('bf_c_CoutPad', _i32 * 4),
-                 ('bf_f_lanes', _i32), ('bf_d_lanes', _i32), ('f_ldsimg', _i32), ('d_ldsimg', _i32),
-                 ('wdp_fwd', _f), ('wdp_dgrad', _f), ('wdp_dcls', _f * 4), ('wdp_scaled', _i32), ('wdp_cls_kw', _i32)])
-WLDS_WORDS = 2 * 2 * 9 * 32 * 36
+    _fields_ = ([(n, _f) for n in ('w_orig', 'u', 'v', 'u_used', 'v_used', 'sigma', 'sn_work')] +
+                [(n, _i32) for n in ('Cout', 'Cin', 'KH', 'KW', 'training', 'shuffle2', 'wdp_scaled')] +
+                [('img', WeightImage * WEIGHT_IMAGES)])
 
 
 class WeightGradDesc(C.Structure):
@@ -155,6 +155,7 @@ _SIGS = {
     'sisr_weights_sn': [_f, _i32, _i32, _i32, _f],
     'sisr_weights_pack': [_f, _i32, _i32, _i32, _f],
     'sisr_weights_pack_deep': [_f, _i32, _i32, _i32, _f],
+    'sisr_weight_image_bytes': [C.POINTER(WeightImage)],
     'sisr_weights_grad': [_f, _i32, _f, _i32, _f],
     'sisr_weights_grad_fast': [_f, _i32, _f, _i32, _i32, _f],
     'sisr_weights_grad_tiles': [C.POINTER(WeightGradDesc)],
@@ -244,6 +245,7 @@ def lib():
     L.sisr_adam_blocks.restype = C.c_int64
     L.sisr_adam_norm_ws_doubles.restype = C.c_int64
     L.sisr_wgrad_bf16_slab_lead.restype = C.c_int64
+    L.sisr_weight_image_bytes.restype = C.c_int64
     L.sisr_version.restype = C.c_char_p
     L.sisr_version.argtypes = []
     sizes = (_i32 * 8)()

@@ -57,7 +57,7 @@ struct TrunkArgs {
     const float *pa, *pb, *pd, *ps, *pt;  // per-channel prologue constants
     const float* slope_p; float slope;
     const void* wpk;                      // bf16 image [2 chunks][64 couts][9 taps][32 cin]
-    const void* wln;                      // the same weights in the consumers' load order (SisrWeightDesc.bf_f_lanes), or nullptr
+    const void* wln;                      // the same weights in the consumers' load order (SISR_WIMG_BF16 with extra set), or nullptr
     const float* bias;
     void* y;                              // bf16 NHWC [N][H][W][64]
     float *stat_part, *cnt_part;          // forward role: [grid][2][64], [grid]

@@ -62,7 +62,7 @@ struct CTrunkF32Args {
     const float *pa, *pb, *pd, *ps, *pt;
     const float* slope_p; float slope;
     const float* wpk;
-    const void* wimg;                     // the weights in this kernel's LDS order (SisrWeightDesc.f_ldsimg / d_ldsimg), mode matching SPLIT, or nullptr
+    const void* wimg;                     // the weights in this kernel's LDS order (SISR_WIMG_F32 with extra set), mode matching SPLIT, or nullptr
     const float* bias;
     const float* res;
     float* y;

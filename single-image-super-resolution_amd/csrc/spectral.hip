@@ -159,79 +159,77 @@ __device__ __forceinline__ int unpermute_cout(int cp, int Cout, int shuffle2) {
     return c * 4 + ij;
 }
 
-// phase 2: pack W/sigma.  grid (n_weights, parts); grid-stride over the packed elements.
+// elements of an image's standard order (fp32 words for SISR_WIMG_F32, bf16 otherwise); the formats: include/sisr_hip.h
+__host__ __device__ __forceinline__ int64_t wimg_elems(const SisrWeightImage& g) {
+    if (g.format == SISR_WIMG_F32) return (int64_t)g.n_chunk * g.KH * g.CoutPad * g.KROWP;
+    if (g.format == SISR_WIMG_BF16) return (int64_t)g.n_chunk * g.CoutPad * g.KH * g.KW * g.CK;
+    return (int64_t)g.n_chunk * g.KH * g.CoutPad * (g.extra * 32 + 8);
+}
+// bytes of the image with the copy `extra` asks for behind it: the one place that knows an image's size
+__host__ __device__ __forceinline__ int64_t wimg_bytes(const SisrWeightImage& g) {
+    if (g.format == SISR_WIMG_F32) return 4 * (wimg_elems(g) + (g.extra ? SISR_WLDS_WORDS : 0));
+    return 2 * wimg_elems(g) * (g.format == SISR_WIMG_BF16 && g.extra ? 2 : 1);
+}
+
+// what every image of a weight is gathered from (the kernels copy it out of the table once; the image records follow one by one)
+struct WimgSource {
+    const float* w_orig;
+    int Cout, Cin, KH, KW, shuffle2;
+    float inv;                                                         // 1 / sigma
+};
+// THE read of W_orig: element (out channel o, in channel i, tap (rp, sp)) of image g = forward tap (R0y + Sy rp, R0x + Sx sp) of
+// W_orig times inv, zero for a channel or a tap outside the weight (a tap past the image's own KH x KW maps outside the weight
+// under every tap map in use).  One predicate of unsigned compares (a negative tap is a huge one) and a 32-bit index -- a weight
+// is far below 2^31 elements -- keep the per-element cost at that of a hard-wired map: the pack kernels are bound by it.
+__device__ __forceinline__ float wimg_value(const WimgSource& w, const SisrWeightImage& g, unsigned o, unsigned i, int rp, int sp) {
+    const unsigned cp = g.transposed ? i : o, ci = g.transposed ? o : i;      // packed forward cout, forward cin
+    const unsigned r = (unsigned)(g.R0y + g.Sy * rp), s = (unsigned)(g.R0x + g.Sx * sp);
+    if ((cp >= (unsigned)w.Cout) | (ci >= (unsigned)w.Cin) | (r >= (unsigned)w.KH) | (s >= (unsigned)w.KW)) return 0.f;
+    const unsigned co = (unsigned)unpermute_cout((int)cp, w.Cout, w.shuffle2);
+    return w.w_orig[((co * (unsigned)w.Cin + ci) * (unsigned)w.KH + r) * (unsigned)w.KW + s] * w.inv;
+}
+
+// phase 2: pack W/sigma.  grid (n_weights, parts); a workgroup walks the images of its weight, grid-stride over the elements of
+// each: one loop per storage order.  (Packed images are far below 2^32 elements: 32-bit index arithmetic.)
+// (The descriptor is copied by value and the image loop unrolled, so that every field of every record is fetched in ONE batch of
+// scalar loads before the first store: a workgroup has only a few elements of each image to hide a dependent round trip per
+// record behind.)
 __global__ void __launch_bounds__(SISR_BLOCK) weights_pack_kernel(const SisrWeightDesc* table) {
-    const SisrWeightDesc w = table[blockIdx.x];
-    const float inv = 1.f / (w.sigma ? w.sigma[0] : 1.f);
+    const SisrWeightDesc t = table[blockIdx.x];
+    const WimgSource w = {t.w_orig, t.Cout, t.Cin, t.KH, t.KW, t.shuffle2, 1.f / (t.sigma ? t.sigma[0] : 1.f)};
     const int64_t stride = (int64_t)gridDim.y * SISR_BLOCK;
     const int64_t start = (int64_t)blockIdx.y * SISR_BLOCK + threadIdx.x;
-    if (w.wpk_fwd) {
-        // [chunk][r][cp][krow], krow = s*PS + (ci - chunk*CK)
-        const int64_t total = (int64_t)w.f_n_chunk * w.KH * w.f_CoutPad * w.f_KROWP;
-        for (int64_t e = start; e < total; e += stride) {
-            unsigned tq = (unsigned)e;          // (packed images are far below 2^32 elements: 32-bit index arithmetic)
-            const int krow = (int)(tq % w.f_KROWP); tq /= w.f_KROWP;
-            const int cp = (int)(tq % w.f_CoutPad); tq /= w.f_CoutPad;
-            const int r = (int)(tq % w.KH);
-            const int chunk = (int)(tq / w.KH);
-            const int s = krow / w.f_PS, cl = krow - s * w.f_PS;
-            const int ci = chunk * w.f_CK + cl;
-            float val = 0.f;
-            if (s < w.KW && cl < w.f_CK && ci < w.Cin && cp < w.Cout) {
-                const int co = unpermute_cout(cp, w.Cout, w.shuffle2);
-                val = w.w_orig[(((int64_t)co * w.Cin + ci) * w.KH + r) * w.KW + s] * inv;
+#pragma unroll
+    for (int gi = 0; gi < SISR_WEIGHT_IMAGES; ++gi) {
+        const SisrWeightImage& g = t.img[gi];
+        if (g.dst == nullptr || g.format == SISR_WIMG_DEEP) continue;
+        const int64_t total = wimg_elems(g);
+        if (g.format == SISR_WIMG_F32) {
+            float* dst = reinterpret_cast<float*>(g.dst);
+            for (int64_t e = start; e < total; e += stride) {           // [chunk][r'][out][krow], krow = s' * PS + (in - chunk * CK)
+                unsigned tq = (unsigned)e;
+                const unsigned krow = tq % g.KROWP; tq /= g.KROWP;
+                const unsigned o = tq % g.CoutPad; tq /= g.CoutPad;
+                const unsigned rp = tq % g.KH, chunk = tq / g.KH;
+                const unsigned sp = krow / g.PS, il = krow - sp * g.PS;
+                dst[e] = il < (unsigned)g.CK ? wimg_value(w, g, o, chunk * g.CK + il, rp, sp) : 0.f;
             }
-            w.wpk_fwd[e] = val;
-        }
-    }
-    if (w.wpk_dgrad) {
-        // data gradient = conv over dy (channels = couts in packed order) with flipped taps:
-        // Wd[op = ci][ip = cp][r'][s'] = W[co(cp)][ci][KH-1-r'][KW-1-s']
-        const int64_t total = (int64_t)w.d_n_chunk * w.KH * w.d_CoutPad * w.d_KROWP;
-        for (int64_t e = start; e < total; e += stride) {
-            unsigned tq = (unsigned)e;
-            const int krow = (int)(tq % w.d_KROWP); tq /= w.d_KROWP;
-            const int op = (int)(tq % w.d_CoutPad); tq /= w.d_CoutPad;
-            const int r = (int)(tq % w.KH);
-            const int chunk = (int)(tq / w.KH);
-            const int s = krow / w.d_PS, il = krow - s * w.d_PS;
-            const int ip = chunk * w.d_CK + il;
-            float val = 0.f;
-            if (s < w.KW && il < w.d_CK && ip < w.Cout && op < w.Cin) {
-                const int co = unpermute_cout(ip, w.Cout, w.shuffle2);
-                val = w.w_orig[(((int64_t)co * w.Cin + op) * w.KH + (w.KH - 1 - r)) * w.KW + (w.KW - 1 - s)] * inv;
-            }
-            w.wpk_dgrad[e] = val;
-        }
-    }
-    // the fp32-tensor trunk conv's LDS-order images (SisrWeightDesc.f_ldsimg / d_ldsimg), behind the standard fp32 images
-    for (int role = 0; role < 2; ++role) {
-        const int mode = role == 0 ? w.f_ldsimg : w.d_ldsimg;
-        float* base = role == 0 ? w.wpk_fwd : w.wpk_dgrad;
-        if (mode == 0 || base == nullptr) continue;
-        const int64_t std_elems = role == 0 ? (int64_t)w.f_n_chunk * w.KH * w.f_CoutPad * w.f_KROWP
-                                            : (int64_t)w.d_n_chunk * w.KH * w.d_CoutPad * w.d_KROWP;
-        unsigned* dst = reinterpret_cast<unsigned*>(base + std_elems);
-        // value of (packed output channel oc, packed input channel ic, tap): the same numbers as the standard images hold
-        auto val = [&](int oc, int ic, int tap) {
-            const int r = tap / 3, sx = tap - 3 * r;
-            if (role == 0) return w.w_orig[(((int64_t)oc * w.Cin + ic) * w.KH + r) * w.KW + sx] * inv;
-            return w.w_orig[(((int64_t)ic * w.Cin + oc) * w.KH + (w.KH - 1 - r)) * w.KW + (w.KW - 1 - sx)] * inv;
-        };
-        for (int64_t e = start; e < SISR_WLDS_WORDS; e += stride) {
-            unsigned tq = (unsigned)e;
-            const int wd = (int)(tq % 36u); tq /= 36u;
-            const int co = (int)(tq & 31u); tq >>= 5;
-            const int tap = (int)(tq % 9u); tq /= 9u;
-            const int q = (int)(tq & 1u), hc = (int)(tq >> 1);
-            unsigned word = 0u;
-            if (wd < 32) {
-                const int oc = 32 * hc + co;
-                if (mode == 1) {
-                    word = __float_as_uint(val(oc, 32 * q + wd, tap));
-                } else {
-                    const int m = wd & 15;
-                    const float v0 = val(oc, 32 * q + 2 * m, tap), v1 = val(oc, 32 * q + 2 * m + 1, tap);
+            if (g.extra == 0) continue;
+            // the fp32-tensor trunk conv's LDS order, behind the standard image: the same numbers
+            unsigned* lds = reinterpret_cast<unsigned*>(dst + total);
+            for (int64_t e = start; e < SISR_WLDS_WORDS; e += stride) {
+                unsigned tq = (unsigned)e;
+                const unsigned wd = tq % 36u; tq /= 36u;
+                const unsigned oc = tq & 31u; tq >>= 5;
+                const unsigned tap = tq % 9u; tq /= 9u;
+                const unsigned q = tq & 1u, o = 32 * (tq >> 1) + oc;
+                const unsigned rp = tap / 3, sp = tap - 3 * rp;
+                unsigned word = 0u;
+                if (wd < 32 && g.extra == 1) {
+                    word = __float_as_uint(wimg_value(w, g, o, 32 * q + wd, rp, sp));
+                } else if (wd < 32) {
+                    const unsigned m = wd & 15;
+                    const float v0 = wimg_value(w, g, o, 32 * q + 2 * m, rp, sp), v1 = wimg_value(w, g, o, 32 * q + 2 * m + 1, rp, sp);
                     const __bf16 h0 = (__bf16)v0, h1 = (__bf16)v1;
                     if (wd < 16) {
                         word = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
@@ -240,194 +238,95 @@ __global__ void __launch_bounds__(SISR_BLOCK) weights_pack_kernel(const SisrWeig
                         word = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
                     }
                 }
+                lds[e] = word;
             }
-            dst[e] = word;
-        }
-    }
-    // bf16 images for conv_bf16.hip: [chunk32][cp][tap*32 + cl]
-    if (w.wbf_fwd) {
-        __bf16* dst = reinterpret_cast<__bf16*>(w.wbf_fwd);
-        const int CKb = w.bf_f_CK;
-        const int taps = w.KH * w.KW, WSG = taps * CKb;
-        const int64_t total = (int64_t)(w.Cin / CKb) * w.bf_f_CoutPad * WSG;
-        for (int64_t e = start; e < total; e += stride) {
-            unsigned tq = (unsigned)e;
-            const int kidx = (int)(tq % WSG); tq /= WSG;
-            const int cp = (int)(tq % w.bf_f_CoutPad);
-            const int chunk = (int)(tq / w.bf_f_CoutPad);
-            const int tap = kidx / CKb, cl = kidx - tap * CKb;
-            const int r = tap / w.KW, sx = tap - r * w.KW, ci = chunk * CKb + cl;
-            float val = 0.f;
-            if (cp < w.Cout) {
-                const int co = unpermute_cout(cp, w.Cout, w.shuffle2);
-                val = w.w_orig[(((int64_t)co * w.Cin + ci) * w.KH + r) * w.KW + sx] * inv;
+        } else {
+            __bf16* dst = reinterpret_cast<__bf16*>(g.dst);
+            const unsigned WSG = g.KH * g.KW * g.CK;
+            for (int64_t e = start; e < total; e += stride) {           // [chunk][out][tap * CK + (in - chunk * CK)]
+                unsigned tq = (unsigned)e;
+                const unsigned kidx = tq % WSG; tq /= WSG;
+                const unsigned o = tq % g.CoutPad, chunk = tq / g.CoutPad;
+                const unsigned tap = kidx / g.CK, il = kidx - tap * g.CK;
+                const unsigned rp = tap / g.KW, sp = tap - rp * g.KW;
+                dst[e] = (__bf16)wimg_value(w, g, o, chunk * g.CK + il, rp, sp);
             }
-            dst[e] = (__bf16)val;
-        }
-        if (w.bf_f_lanes) {
-            // the same values in the persistent trunk kernels' load order (see SisrWeightDesc.bf_f_lanes), behind the image above
+            if (g.extra == 0) continue;
+            // the same values in the persistent trunk kernels' load order, behind the standard image
             for (int64_t e = start; e < total; e += stride) {
                 unsigned tq = (unsigned)e;
-                const int el = (int)(tq & 7); tq >>= 3;
-                const int lane = (int)(tq & 63); tq >>= 6;
-                const int j = (int)(tq & 3); tq >>= 2;
-                const int tap = (int)(tq % 9);
-                const int cp = (int)(tq / 9) * 32 + (lane & 31);
-                const int ci = (j >> 1) * 32 + (j & 1) * 16 + 8 * (lane >> 5) + el;
-                const int r = tap / w.KW, sx = tap - r * w.KW;
-                float val = 0.f;
-                if (cp < w.Cout) {
-                    const int co = unpermute_cout(cp, w.Cout, w.shuffle2);
-                    val = w.w_orig[(((int64_t)co * w.Cin + ci) * w.KH + r) * w.KW + sx] * inv;
-                }
-                dst[total + e] = (__bf16)val;
+                const unsigned el = tq & 7; tq >>= 3;
+                const unsigned lane = tq & 63; tq >>= 6;
+                const unsigned j = tq & 3; tq >>= 2;
+                const unsigned tap = tq % 9;
+                const unsigned o = tq / 9 * 32 + (lane & 31);
+                const unsigned i = (j >> 1) * 32 + (j & 1) * 16 + 8 * (lane >> 5) + el;
+                const unsigned rp = tap / g.KW, sp = tap - rp * g.KW;
+                dst[total + e] = (__bf16)wimg_value(w, g, o, i, rp, sp);
             }
-        }
-    }
-    if (w.wbf_dgrad) {
-        __bf16* dst = reinterpret_cast<__bf16*>(w.wbf_dgrad);
-        const int CKb = w.bf_d_CK;
-        const int taps = w.KH * w.KW, WSG = taps * CKb;
-        const int64_t total = (int64_t)(w.Cout / CKb) * w.bf_d_CoutPad * WSG;
-        for (int64_t e = start; e < total; e += stride) {
-            unsigned tq = (unsigned)e;
-            const int kidx = (int)(tq % WSG); tq /= WSG;
-            const int op = (int)(tq % w.bf_d_CoutPad);
-            const int chunk = (int)(tq / w.bf_d_CoutPad);
-            const int tap = kidx / CKb, il = kidx - tap * CKb;
-            const int r = tap / w.KW, sx = tap - r * w.KW, ip = chunk * CKb + il;
-            float val = 0.f;
-            if (op < w.Cin) {
-                const int co = unpermute_cout(ip, w.Cout, w.shuffle2);
-                val = w.w_orig[(((int64_t)co * w.Cin + op) * w.KH + (w.KH - 1 - r)) * w.KW + (w.KW - 1 - sx)] * inv;
-            }
-            dst[e] = (__bf16)val;
-        }
-        if (w.bf_d_lanes) {
-            for (int64_t e = start; e < total; e += stride) {
-                unsigned tq = (unsigned)e;
-                const int el = (int)(tq & 7); tq >>= 3;
-                const int lane = (int)(tq & 63); tq >>= 6;
-                const int j = (int)(tq & 3); tq >>= 2;
-                const int tap = (int)(tq % 9);
-                const int op = (int)(tq / 9) * 32 + (lane & 31);
-                const int ip = (j >> 1) * 32 + (j & 1) * 16 + 8 * (lane >> 5) + el;
-                const int r = tap / w.KW, sx = tap - r * w.KW;
-                float val = 0.f;
-                if (op < w.Cin) {
-                    const int co = unpermute_cout(ip, w.Cout, w.shuffle2);
-                    val = w.w_orig[(((int64_t)co * w.Cin + op) * w.KH + (w.KH - 1 - r)) * w.KW + (w.KW - 1 - sx)] * inv;
-                }
-                dst[total + e] = (__bf16)val;
-            }
-        }
-    }
-    // stride-2 data gradient: one packed image per output parity class (bf16 image for the bf16 kernels)
-    for (int cls = 0; cls < 4; ++cls) {
-        __bf16* dst = reinterpret_cast<__bf16*>(w.wbf_dcls[cls]);
-        if (dst == nullptr) continue;
-        const int KHc = w.c_KH[cls], KWc = w.c_KW[cls], WSG = KHc * KWc * 32, CoutPad = w.bf_c_CoutPad[cls];
-        const int64_t total = (int64_t)(w.Cout / 32) * CoutPad * WSG;
-        for (int64_t e = start; e < total; e += stride) {
-            unsigned tq = (unsigned)e;
-            const int kidx = (int)(tq % WSG); tq /= WSG;
-            const int op = (int)(tq % CoutPad);
-            const int chunk = (int)(tq / CoutPad);
-            const int tap = kidx >> 5, il = kidx & 31;
-            const int rp = tap / KWc, sp = tap - rp * KWc, ip = chunk * 32 + il;
-            const int r = w.c_R0y[cls] - 2 * rp, sx = w.c_R0x[cls] - 2 * sp;
-            float val = 0.f;
-            if (op < w.Cin && r >= 0 && r < w.KH && sx >= 0 && sx < w.KW)
-                val = w.w_orig[(((int64_t)ip * w.Cin + op) * w.KH + r) * w.KW + sx] * inv;
-            dst[e] = (__bf16)val;
-        }
-    }
-    for (int cls = 0; cls < 4; ++cls) {
-        float* dst = w.wpk_dcls[cls];
-        if (dst == nullptr) continue;
-        const int KHc = w.c_KH[cls], KWc = w.c_KW[cls];
-        const int CK = w.c_CK[cls], PS = w.c_PS[cls], KROWP = w.c_KROWP[cls], CoutPad = w.c_CoutPad[cls];
-        const int64_t total = (int64_t)w.c_n_chunk[cls] * KHc * CoutPad * KROWP;
-        for (int64_t e = start; e < total; e += stride) {
-            unsigned tq = (unsigned)e;
-            const int krow = (int)(tq % KROWP); tq /= KROWP;
-            const int op = (int)(tq % CoutPad); tq /= CoutPad;
-            const int rp = (int)(tq % KHc);
-            const int chunk = (int)(tq / KHc);
-            const int sp = krow / PS, il = krow - sp * PS;
-            const int ip = chunk * CK + il;
-            const int r = w.c_R0y[cls] - 2 * rp, sx = w.c_R0x[cls] - 2 * sp;
-            float val = 0.f;
-            if (sp < KWc && il < CK && ip < w.Cout && op < w.Cin && r >= 0 && r < w.KH && sx >= 0 && sx < w.KW)
-                val = w.w_orig[(((int64_t)ip * w.Cin + op) * w.KH + r) * w.KW + sx] * inv;
-            dst[e] = val;
         }
     }
 }
 
-// conv_deep.hip images (SisrWeightDesc.wdp_*): [32-channel chunk][tap row][cout][KW * 32 + 8] bf16, element kx * 32 + ci, the 8
-// padding elements zero.  Workgroup = one 32 cout x 32 cin tile of a 3x3 weight: its 32 x 288 floats are read ONCE, as 32
-// contiguous 1,152-byte pieces (the generic pack kernel gathers every element with a 36-byte stride, once per image), pass
-// through LDS and leave as whole rows of every image that is asked for -- forward, data gradient (channels swapped, taps
-// flipped), the four output-parity classes of a stride-2 layer's data gradient.  grid (weights, cout chunks, cin chunks).
+// the rows of image g that the workgroup's tile (cout chunk cb, cin chunk kb, in `tile`) holds, in 16-byte items of 8 bf16: 8
+// consecutive in-channels of one tap column (or the 8 padding slots).  TR is g.transposed as a constant: the LDS strides become
+// instruction offsets, and this loop's time goes to its instructions.
+template <bool TR>
+__device__ __forceinline__ void wimg_deep_rows(const SisrWeightImage& g, const float* tile, int cb, int kb, int Cout, int Cin) {
+    __bf16* dst = reinterpret_cast<__bf16*>(g.dst);
+    const int RW = g.extra * 32 + 8, G8 = RW >> 3;
+    // this tile in the image's view: out block / in block, and where (out oc, in ic) sits in `tile`
+    const int ob = TR ? kb : cb, ib = TR ? cb : kb, n_out = TR ? Cin : Cout;
+    constexpr int so = TR ? 9 : 289, si = TR ? 289 : 9;
+    for (int i = threadIdx.x; i < g.KH * 32 * G8; i += SISR_BLOCK) {
+        const int row = i / G8, k8 = i - row * G8, rp = row >> 5, oc = row & 31, sp = k8 >> 2;
+        const unsigned r = g.R0y + g.Sy * rp, sx = g.R0x + g.Sx * sp;         // (a negative tap is a huge one)
+        const bool ok = (sp < g.KW) & (r < 3u) & (sx < 3u);
+        const float* src = tile + oc * so + (k8 & 3) * 8 * si + (ok ? r * 3 + sx : 0u);
+        float v[8];                                                    // (read for a zero item too: its address is inside the tile)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = src[j * si];
+        const u32x4 q = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+        *reinterpret_cast<u32x4*>(dst + ((unsigned)((ib * g.KH + rp) * n_out + ob * 32 + oc) * RW + k8 * 8)) =
+            ok ? q : u32x4{0u, 0u, 0u, 0u};
+    }
+}
+
+// conv_deep.hip images (SISR_WIMG_DEEP): [32-channel chunk][tap row][out][taps per row * 32 + 8] bf16, element s' * 32 + in, the
+// taps a row has no s' for and its 8 padding elements zero.  Workgroup = one 32 cout x 32 cin tile of a 3x3 weight: its 32 x 288
+// floats are read ONCE, as 32 contiguous 1,152-byte pieces (the generic pack kernel gathers every element with a 36-byte stride,
+// once per image), pass through LDS and leave as whole rows of every image that is asked for -- forward, data gradient (channels
+// swapped, taps flipped), the four output-parity classes of a stride-2 layer's data gradient.  grid (weights, cout chunks, cin chunks).
 __global__ void __launch_bounds__(SISR_BLOCK) weights_pack_deep_kernel(const SisrWeightDesc* table) {
-    __shared__ float tile[32][9 * 32 + 1];                         // [cout][ci * 9 + tap]
-    const SisrWeightDesc w = table[blockIdx.x];
-    if (w.wdp_fwd == nullptr && w.wdp_dgrad == nullptr && w.wdp_dcls[0] == nullptr && w.wdp_dcls[1] == nullptr &&
-        w.wdp_dcls[2] == nullptr && w.wdp_dcls[3] == nullptr)
-        return;
+    __shared__ float tile[32 * (9 * 32 + 1)];                      // [cout][ci * 9 + tap], rows of 289
+    // most workgroups of the grid (sized for the largest weight) lie outside their weight: they leave on its dims alone, before
+    // the records are copied
+    const SisrWeightDesc& t = table[blockIdx.x];
     const int cb = blockIdx.y, kb = blockIdx.z;                    // cout chunk, cin chunk
-    if (cb * 32 >= w.Cout || kb * 32 >= w.Cin || w.KH != 3 || w.KW != 3) return;
-    const float sc = w.wdp_scaled ? 1.f / (w.sigma ? w.sigma[0] : 1.f) : 1.f;
+    if ((cb * 32 >= t.Cout) | (kb * 32 >= t.Cin) | (t.KH != 3) | (t.KW != 3)) return;
+    const SisrWeightDesc w = t;                                    // (by value, image loops unrolled: see weights_pack_kernel)
+    bool any = false;
+#pragma unroll
+    for (int gi = 0; gi < SISR_WEIGHT_IMAGES; ++gi) any |= w.img[gi].dst != nullptr && w.img[gi].format == SISR_WIMG_DEEP;
+    if (!any) return;
+    const int Cout = w.Cout, Cin = w.Cin;
+    const float* sigma = w.wdp_scaled ? w.sigma : nullptr;         // (a select: the pointer comes with the records' batch)
+    const float sc = sigma ? 1.f / sigma[0] : 1.f;
     const int tid = threadIdx.x;
     // 32 couts x 288 contiguous floats (32 ci x 9 taps; 1,152-byte rows: 16-byte aligned), one float4 per item
+    const float* w_orig = w.w_orig;
     for (int i = tid; i < 32 * 72; i += SISR_BLOCK) {
         const int co = i / 72, e4 = i - co * 72;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(w.w_orig + ((int64_t)(cb * 32 + co) * w.Cin + kb * 32) * 9 + e4 * 4);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(w_orig + ((int64_t)(cb * 32 + co) * Cin + kb * 32) * 9 + e4 * 4);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) tile[co][e4 * 4 + j] = v[j] * sc;
+        for (int j = 0; j < 4; ++j) tile[co * 289 + e4 * 4 + j] = v[j] * sc;
     }
     __syncthreads();
-    // every image row is written in 16-byte items of 8 bf16: 8 consecutive channels of one tap column (or the 8 padding slots)
-    auto pack8 = [](const float (&v)[8]) {
-        return u32x4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
-    };
-    constexpr int RW = 3 * 32 + 8, G8 = RW / 8;
-    if (w.wdp_fwd) {
-        // rows (ky, co) of chunk kb: element kx * 32 + ci = tile[co][ci][ky][kx]
-        __bf16* dst = reinterpret_cast<__bf16*>(w.wdp_fwd);
-        for (int i = tid; i < 3 * 32 * G8; i += SISR_BLOCK) {
-            const int row = i / G8, k8 = i - row * G8, ky = row >> 5, co = row & 31;
-            float v[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = k8 < 12 ? tile[co][((k8 & 3) * 8 + j) * 9 + ky * 3 + (k8 >> 2)] : 0.f;
-            *reinterpret_cast<u32x4*>(dst + ((int64_t)(kb * 3 + ky) * w.Cout + cb * 32 + co) * RW + k8 * 8) = pack8(v);
-        }
-    }
-    if (w.wdp_dgrad) {
-        // conv over dy: chunk = cb (over the forward couts), rows (ky', op = ci), element kx' * 32 + co = tile[co][ci][2 - ky'][2 - kx']
-        __bf16* dst = reinterpret_cast<__bf16*>(w.wdp_dgrad);
-        for (int i = tid; i < 3 * 32 * G8; i += SISR_BLOCK) {
-            const int row = i / G8, k8 = i - row * G8, ky = row >> 5, ci = row & 31;
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = k8 < 12 ? tile[(k8 & 3) * 8 + j][ci * 9 + (2 - ky) * 3 + (2 - (k8 >> 2))] : 0.f;
-            *reinterpret_cast<u32x4*>(dst + ((int64_t)(cb * 3 + ky) * w.Cin + kb * 32 + ci) * RW + k8 * 8) = pack8(v);
-        }
-    }
-    for (int cls = 0; cls < 4; ++cls) {
-        __bf16* dst = reinterpret_cast<__bf16*>(w.wdp_dcls[cls]);
-        if (dst == nullptr) continue;
-        const int KHc = w.c_KH[cls], KWc = w.c_KW[cls], RWc = (w.wdp_cls_kw ? w.wdp_cls_kw : KWc) * 32 + 8, G8c = RWc >> 3;
-        for (int i = tid; i < KHc * 32 * G8c; i += SISR_BLOCK) {
-            const int row = i / G8c, k8 = i - row * G8c, rp = row >> 5, ci = row & 31;
-            const int r = w.c_R0y[cls] - 2 * rp, sx = w.c_R0x[cls] - 2 * (k8 >> 2);
-            const bool ok = k8 < KWc * 4 && r >= 0 && r < 3 && sx >= 0 && sx < 3;
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = ok ? tile[(k8 & 3) * 8 + j][ci * 9 + r * 3 + sx] : 0.f;
-            *reinterpret_cast<u32x4*>(dst + ((int64_t)(cb * KHc + rp) * w.Cin + kb * 32 + ci) * RWc + k8 * 8) = pack8(v);
-        }
+    for (int gi = 0; gi < SISR_WEIGHT_IMAGES; ++gi) {
+        const SisrWeightImage& g = w.img[gi];
+        if (g.dst == nullptr || g.format != SISR_WIMG_DEEP) continue;
+        g.transposed ? wimg_deep_rows<true>(g, tile, cb, kb, Cout, Cin) : wimg_deep_rows<false>(g, tile, cb, kb, Cout, Cin);
     }
 }
 
@@ -680,6 +579,14 @@ extern "C" int sisr_weights_prepare(const SisrWeightDesc* table_dev, int32_t n, 
                                     void* stream) {
     if (int e = sisr_weights_sn(table_dev, n, max_rows, max_cols, stream)) return e;
     return sisr_weights_pack(table_dev, n, max_rows, max_cols, stream);
+}
+
+extern "C" int64_t sisr_weight_image_bytes(const SisrWeightImage* g) {
+    if (!g || g->format < SISR_WIMG_F32 || g->format > SISR_WIMG_DEEP || g->KH <= 0 || g->KW <= 0 || g->n_chunk <= 0 || g->CoutPad <= 0 ||
+        g->extra < 0 || (g->format == SISR_WIMG_F32 ? g->KROWP <= 0 || g->PS <= 0 || g->CK <= 0 || g->extra > 2
+                         : g->format == SISR_WIMG_BF16 ? g->CK <= 0 || g->extra > 1 : g->extra < g->KW))
+        return SISR_E_BADARG;
+    return wimg_bytes(*g);
 }
 
 // tiles (= workgroups along grid.y, = dot_work entries) one weight of the table needs; `parts` of sisr_weights_grad must

@@ -311,10 +311,6 @@ class S2x4:
     def __init__(self, desc, classes):
         self.desc, self.classes = desc, classes          # classes[c]: S2Taps, c = 2 py + px
 
-    def image_slots(self, c, cout_fwd, cin_fwd):
-        """fp32 slots of class c's weight image [cout_fwd / 32][taps y][cin_fwd][2 * 32 + 8] bf16 (KW = 2 row format)"""
-        return ((cout_fwd // 32) * self.classes[c].kh * cin_fwd * 72 + 1) // 2
-
 
 DG_NONE, DG_CONV, DG_CLASSES, DG_X4 = 'none', 'conv', 'classes', 'x4'
 
@@ -354,8 +350,8 @@ class Prepared:
 
 
 def _trunk_ldsimg(gm, plan_f, plan_d, kinds):
-    """(forward, data-gradient) mode of the LDS-order weight image of the fp32-tensor trunk conv (SisrWeightDesc.f_ldsimg /
-    d_ldsimg): 0 none, 1 fp32 values, 2 split pairs -- for 3x3 64 -> 64 convs on the fp32 kernels"""
+    """(forward, data-gradient) mode of the LDS-order weight image of the fp32-tensor trunk conv (SISR_WIMG_F32's
+    `extra`): 0 none, 1 fp32 values, 2 split pairs -- for 3x3 64 -> 64 convs on the fp32 kernels"""
     if gm.k != 3 or gm.cin != 64 or gm.cout != 64 or gm.stride != 1:
         return 0, 0
     mode = 2 if mfma_split() else 1
@@ -367,7 +363,7 @@ def _trunk_ldsimg(gm, plan_f, plan_d, kinds):
 
 def _trunk_lanes(gm, plan_f, plan_d, kinds):
     """(forward, data-gradient): the bf16 weight buffer also gets the lane-order image of the persistent trunk kernels
-    (SisrWeightDesc.bf_f_lanes / bf_d_lanes) -- only where those kernels can take the layer: 3x3, stride 1, 64 input channels,
+    (SISR_WIMG_BF16's `extra`) -- only where those kernels can take the layer: 3x3, stride 1, 64 input channels,
     64 couts (or the 256 of the upscale conv) on the generic bf16 family (Kind.BF16, not the deep family)"""
     if gm.k != 3 or gm.stride != 1:
         return False, False
@@ -375,16 +371,6 @@ def _trunk_lanes(gm, plan_f, plan_d, kinds):
     ld = (kinds[1] == Kind.BF16 and _dgrad_shape(plan_d) == DG_CONV and gm.cout == 64 and gm.cin == 64
           and plan_d.plan.CK == 32 and plan_d.plan.CoutPad == 64)
     return lf, ld
-
-
-def _img_slots(desc, kind, lanes=False, ldsimg=0):
-    """fp32 slots of one packed weight image: conv_deep.hip's bf16 image, the generic bf16 image (twice with the lane-order copy)
-    or the fp32 image (plus the LDS-order copy)"""
-    if kind == Kind.DEEP:
-        return (desc.deep.wimg_elems + 1) // 2
-    if kind == Kind.BF16:
-        return ((desc.plan.wpk_elems + 1) // 2) * (2 if lanes else 1)
-    return desc.plan.wpk_elems + (L.WLDS_WORDS if ldsimg else 0)
 
 
 _WEIGHT_EPOCH = [0]
@@ -398,115 +384,95 @@ def invalidate_weight_caches():
     _WEIGHT_EPOCH[0] += 1
 
 
+# one packed image of a layer: `slots` floats at `off` of buffer 'b' | 'd', written as its SisrWeightImage `rec` (dst unset) says
+ImageSpec = namedtuple('ImageSpec', 'buf off slots rec')
+
+
+def _image_rec(desc, kind, taps, transposed, ldsimg=0, lanes=False, row_taps=None):
+    """the SisrWeightImage of one role of a layer: desc / kind the consumer's descriptor and Kind, taps = (KH', KW', R0y, Sy, R0x, Sx)
+    its tap map (include/sisr_hip.h); ldsimg: the LDS-order mode, read for an fp32 image only; lanes: the lane-order copy, read for
+    a bf16 image only; row_taps: taps per row of a conv_deep.hip image where they are not its own KW"""
+    g = L.WeightImage()
+    g.transposed = int(transposed)
+    g.KH, g.KW, g.R0y, g.Sy, g.R0x, g.Sx = taps
+    if Kind(kind).deep:
+        g.format, g.CK, g.n_chunk, g.CoutPad, g.extra = L.WIMG_DEEP, 32, desc.Cin // 32, desc.Cout, row_taps or g.KW
+    else:
+        g.format, g.extra = (L.WIMG_BF16, int(bool(lanes))) if kind == Kind.BF16 else (L.WIMG_F32, int(ldsimg))
+        for n in ('CK', 'PS', 'KROWP', 'n_chunk', 'CoutPad'):
+            setattr(g, n, getattr(desc.plan, n))
+    return g
+
+
 def _layout_weights(items, need_dgrad):
     """Host-only pass of prepare_weights (no device call): per layer a Prepared with plans, kinds, lanes, ldsimg and offs[i] =
-    (forward image, data-gradient image(s) | None, sigma block, power-iteration scratch): an image is (buffer, offset, slots),
-    the last two are offsets into 's'.  sizes: fp32 slots of 'b' (images rebuilt on every call), 'd' (conv_deep.hip's), 's'."""
+    (images, sigma block, power-iteration scratch): images[k] is the ImageSpec | None of SisrWeightDesc.img[k] -- the forward image,
+    then the stride-1 data gradient or the four parity classes of a stride-2 one --, its length the library's own answer; the
+    last two are offsets into 's'.  sizes: fp32 slots of 'b' (images rebuilt on every call), 'd' (conv_deep.hip's), 's'."""
+    lib = L.lib()
     sizes = {'b': 0, 'd': 0, 's': 0}
 
     def take(buf, n):
         off = sizes[buf]
-        sizes[buf] += n
+        sizes[buf] += _align4(n)                       # every piece starts on 16 bytes
         return (buf, off, n)
 
-    def image(desc, kind, lanes=False, ldsimg=0):
-        return take('d' if kind == Kind.DEEP else 'b', _align4(_img_slots(desc, kind, lanes, ldsimg)))
+    def image(desc, kind, taps, transposed, **copy):
+        rec = _image_rec(desc, kind, taps, transposed, **copy)
+        nbytes = L.check_count(lib.sisr_weight_image_bytes(C.byref(rec)), 'sisr_weight_image_bytes')
+        return ImageSpec(*take('d' if rec.format == L.WIMG_DEEP else 'b', (nbytes + 3) // 4), rec)
     preps, offs = [], []
     for ref, n, h, w in items:
         gm = ref.geom
+        k = gm.k
         p = Prepared()
         f, d, g, p.kinds = gm.plans(n, h, w)
         p.ref, p.plans = ref, (f, d, g)
         p.lanes = _trunk_lanes(gm, f, d, p.kinds)
         p.ldsimg = _trunk_ldsimg(gm, f, d, p.kinds)
-        off_f = image(f, p.kinds[0], p.lanes[0], p.ldsimg[0])
+        imgs = [image(f, p.kinds[0], (k, k, 0, 1, 0, 1), False, ldsimg=p.ldsimg[0], lanes=p.lanes[0])] + [None] * 4
         shape = _dgrad_shape(d) if need_dgrad else DG_NONE
-        off_d = None
         if shape == DG_X4:
-            off_d = [take('d', _align4(d.image_slots(c, gm.cout, gm.cin))) for c in range(4)]
+            imgs[1:] = [image(d.desc, Kind.DEEP, (t.kh, t.kw, t.r0y, -2, t.r0x, -2), True, row_taps=2) for t in d.classes]
         elif shape == DG_CLASSES:
-            off_d = [None if c is None else image(c.desc, c.kind) for c in d]
+            imgs[1:] = [c and image(c.desc, c.kind, (c.desc.KH, c.desc.KW, c.r0y, -2, c.r0x, -2), True) for c in d]
         elif shape == DG_CONV:
-            off_d = image(d, p.kinds[1], p.lanes[1], p.ldsimg[1])
+            imgs[1] = image(d, p.kinds[1], (k, k, k - 1, -1, k - 1, -1), True, ldsimg=p.ldsimg[1], lanes=p.lanes[1])
         rows, cols = gm.cout, gm.cin * gm.k * gm.k
         sn = ref.u is not None
         off_s = take('s', 4 + (_align4(rows) + _align4(cols) if sn else 0))[1]
         off_w = take('s', _align4((rows + 15) // 16 * cols + rows) if sn else 0)[1]     # power-iteration scratch: [ceil(rows/16)][cols] + [rows]
         preps.append(p)
-        offs.append((off_f, off_d, off_s, off_w))
+        offs.append((imgs, off_s, off_w))
     return preps, offs, sizes
-
-
-# SisrWeightDesc fields of the two whole-conv roles: (deep image, bf16 image, prefix of its CoutPad / CK / lanes, fp32 image,
-# its LDS-order mode, prefix of its plan fields)
-_ROLE_FIELDS = (('wdp_fwd', 'wbf_fwd', 'bf_f_', 'wpk_fwd', 'f_ldsimg', 'f_'),
-                ('wdp_dgrad', 'wbf_dgrad', 'bf_d_', 'wpk_dgrad', 'd_ldsimg', 'd_'))
-_PLAN_FIELDS = ('CK', 'PS', 'KROWP', 'n_chunk', 'CoutPad')
-
-
-def _fill_role(t, role, desc, kind, image, lanes, ldsimg, deep_hit):
-    """the image of one whole-conv role (0 forward, 1 stride-1 data gradient) -> it is a conv_deep.hip image"""
-    wdp, wbf, bf, wpk, lds, pl = _ROLE_FIELDS[role]
-    if kind == Kind.DEEP:
-        vals = () if deep_hit else ((wdp, image.data_ptr()),)
-    elif kind == Kind.BF16:
-        vals = ((wbf, image.data_ptr()), (bf + 'CoutPad', desc.plan.CoutPad), (bf + 'CK', desc.plan.CK), (bf + 'lanes', int(lanes)))
-    else:
-        vals = ((wpk, image.data_ptr()), (lds, ldsimg)) + tuple((pl + n, getattr(desc.plan, n)) for n in _PLAN_FIELDS)
-    for n, v in vals:
-        setattr(t, n, v)
-    return kind == Kind.DEEP
-
-
-def _fill_classes(t, classes, images, deep_hit):
-    """the images of a stride-2 data gradient's four parity classes -> any is a conv_deep.hip image"""
-    has_deep = False
-    for ci, (c, buf) in enumerate(zip(classes, images)):
-        if c is None:
-            continue
-        t.c_KH[ci], t.c_KW[ci], t.c_R0y[ci], t.c_R0x[ci] = c.desc.KH, c.desc.KW, c.r0y, c.r0x
-        if c.kind == Kind.DEEP:
-            has_deep = True
-            if not deep_hit:
-                t.wdp_dcls[ci] = buf.data_ptr()
-        elif c.kind == Kind.BF16:
-            t.wbf_dcls[ci], t.bf_c_CoutPad[ci] = buf.data_ptr(), c.desc.plan.CoutPad
-        else:
-            t.wpk_dcls[ci] = buf.data_ptr()
-            for n in _PLAN_FIELDS:
-                getattr(t, 'c_' + n)[ci] = getattr(c.desc.plan, n)
-    return has_deep
 
 
 def _fill_weight_desc(t, p, off, bufs, training, deep_hit):
     """SisrWeightDesc `t` of one layer and the views of its Prepared `p`, from its layout record and the base tensors bufs['b' | 'd'
     | 's'].  deep_hit: the conv_deep.hip images are cached: not packed again (null pointers).  -> the layer has such an image"""
-    off_f, off_d, off_s, off_w = off
-    ref, gm, (f, d, _) = p.ref, p.ref.geom, p.plans
+    imgs, off_s, off_w = off
+    ref, gm, d = p.ref, p.ref.geom, p.plans[1]
     sm = bufs['s']
-
-    def view(o):
-        return None if o is None else bufs[o[0]][o[1]:o[1] + o[2]]
-    shape = _dgrad_shape(d) if off_d is not None else DG_NONE      # (need_dgrad=False: no data-gradient image is packed)
-    p.wpk_fwd = view(off_f)
-    p.wpk_dgrad = [view(o) for o in off_d] if shape in (DG_X4, DG_CLASSES) else view(off_d)
+    views, has_deep = [None] * len(imgs), False
+    for i, s in enumerate(imgs):
+        if s is None:
+            continue
+        views[i] = bufs[s.buf][s.off:s.off + s.slots]
+        t.img[i] = s.rec
+        deep = s.rec.format == L.WIMG_DEEP
+        has_deep |= deep
+        if not (deep and deep_hit):
+            t.img[i].dst = views[i].data_ptr()
+    p.wpk_fwd = views[0]
+    if all(s is None for s in imgs[1:]):               # (need_dgrad=False: no data-gradient image is packed)
+        p.wpk_dgrad = None
+    else:
+        p.wpk_dgrad = views[1:] if _dgrad_shape(d) in (DG_X4, DG_CLASSES) else views[1]
     p.sigma = sm[off_s:off_s + 1]
     p.inv_sigma = sm[off_s + 1:off_s + 2]          # written next to sigma: the conv_deep.hip epilogue scale
     t.w_orig, t.sigma, t.wdp_scaled = ref.weight.data_ptr(), p.sigma.data_ptr(), 0
     t.Cout, t.Cin, t.KH, t.KW = gm.cout, gm.cin, gm.k, gm.k
     t.training, t.shuffle2 = int(training), int(gm.shuffle2)
-    has_deep = _fill_role(t, 0, f, p.kinds[0], p.wpk_fwd, p.lanes[0], p.ldsimg[0], deep_hit)
-    if shape == DG_X4:
-        has_deep = True
-        t.wdp_cls_kw = 2
-        for ci, (taps, buf) in enumerate(zip(d.classes, p.wpk_dgrad)):
-            t.c_KH[ci], t.c_KW[ci], t.c_R0y[ci], t.c_R0x[ci] = taps
-            if not deep_hit:
-                t.wdp_dcls[ci] = buf.data_ptr()
-    elif shape == DG_CLASSES:
-        has_deep |= _fill_classes(t, d, p.wpk_dgrad, deep_hit)
-    elif shape == DG_CONV:
-        has_deep |= _fill_role(t, 1, d, p.kinds[1], p.wpk_dgrad, p.lanes[1], p.ldsimg[1], deep_hit)
     p.u_used = p.v_used = None
     if ref.u is not None:
         rows, cols = gm.cout, gm.cin * gm.k * gm.k

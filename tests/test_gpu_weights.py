@@ -368,17 +368,12 @@ def _pack_layers(E):
 
 
 def _images(E, p):
-    """[(name, the written floats of the image)] of one Prepared"""
-    f, d, _ = p.plans
-    out = [('fwd', p.wpk_fwd[:E._img_slots(f, p.kinds[0], p.lanes[0], p.ldsimg[0])])]
-    shape = E._dgrad_shape(d)
-    if shape == E.DG_CONV:
-        out.append(('dgrad', p.wpk_dgrad[:E._img_slots(d, p.kinds[1], p.lanes[1], p.ldsimg[1])]))
-    elif shape == E.DG_X4:
-        gm = p.ref.geom
-        out += [('dgrad class %d' % c, p.wpk_dgrad[c][:d.image_slots(c, gm.cout, gm.cin)]) for c in range(4)]
-    elif shape == E.DG_CLASSES:
-        out += [('dgrad class %d' % c, p.wpk_dgrad[c][:E._img_slots(cl.desc, cl.kind)]) for c, cl in enumerate(d) if cl is not None]
+    """[(name, the written floats of the image)] of one Prepared: a view is exactly as long as its image"""
+    out = [('fwd', p.wpk_fwd)]
+    if isinstance(p.wpk_dgrad, list):
+        out += [('dgrad class %d' % c, v) for c, v in enumerate(p.wpk_dgrad) if v is not None]
+    elif p.wpk_dgrad is not None:
+        out.append(('dgrad', p.wpk_dgrad))
     out += [('sigma', p.sigma), ('inv_sigma', p.inv_sigma)]
     if p.u_used is not None:
         out += [('u_used', p.u_used), ('v_used', p.v_used)]
@@ -441,9 +436,11 @@ def test_prepare_is_the_power_iteration_then_the_pack(L, E):
     img = Buf(plan.wpk_elems)
     table = (L.WeightDesc * 1)()
     p.fill(table[0])
-    table[0].wpk_fwd = img.ptr()
+    g = table[0].img[0]
+    g.dst, g.format, g.KH, g.KW, g.Sy, g.Sx = img.ptr(), L.WIMG_F32, k, k, 1, 1
     for n in WC.PLAN_FIELDS:
-        setattr(table[0], 'f_' + n, getattr(plan, n))
+        setattr(g, n, getattr(plan, n))
+    assert L.lib().sisr_weight_image_bytes(C.byref(g)) == 4 * plan.wpk_elems
     tab = _table(E, table)
     run2(lambda: L.lib().sisr_weights_prepare(tab.data_ptr(), 1, p.rows, p.cols, _st()), p.outs + [img])
     got = p.results()

@@ -100,3 +100,94 @@ def test_epilogue_inputs_meet_their_conditions(shape, layout, seed):
         assert c.plan['CK'] == 32 and c.plan['n_chunk'] == 2          # second chunk ragged: 8 channels
     if (shape, layout) == ((64, 3, 9, 0), 0):
         assert c.tg == 10 and 81 % 10 == 1                            # nine tap groups, the last holds one tap
+
+
+# ---- packed weight images: what tests/test_gpu_weight_images.py needs without a device ---------------------------------------------
+@pytest.fixture(scope='module')
+def E():
+    return importlib.import_module('single-image-super-resolution_amd.engine')
+
+
+@pytest.mark.parametrize('build', ['fp32', 'bf16x3', 'bf16'])
+def test_image_references_have_the_images_sizes_and_count_every_padding_slot(E, build):
+    """every layer of the image table reaches the format it is listed for; each reference image is as long as the engine's size
+    formulas say (plan.wpk_elems + the LDS-order words, ceil(wpk_elems / 2) twice with the lane-order copy, ceil(wimg_elems / 2), the
+    KW = 2 rows of the one-launch stride-2 plan), and its standard order holds exactly one element per (cout, cin, forward tap the
+    image reaches) -- every other slot is a zero the comparison counts"""
+    import torch
+    n_images = 0
+    for i, (gm, _, p) in enumerate(WC.image_layers(E, build)):
+        WC.check_reach(E, build, i, p)
+        wm = WC.sn_inputs((gm.cout, gm.cin, gm.k), seed=60 + i)[0]
+        w4 = wm.reshape(gm.cout, gm.cin, gm.k, gm.k)
+        assert bool((w4.to(torch.bfloat16) != 0).all())
+        for spec in WC.image_specs(E, p):
+            if spec is None:
+                continue
+            slots, std = WC.expected_image(spec, w4, torch.tensor(0.75), gm.shuffle2)
+            assert slots.numel() == spec.old_slots, (build, i, spec.name, slots.numel(), spec.old_slots)
+            kh, kw, r0y, sy, r0x, sx = spec.taps
+            reached = sum(0 <= r0y + sy * a < gm.k for a in range(kh)) * sum(0 <= r0x + sx * b < gm.k for b in range(kw))
+            assert int((std != 0).sum()) == gm.cout * gm.cin * reached, (build, i, spec.name)
+            n_images += 1
+    assert n_images == {'fp32': 15, 'bf16x3': 2, 'bf16': 23}[build]
+
+
+def _plan_digest_layers():
+    """the layer list of tools/plan_digest.py (imported from the module the tool imports it from: the lists cannot drift apart)"""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location(
+        'plan_layers', os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools', 'plan_layers.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return list(mod.LAYERS)
+
+
+@pytest.mark.parametrize('build', ['fp32', 'bf16x3', 'bf16'])
+def test_library_image_sizes_equal_the_engines_former_formulas(E, L, build):
+    """sisr_weight_image_bytes, the one place that knows an image's size, against the formulas the engine used to carry (they live
+    on in weights_cases.image_specs): every image of the fourteen layers of the image table and of tools/plan_digest.py's layer
+    list, and the layout's (offset, length) records, which must tile the buffers in 16-byte steps"""
+    layers = [(cin, cout, k, s, bool(sh), False, 2, h, w) for cin, cout, k, s, sh, h, w in WC.IMAGE_CASES[build]] + _plan_digest_layers()
+    assert len(layers) == len(WC.IMAGE_CASES[build]) + 17
+    before = E.PRECISION
+    E.set_precision(build)
+    try:
+        items = [(E.ConvRef(E.ConvGeom(cin, cout, k, s, shuffle2=sh, deep_dgrad=dd), None, None), n, h, w)
+                 for cin, cout, k, s, sh, dd, n, h, w in layers]
+        preps, offs, sizes = E._layout_weights(items, True)
+        used, n_images = {'b': 0, 'd': 0}, 0
+        for p, (imgs, _, _) in zip(preps, offs):
+            specs = WC.image_specs(E, p)
+            assert [s is None for s in specs] == [i is None for i in imgs]
+            for spec, img in zip(specs, imgs):
+                if spec is None:
+                    continue
+                assert L.lib().sisr_weight_image_bytes(C.byref(img.rec)) == 4 * spec.old_slots, (build, spec.name)
+                assert img.slots == spec.old_slots and img.buf == ('d' if spec.fmt == WC.IMG_DEEP else 'b')
+                assert img.off == used[img.buf] and img.off % 4 == 0
+                used[img.buf] += (img.slots + 3) & ~3
+                n_images += 1
+        assert (used['b'], used['d']) == (sizes['b'], sizes['d']) and n_images >= 2 * len(layers)
+    finally:
+        E.set_precision(before)
+
+
+def test_weight_image_bytes_rejects_records_no_kernel_packs(L):
+    def rec(**kw):
+        g = L.WeightImage()
+        g.format, g.KH, g.KW, g.CK, g.PS, g.KROWP, g.n_chunk, g.CoutPad = L.WIMG_F32, 3, 3, 32, 33, 100, 2, 64
+        for n, v in kw.items():
+            setattr(g, n, v)
+        return g
+    lib = L.lib()
+    assert lib.sisr_weight_image_bytes(None) == BADARG
+    assert lib.sisr_weight_image_bytes(C.byref(rec())) == 4 * 2 * 3 * 64 * 100          # dst is not read
+    assert lib.sisr_weight_image_bytes(C.byref(rec(extra=2))) == 4 * (2 * 3 * 64 * 100 + 2 * 2 * 9 * 32 * 36)
+    assert lib.sisr_weight_image_bytes(C.byref(rec(format=L.WIMG_BF16, extra=1))) == 2 * 2 * (2 * 64 * 9 * 32)
+    assert lib.sisr_weight_image_bytes(C.byref(rec(format=L.WIMG_DEEP, KH=2, KW=1, extra=2))) == 2 * (2 * 2 * 64 * 72)
+    for bad in (dict(format=3), dict(format=-1), dict(KH=0), dict(KW=-3), dict(n_chunk=0), dict(CoutPad=0), dict(KROWP=0), dict(PS=0),
+                dict(CK=0), dict(extra=3), dict(extra=-1), dict(format=L.WIMG_BF16, extra=2), dict(format=L.WIMG_BF16, CK=0),
+                dict(format=L.WIMG_DEEP, extra=2), dict(format=L.WIMG_DEEP, extra=0)):
+        assert lib.sisr_weight_image_bytes(C.byref(rec(**bad))) == BADARG, bad

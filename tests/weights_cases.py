@@ -270,3 +270,233 @@ def case_of(shape, layout):
         if s == shape and lay == layout:
             return grad_case(s, lay, seed)
     raise KeyError((shape, layout))
+
+
+# ---- c. packed weight images ----------------------------------------------------------------------------------------------------
+# Every image the pack kernels write is ONE gather under one tap map, laid out in one of five storage orders (include/sisr_hip.h):
+# element (out, in, r', s') of an image holds forward tap (R0y + Sy r', R0x + Sx s') of the weight -- zero outside it -- with
+#   (R0, S) = (0, +1)        the forward image                      out = packed cout, in = cin
+#             (K - 1, -1)    the stride-1 data gradient             out = cin, in = packed cout  ("transposed")
+#             (c_R0, -2)     one parity class of a stride-2 one     out = cin, in = cout
+# (build, [(cin, cout, k, stride, shuffle2, h, w)]), n = 2: what each layer reaches is asserted by tests/test_gpu_weight_images.py
+IMAGE_CASES = {
+    'fp32': [(64, 64, 3, 1, 0, 16, 16), (64, 256, 3, 1, 1, 16, 16), (3, 64, 9, 1, 0, 16, 16), (64, 3, 3, 1, 0, 16, 16),
+             (40, 48, 3, 1, 0, 16, 16), (64, 64, 3, 2, 0, 16, 16)],
+    'bf16x3': [(64, 64, 3, 1, 0, 16, 16)],
+    'bf16': [(64, 64, 3, 1, 0, 16, 16), (64, 256, 3, 1, 1, 16, 16), (64, 3, 3, 1, 0, 16, 16), (32, 64, 3, 2, 0, 16, 16),
+             (64, 64, 3, 2, 0, 16, 16), (64, 64, 3, 2, 0, 15, 15), (64, 64, 3, 1, 0, 12, 12)],
+}
+IMG_F32, IMG_BF16, IMG_DEEP = 0, 1, 2
+WLDS_WORDS = 2 * 2 * 9 * 32 * 36
+I32, BF16 = torch.int32, torch.bfloat16
+
+
+class ImageSpec:
+    """one image of a layer as the host planner decided it.  fmt: IMG_*; transposed: out = cin; taps = (KH', KW', R0y, Sy, R0x, Sx);
+    plan: the SisrConvPlan fields of the role's descriptor (fp32 and bf16 orders); copy: LDS-order mode (fp32) or lane-order copy
+    (bf16); row_taps: taps per row of the conv_deep.hip row format; old_slots: fp32 slots by the formulas of the engine before
+    the library answered the question itself"""
+
+    def __init__(self, name, fmt, transposed, taps, plan=None, copy=0, row_taps=0, old_slots=0):
+        self.name, self.fmt, self.transposed, self.taps, self.plan = name, fmt, transposed, taps, plan
+        self.copy, self.row_taps, self.old_slots = int(copy), row_taps, old_slots
+
+
+def image_specs(E, p):
+    """[ImageSpec | None] x 5 of one Prepared (plans, kinds, lanes, ldsimg; no device): forward, then the stride-1 data gradient or
+    the four parity classes of a stride-2 one"""
+    gm, (f, d, _) = p.ref.geom, p.plans
+    k = gm.k
+
+    def spec(name, desc, kind, taps, transposed, lanes=False, ldsimg=0, row_taps=None):
+        plan = {n: getattr(desc.plan, n) for n in PLAN_FIELDS}
+        if E.Kind(kind).deep:
+            rows = row_taps or desc.KW
+            old = (desc.deep.wimg_elems + 1) // 2 if row_taps is None else ((gm.cout // 32) * taps[0] * gm.cin * 72 + 1) // 2
+            return ImageSpec(name, IMG_DEEP, transposed, taps, row_taps=rows, old_slots=old)
+        if kind == E.Kind.BF16:
+            return ImageSpec(name, IMG_BF16, transposed, taps, plan, lanes, old_slots=((desc.plan.wpk_elems + 1) // 2) * (2 if lanes else 1))
+        return ImageSpec(name, IMG_F32, transposed, taps, plan, ldsimg, old_slots=desc.plan.wpk_elems + (WLDS_WORDS if ldsimg else 0))
+    out = [spec('fwd', f, p.kinds[0], (k, k, 0, 1, 0, 1), False, p.lanes[0], p.ldsimg[0])] + [None] * 4
+    shape = E._dgrad_shape(d)
+    if shape == E.DG_CONV:
+        out[1] = spec('dgrad', d, p.kinds[1], (k, k, k - 1, -1, k - 1, -1), True, p.lanes[1], p.ldsimg[1])
+    elif shape == E.DG_X4:
+        for c, t in enumerate(d.classes):
+            out[1 + c] = spec('dgrad class %d' % c, d.desc, E.Kind.DEEP, (t.kh, t.kw, t.r0y, -2, t.r0x, -2), True, row_taps=2)
+    elif shape == E.DG_CLASSES:
+        for c, cl in enumerate(d):
+            if cl is not None:
+                out[1 + c] = spec('dgrad class %d' % c, cl.desc, cl.kind, (cl.desc.KH, cl.desc.KW, cl.r0y, -2, cl.r0x, -2), True)
+    return out
+
+
+def image_values(w4, shuffle2, transposed, taps):
+    """the one gather: V[out][in][r'][s'] = w4[cout][cin][R0y + Sy r'][R0x + Sx s'] or 0 outside the weight, cout in packed order"""
+    cout, cin, kh_w, kw_w = w4.shape
+    kh, kw, r0y, sy, r0x, sx = taps
+    wp = w4[packed_order(cout, shuffle2)]
+    v = torch.zeros(cout, cin, kh, kw, dtype=F32)
+    for rp in range(kh):
+        for sp in range(kw):
+            r, s = r0y + sy * rp, r0x + sx * sp
+            if 0 <= r < kh_w and 0 <= s < kw_w:
+                v[:, :, rp, sp] = wp[:, :, r, s]
+    return v.transpose(0, 1).contiguous() if transposed else v
+
+
+def order_f32(v, plan):
+    """fp32 [chunk of CK in][r'][out, CoutPad][krow = s' * PS + (in - chunk * CK), KROWP]; every other slot zero"""
+    n_out, n_in, kh, kw = v.shape
+    CK, PS, KROWP, n_chunk, CoutPad = (plan[n] for n in PLAN_FIELDS)
+    assert n_chunk == cdiv(n_in, CK) and kw * PS <= KROWP and CK <= PS and n_out <= CoutPad
+    out = torch.zeros(n_chunk, kh, CoutPad, KROWP, dtype=F32)
+    for ch in range(n_chunk):
+        n = min(CK, n_in - ch * CK)
+        dst = out[ch, :, :, :kw * PS].view(kh, CoutPad, kw, PS)
+        dst[:, :n_out, :, :n] = v[:, ch * CK:ch * CK + n].permute(2, 0, 3, 1)
+    return out.reshape(-1)
+
+
+def order_bf16(v, plan):
+    """bf16 [chunk of CK in][out, CoutPad][tap * CK + (in - chunk * CK)], RNE; rows out >= the channel count zero"""
+    n_out, n_in, kh, kw = v.shape
+    CK, CoutPad = plan['CK'], plan['CoutPad']
+    assert n_in % CK == 0 and n_out <= CoutPad and plan['n_chunk'] == n_in // CK and plan['KROWP'] == kh * kw * CK
+    out = torch.zeros(n_in // CK, CoutPad, kh * kw, CK, dtype=F32)
+    out[:, :n_out] = v.reshape(n_out, n_in // CK, CK, kh * kw).permute(1, 0, 3, 2)
+    return out.reshape(-1).to(BF16)
+
+
+def order_lanes(v, plan):
+    """the persistent trunk kernels' load order: [32-out block][tap][k slice j][lane = kk * 32 + out][8] bf16, in-channel
+    (j >> 1) * 32 + (j & 1) * 16 + 8 kk + el"""
+    n_out, n_in, kh, kw = v.shape
+    CoutPad = plan['CoutPad']
+    assert (n_in, kh, kw) == (64, 3, 3) and CoutPad % 32 == 0
+    vp = torch.zeros(CoutPad, 64, 9, dtype=F32)
+    vp[:n_out] = v.reshape(n_out, 64, 9)
+    blk, tap, j, lane, el = torch.meshgrid(torch.arange(CoutPad // 32), torch.arange(9), torch.arange(4), torch.arange(64),
+                                           torch.arange(8), indexing='ij')
+    return vp[blk * 32 + (lane & 31), (j >> 1) * 32 + (j & 1) * 16 + 8 * (lane >> 5) + el, tap].reshape(-1).to(BF16)
+
+
+def _bits16(t):
+    return t.to(BF16).view(torch.int16).to(torch.int64) & 0xffff
+
+
+def _word(lo16, hi16):
+    """two 16-bit patterns (int64) -> the int32 with the same 32 bits"""
+    x = lo16 | (hi16 << 16)
+    return (x - ((x >> 31) << 32)).to(I32)
+
+
+def order_lds(v, mode):
+    """the fp32-tensor trunk conv's LDS order: 32-bit words [out half][in half q][tap][out 32][32 + 4]; mode 1: word wd < 32 the fp32
+    value of in-channel 32 q + wd; mode 2: words 0..15 the RNE bf16 heads of in-channels (32 q + 2 m, + 1) (low, high half),
+    words 16..31 the bf16 of what the heads leave; words 32..35 zero"""
+    assert tuple(v.shape) == (64, 64, 3, 3) and mode in (1, 2)
+    x = v.reshape(2, 32, 2, 32, 9).permute(0, 2, 4, 1, 3).contiguous()              # [hc][q][tap][co][in 32]
+    out = torch.zeros(2, 2, 9, 32, 36, dtype=I32)
+    if mode == 1:
+        out[..., :32] = x.view(I32)
+    else:
+        hi = x.to(BF16)
+        lo = (x - hi.float()).to(BF16)
+        for half, t in ((0, hi), (16, lo)):
+            b = _bits16(t)
+            out[..., half:half + 16] = _word(b[..., 0::2], b[..., 1::2])
+    return out.reshape(-1)
+
+
+def order_deep(v, row_taps):
+    """conv_deep.hip rows: bf16 [chunk of 32 in][r'][out][row_taps * 32 + 8], element s' * 32 + (in - chunk * 32); the taps a row
+    has no s' for and the 8 padding elements zero"""
+    n_out, n_in, kh, kw = v.shape
+    assert n_in % 32 == 0 and kw <= row_taps
+    out = torch.zeros(n_in // 32, kh, n_out, row_taps * 32 + 8, dtype=F32)
+    out[..., :kw * 32] = v.reshape(n_out, n_in // 32, 32, kh, kw).permute(1, 3, 0, 4, 2).reshape(n_in // 32, kh, n_out, kw * 32)
+    return out.reshape(-1).to(BF16)
+
+
+def _slots(t):
+    """any storage order as the 32-bit slots of the fp32 buffer it lives in"""
+    if t.dtype == BF16:
+        assert t.numel() % 2 == 0
+    return t.contiguous().view(I32)
+
+
+def expected_image(spec, w4, inv, shuffle2):
+    """the 32-bit slots of one image: w4 the OIHW weight, inv = fl(1 / sigma) as an fp32 tensor (None: W_orig itself).
+    fl32(W_orig * inv): one IEEE product per element -> (slots, elements of the standard order that hold a weight)"""
+    scaled = w4 if inv is None else w4 * inv
+    v = image_values(scaled, shuffle2, spec.transposed, spec.taps)
+    if spec.fmt == IMG_DEEP:
+        std = order_deep(v, spec.row_taps)
+        parts = [std]
+    elif spec.fmt == IMG_BF16:
+        std = order_bf16(v, spec.plan)
+        parts = [std] + ([order_lanes(v, spec.plan)] if spec.copy else [])
+    else:
+        std = order_f32(v, spec.plan)
+        parts = [std] + ([order_lds(v, spec.copy)] if spec.copy else [])
+    return torch.cat([_slots(x) for x in parts]), std
+
+
+def image_layers(E, build):
+    """the layers of IMAGE_CASES[build] planned under that build: [(geometry, (n, h, w), Prepared of _layout_weights)]"""
+    before = E.PRECISION
+    E.set_precision(build)
+    try:
+        out = []
+        for cin, cout, k, stride, shuffle2, h, w in IMAGE_CASES[build]:
+            gm = E.ConvGeom(cin, cout, k, stride, shuffle2=bool(shuffle2))
+            ref = E.ConvRef(gm, None, None)
+            out.append((gm, (2, h, w), E._layout_weights([(ref, 2, h, w)], True)[0][0]))
+        return out
+    finally:
+        E.set_precision(before)
+
+
+def check_reach(E, build, i, p):
+    """what layer i of IMAGE_CASES[build] must reach for its images to cover the format they are listed for (host planner facts)"""
+    K = E.Kind
+    f, d, _ = p.plans
+    shape = E._dgrad_shape(d)
+    plan = {n: getattr(f.plan, n) for n in PLAN_FIELDS}
+    what = (build, i, tuple(int(k) for k in p.kinds), p.lanes, p.ldsimg, shape, plan)
+    if build in ('fp32', 'bf16x3'):
+        assert p.kinds[0] == K.F32 and p.kinds[1] == K.F32 and p.lanes == (False, False), what
+    if build == 'bf16x3':
+        assert shape == E.DG_CONV and p.ldsimg == (2, 2), what
+    elif build == 'fp32':
+        if i == 0:
+            assert shape == E.DG_CONV and p.ldsimg == (1, 1), what
+        elif i in (1, 2, 3, 4):
+            assert shape == E.DG_CONV and p.ldsimg == (0, 0), what
+            if i == 2:
+                assert (plan['CK'], plan['PS'], plan['KROWP']) == (3, 3, 28) and d.Cout == 3, what
+            if i == 3:
+                assert plan['CoutPad'] == 32, what
+            if i == 4:
+                assert (plan['CK'], plan['n_chunk']) == (32, 2), what
+        else:
+            assert shape == E.DG_CLASSES and all(c is not None and c.kind == K.F32 for c in d), what
+            assert sorted((c.desc.KH, c.desc.KW) for c in d) == [(1, 1), (1, 2), (2, 1), (2, 2)], what
+    else:
+        if i == 0:
+            assert p.kinds[:2] == (K.BF16, K.BF16) and shape == E.DG_CONV and p.lanes == (True, True), what
+        elif i == 1:
+            assert p.kinds[:2] == (K.BF16, K.BF16) and shape == E.DG_CONV and p.lanes == (True, False) and plan['CoutPad'] == 256, what
+        elif i == 2:
+            assert p.kinds[:2] == (K.BF16, K.F32) and shape == E.DG_CONV and plan['CoutPad'] > 3, what
+        elif i == 3:
+            assert p.kinds[0] == K.DEEP and shape == E.DG_CLASSES and all(c is not None and c.kind == K.BF16 for c in d), what
+        elif i == 4:
+            assert p.kinds[1] == K.DEEP_S2X4 and shape == E.DG_X4, what
+        elif i == 5:
+            assert shape == E.DG_CLASSES and all(c is not None and c.kind == K.DEEP for c in d), what
+            assert sorted(c.desc.KW for c in d) == [1, 1, 2, 2], what
+        else:
+            assert p.kinds[:2] == (K.DEEP, K.DEEP) and shape == E.DG_CONV, what
+        assert p.ldsimg == (0, 0), what

@@ -6,21 +6,19 @@ with fake non-null addresses (the entry points asked are host-only and never der
 operands / epilogues and both storage types of either tensor, and each sisr_*_eligible / *_parts / *_bnb_parts / *_slabs / *_slab_lead answer is
 printed, with engine.can_fuse_bn_backward per layer.  Run it under each A/B switch (SISR_TRUNK=0, ...): two trees that route alike
 print byte-identical JSON.
-usage: python tools/plan_digest.py [--routes] [root of the tree whose package is digested; default: this one]"""
+--weights prints how engine._layout_weights lays the packed weight images of the layer list out, per build and with / without the
+data gradient: every image's (buffer, offset, fp32 slots rounded up to the 16 bytes the next piece starts on) and the sizes of
+the buffers.  Two trees that lay out alike print byte-identical JSON.
+usage: python tools/plan_digest.py [--routes | --weights] [root of the tree whose package is digested; default: this one]"""
 import ctypes as C, hashlib, importlib, itertools, json, os, sys, types
-ROUTES = '--routes' in sys.argv[1:]
-_args = [a for a in sys.argv[1:] if a != '--routes']
+ROUTES, WEIGHTS = '--routes' in sys.argv[1:], '--weights' in sys.argv[1:]
+_args = [a for a in sys.argv[1:] if a not in ('--routes', '--weights')]
 ROOT = os.path.abspath(_args[0] if _args else os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.dirname(os.path.abspath(__file__)))
 E = importlib.import_module('single-image-super-resolution_amd.engine')
 
-T, F = True, False
-LAYERS = [    # (cin, cout, k, stride, shuffle2, deep_dgrad, n, h, w)
-    (3, 64, 9, 1, F, F, 16, 96, 96), (64, 64, 3, 1, F, F, 16, 96, 96), (64, 64, 3, 1, F, F, 16, 48, 48), (64, 64, 3, 1, F, F, 16, 24, 24),
-    (64, 256, 3, 1, T, F, 16, 96, 96), (64, 3, 3, 1, F, F, 16, 192, 192), (3, 64, 3, 1, F, F, 16, 96, 96), (64, 64, 3, 2, F, F, 16, 96, 96),
-    (64, 128, 3, 1, F, F, 16, 48, 48), (128, 128, 3, 2, F, F, 16, 48, 48), (256, 512, 3, 1, F, F, 16, 12, 12), (512, 512, 3, 2, F, F, 16, 12, 12),
-    (64, 64, 3, 1, F, T, 16, 96, 96), (128, 256, 3, 1, F, T, 16, 24, 24), (16, 16, 3, 1, F, F, 16, 96, 96), (64, 64, 3, 2, F, F, 16, 95, 95),
-    (64, 64, 3, 1, F, F, 2, 20, 48)]
+from plan_layers import LAYERS                   # beside this file
 
 
 def sha(desc):
@@ -122,9 +120,21 @@ def routes(geom, f, d, g, kinds):
     return out
 
 
+def weights(need_dgrad):
+    """the layer list as ONE table (offsets run on from layer to layer)"""
+    items = [(E.ConvRef(E.ConvGeom(cin, cout, k, stride, shuffle2=sh, deep_dgrad=dd), None, None), n, h, w)
+             for cin, cout, k, stride, sh, dd, n, h, w in LAYERS]
+    _, offs, sizes = E._layout_weights(items, need_dgrad)
+    layers = [{'images': [[i.buf, i.off, (i.slots + 3) & ~3] for i in imgs if i is not None], 's': [s0, s1]} for imgs, s0, s1 in offs]
+    return {'layers': layers, 'sizes': sizes}
+
+
 out = {}
 for build in ('fp32', 'bf16x3', 'bf16'):
     E.set_precision(build)
+    if WEIGHTS:
+        out[build] = {'with dgrad': weights(True), 'forward only': weights(False)}
+        continue
     for cin, cout, k, stride, shuffle2, deep_dgrad, n, h, w in LAYERS:
         geom = E.ConvGeom(cin, cout, k, stride, shuffle2=shuffle2, deep_dgrad=deep_dgrad)
         f, d, g, kinds = geom.plans(n, h, w)
