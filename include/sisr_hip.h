@@ -324,6 +324,25 @@ int sisr_slab_reduce_multi(const void *const *slabs, void *const *outs, const in
  * weight-gradient kernel writes: sisr_wgrad_bf16_slab_lead(d)), the rest -- the bias partials -- as fp32 at their float offset; 0: fp32 rows */
 int64_t sisr_wgrad_bf16_slab_lead(const SisrWgradDesc *d);
 
+/* ---- the kernel family a fully filled descriptor goes to.  Each of the four dispatchers (sisr_conv2d_bf16 / _f32,
+ * sisr_conv2d_wgrad_bf16 / _f32) has ONE route function that holds the ordered chain of the sisr_*_eligible calls above; the
+ * dispatcher and the sizing entry points its callers allocate from (*_parts, *_bnb_parts, *_slabs, *_slab_lead) switch on that
+ * route, so no buffer is sized for another kernel than the one that runs -- and a caller that must know the family (which launches
+ * can be batched, which layer needs a padded copy of its gradient) asks the same function instead of rebuilding the chain.
+ * The values are ABI.  A dispatcher only returns the routes its chain holds (DEEP: the two bf16 ones; THIN: the two fp32 ones).
+ * HOST only, no HIP call; SISR_E_BADARG for a null pointer. */
+enum SisrRoute {
+    SISR_ROUTE_GENERIC = 0,   /* the dispatcher's own tiled kernel (conv_fwd / conv_bf16 / conv_wgrad / wgrad_bf16 .hip)  */
+    SISR_ROUTE_DEEP = 1,      /* conv_deep.hip / wgrad_deep.hip                                                            */
+    SISR_ROUTE_TOIMAGE = 2,   /* conv_toimage.hip / wgrad_toimage.hip: the generator's last conv (64 -> 3)                 */
+    SISR_ROUTE_TRUNK = 3,     /* the persistent trunk kernels (conv_trunk / conv_trunk_f32 / wgrad_trunk / wgrad_trunk_f32) */
+    SISR_ROUTE_THIN = 4       /* conv_thin.hip / wgrad_thin.hip: convs over the 3-channel image                            */
+};
+int32_t sisr_conv2d_bf16_route(const SisrConvDesc *d);
+int32_t sisr_conv2d_f32_route(const SisrConvDesc *d);
+int32_t sisr_wgrad_bf16_route(const SisrWgradDesc *d);
+int32_t sisr_wgrad_f32_route(const SisrWgradDesc *d);
+
 /* ---- weights: spectral norm power iteration + packing (legacy torch.nn.utils.spectral_norm
  *      hook, model_generator.py:3; model_discriminator.py:2), multi-tensor: one launch serves
  *      every convolution of a network.  The descriptor TABLE lives in device memory. ---------- */

@@ -16,6 +16,7 @@ PRO_NONE, PRO_ACT, PRO_AFFINE_ACT, PRO_BNBWD, PRO_BNACT_BWD, PRO_ACT_BWD, PRO_TA
 X_NHWC, X_NCHW, X_UNSHUFFLE2 = range(3)
 Y_NHWC, Y_NCHW, Y_SHUFFLE2 = range(3)
 EPI_NONE, EPI_TANH = range(2)
+ROUTE_GENERIC, ROUTE_DEEP, ROUTE_TOIMAGE, ROUTE_TRUNK, ROUTE_THIN = range(5)      # enum SisrRoute: what the sisr_*_route calls answer
 
 _f = C.c_void_p      # device pointers travel as void*
 _i32 = C.c_int32
@@ -151,6 +152,10 @@ _SIGS = {
     'sisr_slab_reduce_f32': [_f, _f, _i32, _i64, _i64, _f],
     'sisr_slab_reduce_multi': [_f, _f, _f, _f, _f, _i32, _f],
     'sisr_wgrad_bf16_slab_lead': [C.POINTER(WgradDesc)],
+    'sisr_conv2d_bf16_route': [C.POINTER(ConvDesc)],
+    'sisr_conv2d_f32_route': [C.POINTER(ConvDesc)],
+    'sisr_wgrad_bf16_route': [C.POINTER(WgradDesc)],
+    'sisr_wgrad_f32_route': [C.POINTER(WgradDesc)],
     'sisr_weights_prepare': [_f, _i32, _i32, _i32, _f],
     'sisr_weights_sn': [_f, _i32, _i32, _i32, _f],
     'sisr_weights_pack': [_f, _i32, _i32, _i32, _f],

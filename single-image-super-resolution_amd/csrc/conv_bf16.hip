@@ -619,7 +619,8 @@ static int launch_conv_bf16(const SisrConvDesc* d, hipStream_t st) {
 }
 
 // the kernel family sisr_conv2d_bf16 hands `d` to (the only place that orders these families)
-static SisrRoute conv_bf16_route(const SisrConvDesc* d) {
+extern "C" int32_t sisr_conv2d_bf16_route(const SisrConvDesc* d) {
+    if (!d) return SISR_E_BADARG;
     if (d->deep.enabled && d->wdeep) return SISR_ROUTE_DEEP;                    // planned for conv_deep.hip: runs there or is refused
     if (sisr_conv2d_toimage_eligible(d)) return SISR_ROUTE_TOIMAGE;             // the generator's last conv (64 -> 3)
     // the generator's trunk geometry: persistent weights-in-registers kernel
@@ -630,7 +631,7 @@ static SisrRoute conv_bf16_route(const SisrConvDesc* d) {
 // workgroup, the generic kernels (and the last conv's, which has neither epilogue) one per tile (plan.n_tiles)
 extern "C" int sisr_conv2d_bf16_parts(const SisrConvDesc* d) {
     if (!d) return SISR_E_BADARG;
-    switch (conv_bf16_route(d)) {
+    switch (sisr_conv2d_bf16_route(d)) {
         case SISR_ROUTE_DEEP: return sisr_conv2d_deep_parts(d);
         case SISR_ROUTE_TRUNK: return sisr_conv2d_trunk_grid(d);
         default: return d->plan.n_tiles;
@@ -639,7 +640,7 @@ extern "C" int sisr_conv2d_bf16_parts(const SisrConvDesc* d) {
 
 extern "C" int sisr_conv2d_bf16(const SisrConvDesc* d, void* stream) {
     if (!d || !d->x1 || !d->y) return SISR_E_BADARG;
-    const SisrRoute route = conv_bf16_route(d);
+    const int32_t route = sisr_conv2d_bf16_route(d);
     // the split-K implicit-GEMM family (conv_deep.hip): a descriptor planned for it carries that family's weight image and
     // NOT the generic one, so it either runs there or is refused -- never silently on another kernel
     if (route == SISR_ROUTE_DEEP) {

@@ -410,7 +410,8 @@ static int launch_conv(const SisrConvDesc* d, hipStream_t st) {
 }
 
 // the kernel family sisr_conv2d_f32 hands `d` to (the only place that orders these families)
-static SisrRoute conv_f32_route(const SisrConvDesc* d) {
+extern "C" int32_t sisr_conv2d_f32_route(const SisrConvDesc* d) {
+    if (!d) return SISR_E_BADARG;
     if (sisr_conv2d_trunk_f32_eligible(d)) return SISR_ROUTE_TRUNK;
     if (sisr_conv2d_thin_eligible(d)) return SISR_ROUTE_THIN;                   // bf16 build: 9x9 over a 3-channel image
     return sisr_conv2d_toimage_f32_eligible(d) ? SISR_ROUTE_TOIMAGE : SISR_ROUTE_GENERIC;      // the generator's last conv (64 -> 3)
@@ -420,14 +421,14 @@ static SisrRoute conv_f32_route(const SisrConvDesc* d) {
 // tile on the generic one (the thin and last-conv kernels have no statistics epilogue; they answer as the generic kernel)
 extern "C" int sisr_conv2d_f32_parts(const SisrConvDesc* d) {
     if (!d) return SISR_E_BADARG;
-    return conv_f32_route(d) == SISR_ROUTE_TRUNK ? sisr_conv2d_trunk_f32_streams(d) : d->plan.n_tiles;
+    return sisr_conv2d_f32_route(d) == SISR_ROUTE_TRUNK ? sisr_conv2d_trunk_f32_streams(d) : d->plan.n_tiles;
 }
 
 // rows of bnb_part (one per workgroup) a launch of this descriptor writes: the persistent kernel in its data-gradient role (2) has
 // that epilogue; 0: the kernel it goes to does not take it
 extern "C" int sisr_conv2d_f32_bnb_parts(const SisrConvDesc* d) {
     if (!d) return SISR_E_BADARG;
-    const bool takes = conv_f32_route(d) == SISR_ROUTE_TRUNK && sisr_conv2d_trunk_f32_eligible(d) == 2;
+    const bool takes = sisr_conv2d_f32_route(d) == SISR_ROUTE_TRUNK && sisr_conv2d_trunk_f32_eligible(d) == 2;
     return takes ? 2 * sisr_conv2d_trunk_f32_streams(d) : 0;
 }
 
@@ -443,7 +444,7 @@ extern "C" int sisr_conv2d_f32(const SisrConvDesc* d, void* stream) {
     const SisrConvPlan& p = d->plan;
     if (p.n_tiles <= 0 || p.lds_bytes <= 0 || p.lds_bytes > 160 * 1024) return SISR_E_BADARG;
     hipStream_t st = sisr_stream(stream);
-    const SisrRoute route = conv_f32_route(d);
+    const int32_t route = sisr_conv2d_f32_route(d);
     if (route == SISR_ROUTE_TRUNK) return sisr_conv2d_trunk_f32_launch(d, st);
     if (route == SISR_ROUTE_THIN) return sisr_conv2d_thin_launch(d, st);
     if (route == SISR_ROUTE_TOIMAGE) return sisr_conv2d_toimage_launch(d, st);

@@ -260,7 +260,8 @@ static int launch_wgrad(const SisrWgradDesc* d, hipStream_t st) {
 }
 
 // the kernel family sisr_conv2d_wgrad_f32 hands `d` to (the only place that orders these families)
-static SisrRoute wgrad_f32_route(const SisrWgradDesc* d) {
+extern "C" int32_t sisr_wgrad_f32_route(const SisrWgradDesc* d) {
+    if (!d) return SISR_E_BADARG;
     if (sisr_wgrad_trunk_f32_eligible(d)) return SISR_ROUTE_TRUNK;
     if (sisr_wgrad_thin_eligible(d)) return SISR_ROUTE_THIN;                    // bf16 build: the first conv (3-channel image)
     return sisr_wgrad_toimage_f32_eligible(d) ? SISR_ROUTE_TOIMAGE : SISR_ROUTE_GENERIC;       // the last conv (64 -> 3), fp32 tensors
@@ -269,7 +270,7 @@ static SisrRoute wgrad_f32_route(const SisrWgradDesc* d) {
 // slabs a launch of this descriptor writes (rows of `slab` at slab_stride)
 extern "C" int sisr_wgrad_f32_slabs(const SisrWgradDesc* d) {
     if (!d) return SISR_E_BADARG;
-    switch (wgrad_f32_route(d)) {
+    switch (sisr_wgrad_f32_route(d)) {
         case SISR_ROUTE_TRUNK: return sisr_wgrad_trunk_f32_slabs(d);
         case SISR_ROUTE_THIN: return sisr_wgrad_thin_slabs(d);
         case SISR_ROUTE_TOIMAGE: return sisr_wgrad_toimage_slabs(d);
@@ -285,7 +286,7 @@ extern "C" int sisr_conv2d_wgrad_f32(const SisrWgradDesc* d, void* stream) {
     if (d->grid_x <= 0 || d->lds_bytes <= 0 || d->lds_bytes > 160 * 1024 || d->KH * d->NT > WG_NACC)
         return SISR_E_BADARG;
     hipStream_t st = sisr_stream(stream);
-    const SisrRoute route = wgrad_f32_route(d);
+    const int32_t route = sisr_wgrad_f32_route(d);
     if (route == SISR_ROUTE_TRUNK) return sisr_wgrad_trunk_f32_launch(d, st);
     if (route == SISR_ROUTE_THIN) return sisr_wgrad_thin_launch(d, st);
     if (route == SISR_ROUTE_TOIMAGE) return sisr_wgrad_toimage_f32_launch(d, st);

@@ -103,5 +103,5 @@ extern "C" int sisr_struct_sizes(int32_t* out, int32_t cap) {
 // would report it as its own.  Returns the error that was pending (0: none) and clears it.
 extern "C" int sisr_clear_last_error(void) { return (int)hipGetLastError(); }
 
-extern "C" const char* sisr_version(void) { return "sisr_hip 0.5 (gfx950)"; }
+extern "C" const char* sisr_version(void) { return "sisr_hip 0.6 (gfx950)"; }
 

@@ -60,11 +60,6 @@ static int sisr_launch(dim3 grid, dim3 block, int lds, int lds_base, hipStream_t
     return 0;
 }
 
-// ---- the kernel family a descriptor goes to.  Each of the four dispatchers (sisr_conv2d_bf16 / _f32, sisr_conv2d_wgrad_bf16 / _f32)
-// has ONE route function next to it that holds the ordered chain of the public sisr_*_eligible calls; the dispatcher and the sizing
-// entry points its callers allocate from switch on that route, so no buffer is sized for another kernel than the one that runs ----
-enum SisrRoute { SISR_ROUTE_GENERIC, SISR_ROUTE_DEEP, SISR_ROUTE_TOIMAGE, SISR_ROUTE_TRUNK, SISR_ROUTE_THIN };
-
 // ---- host entry points called across files: the dispatchers hand a routed descriptor to the specialised kernel's file, and ask it
 // for the grid its launch will have ------------------------------------------------------------------------------------------------
 int sisr_conv2d_trunk_launch(const SisrConvDesc* d, hipStream_t st);          // conv_trunk.hip

@@ -253,7 +253,8 @@ static int launch_wgrad_bf16(const SisrWgradDesc* d, hipStream_t st) {
 }
 
 // the kernel family sisr_conv2d_wgrad_bf16 hands `d` to (the only place that orders these families)
-static SisrRoute wgrad_bf16_route(const SisrWgradDesc* d) {
+extern "C" int32_t sisr_wgrad_bf16_route(const SisrWgradDesc* d) {
+    if (!d) return SISR_E_BADARG;
     if (sisr_wgrad_trunk_eligible(d)) return SISR_ROUTE_TRUNK;
     if (sisr_wgrad_toimage_eligible(d)) return SISR_ROUTE_TOIMAGE;              // the generator's last conv (64 -> 3)
     return sisr_wgrad_deep_eligible(d) ? SISR_ROUTE_DEEP : SISR_ROUTE_GENERIC;  // 3x3, channels in 64s
@@ -262,7 +263,7 @@ static SisrRoute wgrad_bf16_route(const SisrWgradDesc* d) {
 // slabs a launch of this descriptor writes (rows of `slab` at slab_stride): one per workgroup
 extern "C" int sisr_wgrad_bf16_slabs(const SisrWgradDesc* d) {
     if (!d) return SISR_E_BADARG;
-    switch (wgrad_bf16_route(d)) {
+    switch (sisr_wgrad_bf16_route(d)) {
         case SISR_ROUTE_TRUNK: return sisr_wgrad_trunk_slabs(d);
         case SISR_ROUTE_TOIMAGE: return sisr_wgrad_toimage_slabs(d);
         case SISR_ROUTE_DEEP: return d->deep.n_pb;
@@ -274,7 +275,7 @@ extern "C" int sisr_wgrad_bf16_slabs(const SisrWgradDesc* d) {
 // sisr_bn_bwd_finalize_slab); 0: fp32 slabs
 extern "C" int64_t sisr_wgrad_bf16_slab_lead(const SisrWgradDesc* d) {
     if (!d) return 0;
-    switch (wgrad_bf16_route(d)) {
+    switch (sisr_wgrad_bf16_route(d)) {
         case SISR_ROUTE_TRUNK: return !sisr_switch_off("SISR_SLAB_BF16") ? (int64_t)d->slab_elems : 0;
         case SISR_ROUTE_DEEP: return d->deep.slab_bf16 ? (int64_t)d->slab_elems : 0;
         default: return 0;
@@ -288,7 +289,7 @@ extern "C" int sisr_conv2d_wgrad_bf16(const SisrWgradDesc* d, void* stream) {
     if (d->slab_stride < d->slab_elems || d->CK != BF_CK || d->PS != BF_PS) return SISR_E_BADARG;
     if (d->grid_x <= 0 || d->lds_bytes <= 0 || d->lds_bytes > 160 * 1024) return SISR_E_BADARG;
     hipStream_t st = sisr_stream(stream);
-    const SisrRoute route = wgrad_bf16_route(d);
+    const int32_t route = sisr_wgrad_bf16_route(d);
     if (route == SISR_ROUTE_TRUNK) return sisr_wgrad_trunk_launch(d, st);
     if (route == SISR_ROUTE_TOIMAGE) return sisr_wgrad_toimage_launch(d, st);
     if (route == SISR_ROUTE_DEEP) return sisr_wgrad_deep_launch(d, st);

@@ -484,19 +484,22 @@ static int launch_wd(const SisrWgradDesc* d, hipStream_t st) {
     return sisr_launch<wgrad_deep_kernel<S, NITX, NITD, false>>(grid, dim3(WD_THREADS), p.lds_bytes, 0, st, *d);
 }
 
-int sisr_wgrad_deep_launch(const SisrWgradDesc* d, hipStream_t st) {
+// what a launch of its own and a member of a batch must both satisfy: the constants its prologues read, a split into pixel blocks that
+// covers the tiles with none empty, and no more staging items per thread than the kernels of its stride are instantiated for
+static int wd_member_check(const SisrWgradDesc* d) {
     const SisrWgradDeepPlan& p = d->deep;
     if (d->pro_mode == SISR_PRO_AFFINE_ACT && (!d->pa || !d->pd)) return SISR_E_BADARG;
     const int gp = d->gpro_mode;
     if ((gp == SISR_PRO_BNBWD || gp == SISR_PRO_BNACT_BWD) && (!d->qa || !d->qb || !d->qd)) return SISR_E_BADARG;
     if (gp == SISR_PRO_BNACT_BWD && (!d->qs || !d->qt)) return SISR_E_BADARG;
     if (p.n_pb <= 0 || p.tiles_per_pb <= 0 || (p.n_pb - 1) * p.tiles_per_pb >= p.n_tiles) return SISR_E_BADARG;
-    if (d->stride == 1) {
-        if (p.NITX > 6 || p.NITD > 4) return SISR_E_BADARG;
-        return launch_wd<1, 6, 4>(d, st);
-    }
-    if (p.NITX > 10 || p.NITD > 3) return SISR_E_BADARG;
-    return launch_wd<2, 10, 3>(d, st);
+    if (d->stride == 1 ? (p.NITX > 6 || p.NITD > 4) : (p.NITX > 10 || p.NITD > 3)) return SISR_E_BADARG;
+    return 0;
+}
+
+int sisr_wgrad_deep_launch(const SisrWgradDesc* d, hipStream_t st) {
+    if (int e = wd_member_check(d)) return e;
+    return d->stride == 1 ? launch_wd<1, 6, 4>(d, st) : launch_wd<2, 10, 3>(d, st);
 }
 
 template <int S, int NITX, int NITD>
@@ -517,12 +520,7 @@ extern "C" int sisr_wgrad_deep_batch(const SisrWgradDesc* table_host, const Sisr
         const SisrWgradDeepPlan& p = d->deep;
         if (!sisr_wgrad_deep_eligible(d) || d->stride != S || operand_needs_x2(d->gpro_mode) != two) return SISR_E_BADARG;
         if (!d->x1 || !d->g1 || !d->slab || (two && !d->g2) || d->slab_stride < d->slab_elems) return SISR_E_BADARG;
-        if (d->pro_mode == SISR_PRO_AFFINE_ACT && (!d->pa || !d->pd)) return SISR_E_BADARG;
-        const int gp = d->gpro_mode;
-        if ((gp == SISR_PRO_BNBWD || gp == SISR_PRO_BNACT_BWD) && (!d->qa || !d->qb || !d->qd)) return SISR_E_BADARG;
-        if (gp == SISR_PRO_BNACT_BWD && (!d->qs || !d->qt)) return SISR_E_BADARG;
-        if (p.n_pb <= 0 || p.tiles_per_pb <= 0 || (p.n_pb - 1) * p.tiles_per_pb >= p.n_tiles) return SISR_E_BADARG;
-        if (S == 1 ? (p.NITX > 6 || p.NITD > 4) : (p.NITX > 10 || p.NITD > 3)) return SISR_E_BADARG;
+        if (wd_member_check(d)) return SISR_E_BADARG;
         if (p.batch_first_wg != total) return SISR_E_BADARG;       // the caller numbers the members' workgroups consecutively
         total += p.n_cib * p.n_cob * p.n_pb;
         lds = std::max(lds, p.lds_bytes);

@@ -103,13 +103,13 @@ class Kind(enum.IntEnum):
 
 # the library's entry points per tensor family, keyed by Kind.bf16: every call site asks this table.  (The two families size the
 # BatchNorm-backward rows through different calls; the fp32 kernels' slabs are never bf16, so that family has no slab_lead.)
-Family = namedtuple('Family', 'conv parts bnb_parts trunk_eligible wgrad slabs slab_lead batch_arg_bytes batch_args batch')
+Family = namedtuple('Family', 'conv parts bnb_parts trunk_eligible wgrad wgrad_route slabs slab_lead batch_arg_bytes batch_args batch')
 _FAMILY = {
     False: Family('sisr_conv2d_f32', 'sisr_conv2d_f32_parts', 'sisr_conv2d_f32_bnb_parts', 'sisr_conv2d_trunk_f32_eligible',
-                  'sisr_conv2d_wgrad_f32', 'sisr_wgrad_f32_slabs', None,
+                  'sisr_conv2d_wgrad_f32', 'sisr_wgrad_f32_route', 'sisr_wgrad_f32_slabs', None,
                   'sisr_wgrad_trunk_f32_batch_arg_bytes', 'sisr_wgrad_trunk_f32_batch_args', 'sisr_wgrad_trunk_f32_batch'),
     True: Family('sisr_conv2d_bf16', 'sisr_conv2d_bf16_parts', 'sisr_conv2d_bf16_parts', 'sisr_conv2d_trunk_eligible',
-                 'sisr_conv2d_wgrad_bf16', 'sisr_wgrad_bf16_slabs', 'sisr_wgrad_bf16_slab_lead',
+                 'sisr_conv2d_wgrad_bf16', 'sisr_wgrad_bf16_route', 'sisr_wgrad_bf16_slabs', 'sisr_wgrad_bf16_slab_lead',
                  'sisr_wgrad_trunk_batch_arg_bytes', 'sisr_wgrad_trunk_batch_args', 'sisr_wgrad_trunk_batch'),
 }
 
@@ -800,6 +800,16 @@ def _count(key, n=1):
     KERNEL_COUNTS[key] = KERNEL_COUNTS.get(key, 0) + n
 
 
+# one fixed-order sum of per-workgroup slabs: red[i] = sum_s slab[s][i], i < stride; lead: the leading elements of every row stored as bf16
+SlabJob = namedtuple('SlabJob', 'slab red n_slabs stride lead')
+
+
+def _reduce_slabs(job):
+    """the sum of one SlabJob in a launch of its own"""
+    L.check(L.lib().sisr_slab_reduce_f32(job.slab.data_ptr(), job.red.data_ptr(), job.n_slabs, job.stride, job.lead, _stream()),
+            'sisr_slab_reduce_f32')
+
+
 class PendingSlabs:
     """Slab reductions that have not been launched yet.  conv_wgrad(..., defer=pending) leaves the fixed-order sum of
     its per-workgroup slabs here instead of launching sisr_slab_reduce_f32; the next bn_backward(..., part=rows,
@@ -808,7 +818,7 @@ class PendingSlabs:
     left the ordinary way.  The reduced buffers are valid in stream order after either."""
 
     def __init__(self):
-        self.jobs = []                      # (slab tensor, reduced tensor, n_slabs, stride, leading bf16 elements per row)
+        self.jobs = []                      # SlabJob
 
     def pop(self):
         return self.jobs.pop(0) if self.jobs else None
@@ -819,64 +829,72 @@ class PendingSlabs:
             return
         jobs, self.jobs = self.jobs, []
         n = len(jobs)
-        slabs = (C.c_void_p * n)(*[j[0].data_ptr() for j in jobs])
-        outs = (C.c_void_p * n)(*[j[1].data_ptr() for j in jobs])
-        counts = (C.c_int32 * n)(*[j[2] for j in jobs])
-        elems = (C.c_int64 * n)(*[j[3] for j in jobs])
-        leads = (C.c_int64 * n)(*[j[4] for j in jobs])
+        slabs = (C.c_void_p * n)(*[j.slab.data_ptr() for j in jobs])
+        outs = (C.c_void_p * n)(*[j.red.data_ptr() for j in jobs])
+        counts = (C.c_int32 * n)(*[j.n_slabs for j in jobs])
+        elems = (C.c_int64 * n)(*[j.stride for j in jobs])
+        leads = (C.c_int64 * n)(*[j.lead for j in jobs])
         L.check(L.lib().sisr_slab_reduce_multi(C.addressof(slabs), C.addressof(outs), C.addressof(counts), C.addressof(elems),
                                                C.addressof(leads), n, _stream()), 'sisr_slab_reduce_multi')
 
 
-def _bind_slabs(g, n_slabs, dev, bf16):
-    """the [n_slabs, slab_stride] slab tensor of weight-gradient descriptor g, bound to it (a row: one workgroup's gradient part, then
-    its bias row) -> (slab, leading elements of every row that the launch of g stores as bf16: the persistent and the deep bf16 kernels)"""
-    slab = torch.empty((n_slabs, g.slab_stride), dtype=torch.float32, device=dev)
+# One weight gradient, prepared ONCE: g, the copy of the planned WgradDesc with both operands and mfma_split filled in; the operands
+# themselves (their tensors stay alive until the launch); red, the buffer the reduced gradient WILL be in; route, the kernel family
+# (L.ROUTE_*) the library's dispatcher sends g to -- asked here and nowhere else.  Whoever launches it (alone: _launch_wgrad; with
+# others: WgradDeepBatch) binds the slabs.
+WgradLaunch = namedtuple('WgradLaunch', 'prep g x_op dy_op red route')
+
+
+def _wgrad_launch(prep, x_op, dy_op):
+    g, bf16 = _copy_struct(prep.plans[2]), prep.kinds[2].bf16
+    assert tuple(x_op.dims) == (g.N, g.H, g.W, g.Cin) and tuple(dy_op.dims) == (g.N, g.Ho, g.Wo, prep.ref.geom.cout), \
+        (x_op.dims, dy_op.dims)
+    x_op.fill(g)
+    dy_op.fill(g, g=True)
+    g.mfma_split = mfma_split()
+    red = torch.empty((g.slab_stride,), dtype=torch.float32, device=x_op.x1.device)
+    return WgradLaunch(prep, g, x_op, dy_op, red, _entry(bf16, 'wgrad_route')(C.byref(g)))
+
+
+def _bind_slabs(w, n_slabs):
+    """the [n_slabs, slab_stride] slab tensor of weight gradient w, bound to its descriptor (a row: one workgroup's gradient part, then its
+    bias row) -> the SlabJob that sums it; its lead: what the launch of w.g stores as bf16 (the persistent and the deep bf16 kernels)"""
+    g = w.g
+    slab = torch.empty((n_slabs, g.slab_stride), dtype=torch.float32, device=w.red.device)
     g.slab = slab.data_ptr()
     g.bias_slab = slab.data_ptr() + 4 * g.slab_elems
-    return slab, int(_entry(True, 'slab_lead')(C.byref(g))) if bf16 else 0
+    lead = int(_entry(True, 'slab_lead')(C.byref(g))) if w.prep.kinds[2].bf16 else 0
+    return SlabJob(slab, w.red, n_slabs, g.slab_stride, lead)
+
+
+def _launch_wgrad(w, defer=None):
+    """weight gradient w in a launch of its own -> w.red"""
+    g, dy_op, bf16, cout = w.g, w.dy_op, w.prep.kinds[2].bf16, w.prep.ref.geom.cout
+    if g.Cout != cout and w.route != L.ROUTE_TOIMAGE:
+        # the generator's last conv (64 -> 3) where the kernel that reads the NCHW image gradient itself (wgrad_toimage.hip) does not take
+        # it: the bf16 kernel on a channel-padded NHWC copy of the gradient
+        if dy_op.mode != L.X_NCHW or dy_op.pro not in (L.PRO_NONE, L.PRO_TANH_BWD):
+            raise RuntimeError('padded weight gradient: NCHW gradient with no / tanh-backward prologue expected')
+        g4 = torch.empty((g.N, g.Ho, g.Wo, g.Cout), dtype=torch.float32, device=w.red.device)
+        L.check(L.lib().sisr_nchw_grad_to_nhwc4(dy_op.x1.data_ptr(), _ptr(dy_op.x2) if dy_op.pro == L.PRO_TANH_BWD else None,
+                                                g4.data_ptr(), g.N, cout, g.Ho, g.Wo, g.Cout, _stream()), 'sisr_nchw_grad_to_nhwc4')
+        Operand.plain(g4).fill(g, g=True)
+    if w.route == L.ROUTE_DEEP:
+        _count('wgrad_deep')
+    job = _bind_slabs(w, _entry(bf16, 'slabs')(C.byref(g)))
+    fn = _entry(bf16, 'wgrad')
+    L.check(fn(C.byref(g), _stream()), fn.__name__)
+    if defer is not None and _on('SISR_FUSE_SLABRED'):
+        defer.jobs.append(job)
+    else:
+        _reduce_slabs(job)
+    return w.red
 
 
 def conv_wgrad(prep, x_op, dy_op, defer=None):
     """Weight + bias gradient in packed layout: returns the reduced [slab_elems + CoutPad] buffer.
     defer (PendingSlabs or None): leave the slab reduction to a later launch (see PendingSlabs)."""
-    lib = L.lib()
-    g, bf16 = _copy_struct(prep.plans[2]), prep.kinds[2].bf16
-    cout = prep.ref.geom.cout
-    assert tuple(x_op.dims) == (g.N, g.H, g.W, g.Cin) and tuple(dy_op.dims) == (g.N, g.Ho, g.Wo, cout), \
-        (x_op.dims, dy_op.dims)
-    dev = x_op.x1.device
-    direct = False
-    if g.Cout != cout and dy_op.mode == L.X_NCHW:
-        # the generator's last conv (64 -> 3) has a kernel that reads the NCHW image gradient itself (wgrad_toimage.hip)
-        x_op.fill(g)
-        dy_op.fill(g, g=True)
-        direct = bool(lib.sisr_wgrad_toimage_eligible(C.byref(g)))
-    if g.Cout != cout and not direct:   # bf16 kernel on a channel-padded NHWC copy of the (NCHW, few-channel) gradient
-        if dy_op.mode != L.X_NCHW or dy_op.pro not in (L.PRO_NONE, L.PRO_TANH_BWD):
-            raise RuntimeError('padded weight gradient: NCHW gradient with no / tanh-backward prologue expected')
-        g4 = torch.empty((g.N, g.Ho, g.Wo, g.Cout), dtype=torch.float32, device=dev)
-        L.check(lib.sisr_nchw_grad_to_nhwc4(dy_op.x1.data_ptr(), _ptr(dy_op.x2) if dy_op.pro == L.PRO_TANH_BWD else None,
-                                            g4.data_ptr(), g.N, cout, g.Ho, g.Wo, g.Cout, _stream()),
-                'sisr_nchw_grad_to_nhwc4')
-        dy_op = Operand.plain(g4)
-    stride = g.slab_stride
-    x_op.fill(g)
-    dy_op.fill(g, g=True)
-    g.mfma_split = mfma_split()
-    n_slabs = _entry(bf16, 'slabs')(C.byref(g))
-    if bf16 and g.deep.enabled and lib.sisr_wgrad_deep_eligible(C.byref(g)):
-        _count('wgrad_deep')
-    slab, lead = _bind_slabs(g, n_slabs, dev, bf16)
-    fn = _entry(bf16, 'wgrad')
-    L.check(fn(C.byref(g), _stream()), fn.__name__)
-    red = torch.empty((stride,), dtype=torch.float32, device=dev)
-    if defer is not None and _on('SISR_FUSE_SLABRED'):
-        defer.jobs.append((slab, red, n_slabs, stride, lead))
-        return red
-    L.check(lib.sisr_slab_reduce_f32(slab.data_ptr(), red.data_ptr(), n_slabs, stride, lead, _stream()),
-            'sisr_slab_reduce_f32')
-    return red
+    return _launch_wgrad(_wgrad_launch(prep, x_op, dy_op), defer)
 
 
 def _deep_batch_key(g):
@@ -891,6 +909,22 @@ def _trunk_batch_key(prep, g):
     return prep.kinds[2].bf16, g.gpro_mode
 
 
+def _batch_table(group, n_slabs, pending):
+    """the descriptor table of one batched launch, every member's n_slabs(g) slabs bound to it and their sums left with `pending`"""
+    table = (L.WgradDesc * len(group))()
+    for i, w in enumerate(group):
+        pending.jobs.append(_bind_slabs(w, n_slabs(w.g)))
+        table[i] = w.g
+    return table
+
+
+def _grouped(members, key):
+    groups = {}
+    for w in members:
+        groups.setdefault(key(w), []).append(w)
+    return groups
+
+
 class WgradDeepBatch:
     """Weight gradients of the layers that run on wgrad_deep.hip, collected during a backward pass and launched TOGETHER (one launch
     per stride: grid z = layer).  Nothing consumes a weight gradient before the optimizer step, so a schedule may hold them back;
@@ -899,112 +933,94 @@ class WgradDeepBatch:
     a third of the slabs.  add() returns the buffer the reduced gradient WILL be in -- valid after run(pending) and pending.flush()."""
 
     def __init__(self):
-        self.items = []
+        self.items = []                 # WgradLaunch
         self.trunk = []                 # layers the persistent trunk kernel keeps (LR 96): batched per gradient-prologue kind
 
     def add(self, prep, x_op, dy_op):
         """-> reduced-gradient buffer, or None when the layer does not qualify (the caller then runs conv_wgrad as usual)"""
+        return self.offer(_wgrad_launch(prep, x_op, dy_op))
+
+    def offer(self, w):
+        """-> w.red, or None when weight gradient w (a WgradLaunch) does not qualify (the caller then launches it: _launch_wgrad).  Which
+        list keeps it follows from the build, its route and wgrad_deep.hip's own answer"""
+        g, members = w.g, self.items
+        plain_trunk = w.route == L.ROUTE_TRUNK and g.Cout == 64      # (what the batched trunk kernels take: not the upscale conv)
         if not _on('SISR_WGRAD_BATCH'):
             return None
-        lib = L.lib()
-        g = _copy_struct(prep.plans[2])
-        x_op.fill(g)
-        dy_op.fill(g, g=True)
-        members = self.items                                         # (the operands' tensors stay alive until run())
-        if not prep.kinds[2].bf16:
-            # fp32-tensor builds: the persistent trunk kernel's plain layers (Cout = 64) are batched like the bf16 build's
-            g.mfma_split = mfma_split()
-            if g.Cout != 64 or dy_op.mode != L.X_NHWC or not lib.sisr_wgrad_trunk_f32_eligible(C.byref(g)):
+        if not w.prep.kinds[2].bf16:
+            # fp32-tensor builds: the persistent trunk kernel's plain layers are batched like the bf16 build's
+            if not plain_trunk or g.g_mode != L.X_NHWC:
                 return None
             members = self.trunk
-        elif not g.deep.enabled:
+        elif w.route == L.ROUTE_TOIMAGE or not L.lib().sisr_wgrad_deep_eligible(C.byref(g)):
             return None
-        # (the last conv's kernel comes first in sisr_conv2d_wgrad_bf16's dispatch and stays; so does the persistent trunk kernel
-        # where its 8 x 16 tiles fill the chip -- at LR 48 they are 288 for 256 CUs: 144 workgroups of two, and the batch measured
-        # 366 us for the 33 trunk layers against 33 x 16.5 us)
-        elif lib.sisr_wgrad_toimage_eligible(C.byref(g)) or not lib.sisr_wgrad_deep_eligible(C.byref(g)):
-            return None
-        elif lib.sisr_wgrad_trunk_eligible(C.byref(g)):
-            if g.N * g.H * g.W >= int(_knob('SISR_WGRAD_BATCH_TRUNK_PIXELS', 384 * 128)) or not _on('SISR_WGRAD_BATCH_TRUNK'):
-                # the persistent kernel keeps the layer -- and, for the plain trunk layers (Cout = 64), its launches are batched
-                # too (run(): sisr_wgrad_trunk_batch, workgroups [z * wpl, (z + 1) * wpl) serve layer z)
-                if g.Cout != 64:
-                    return None
-                members = self.trunk
-            # (else sisr_wgrad_bf16_slab_lead answers for the trunk kernel: the same SISR_SLAB_BF16 rule as wgrad_deep.hip's)
-        red = torch.empty((g.slab_stride,), dtype=torch.float32, device=x_op.x1.device)
-        members.append((prep, g, x_op, dy_op, red))
-        return red
+        # the persistent trunk kernel keeps a layer where its 8 x 16 tiles fill the chip -- at LR 48 they are 288 for 256 CUs: 144 workgroups
+        # of two, and the batch measured 366 us for the 33 trunk layers against 33 x 16.5 us (sisr_wgrad_bf16_slab_lead then answers for
+        # the trunk kernel: the same SISR_SLAB_BF16 rule as wgrad_deep.hip's) -- and its launches are batched too (_run_trunk)
+        elif w.route == L.ROUTE_TRUNK and (g.N * g.H * g.W >= int(_knob('SISR_WGRAD_BATCH_TRUNK_PIXELS', 384 * 128))
+                                           or not _on('SISR_WGRAD_BATCH_TRUNK')):
+            if not plain_trunk:
+                return None
+            members = self.trunk
+        members.append(w)
+        return w.red
 
     def run(self, pending):
         """launch what was collected; the slab sums are left with `pending` (PendingSlabs: the caller flushes it)"""
         self._run_trunk(pending)
-        if not self.items:
-            return
         lib = L.lib()
         items, self.items = self.items, []
-        groups = {}
-        for it in items:
-            groups.setdefault(_deep_batch_key(it[1]), []).append(it)
-        for group in groups.values():
-            work = [float(g.N) * g.Ho * g.Wo * g.Cin * g.Cout for _, g, _, _, _ in group]
+        for group in _grouped(items, lambda w: _deep_batch_key(w.g)).values():
+            work = [float(w.g.N) * w.g.Ho * w.g.Wo * w.g.Cin * w.g.Cout for w in group]
             tot = sum(work)
-            table = (L.WgradDesc * len(group))()
             first_wg = 0
-            for i, (prep, g, x_op, dy_op, red) in enumerate(group):
+            for w, wk in zip(group, work):
+                g = w.g
                 if len(group) > 1:
                     blocks = (g.Cin // 64) * (g.Cout // 64)
-                    share = max(blocks, int(round(256.0 * work[i] / tot)))
-                    cache, key = prep.ref.geom._plans, ('wgrad_deep_share', g.N, g.H, g.W, share, _knob('SISR_SLAB_BF16', '1'))
+                    share = max(blocks, int(round(256.0 * wk / tot)))
+                    cache, key = w.prep.ref.geom._plans, ('wgrad_deep_share', g.N, g.H, g.W, share, _knob('SISR_SLAB_BF16', '1'))
                     if key not in cache:
                         t = _copy_struct(g)
                         L.check(lib.sisr_wgrad_deep_plan(C.byref(t), share), 'sisr_wgrad_deep_plan(share)')
                         cache[key] = _copy_struct(t.deep)
                     g.deep = cache[key]
-                n_slabs = g.deep.n_pb
                 g.deep.batch_first_wg = first_wg
-                first_wg += g.deep.n_cib * g.deep.n_cob * n_slabs
-                slab, lead = _bind_slabs(g, n_slabs, red.device, True)
-                table[i] = g
-                pending.jobs.append((slab, red, n_slabs, g.slab_stride, lead))
-            dev = _table_to_device(table, group[0][4].device)
+                first_wg += g.deep.n_cib * g.deep.n_cob * g.deep.n_pb
+            table = _batch_table(group, lambda g: g.deep.n_pb, pending)
+            dev = _table_to_device(table, group[0].red.device)
             L.check(lib.sisr_wgrad_deep_batch(table, dev.data_ptr(), len(group), _stream()), 'sisr_wgrad_deep_batch')
             _count('wgrad_deep', len(group))
             _count('wgrad_deep_batch')
 
     def _run_trunk(self, pending):
-        if not self.trunk:
-            return
         items, self.trunk = self.trunk, []
-        groups = {}
-        for it in items:
-            groups.setdefault(_trunk_batch_key(it[0], it[1]), []).append(it)
-        for (is_bf16, _), group in groups.items():
+        for (is_bf16, _), group in _grouped(items, lambda w: _trunk_batch_key(w.prep, w.g)).items():
             n = len(group)
             # 256 workgroup slots over the layers: every workgroup walks its share of ONE layer's tiles back to back (17 layers of 1,152
             # tiles: 15 workgroups x 77; alone, a layer is 231 workgroups x 5 with a tenth of the chip idle)
             wpl = max(1, min(256 // n, 231))
-            table = (L.WgradDesc * n)()
-            for i, (prep, g, x_op, dy_op, red) in enumerate(group):
-                slab, lead = _bind_slabs(g, wpl, red.device, is_bf16)
-                table[i] = g
-                pending.jobs.append((slab, red, wpl, g.slab_stride, lead))
+            table = _batch_table(group, lambda g: wpl, pending)
             args = (C.c_char * (n * _entry(is_bf16, 'batch_arg_bytes')()))()
             f_args, f_run = _entry(is_bf16, 'batch_args'), _entry(is_bf16, 'batch')
             L.check(f_args(table, n, C.addressof(args)), f_args.__name__)
-            dev = _table_to_device(args, group[0][4].device)
+            dev = _table_to_device(args, group[0].red.device)
             L.check(f_run(table, dev.data_ptr(), n, wpl, _stream()), f_run.__name__)
             _count('wgrad_trunk_batch')
+
+
+# a reduced packed gradient waiting to be un-packed into the gradients of its layer's weight and bias
+GradItem = namedtuple('GradItem', 'prep red want_w want_b')
 
 
 class WeightGradBatch:
     """Collects (prepared conv, reduced packed gradient) pairs; one launch un-packs them all."""
 
     def __init__(self):
-        self.items = []
+        self.items = []                 # GradItem
 
     def add(self, prep, red, want_w=True, want_b=True):
-        self.items.append((prep, red, want_w, want_b))
+        self.items.append(GradItem(prep, red, want_w, want_b))
 
     def run(self):
         """returns {id(ConvRef): (grad_w or None, grad_b or None)}"""
@@ -1014,8 +1030,8 @@ class WeightGradBatch:
         # un-packing (sisr_weights_grad_fast); the rest (9x9 / 3-channel / fp32-slab layers) the generic pair
         fast, slow = [], []
         for it in self.items:
-            gm, g = it[0].ref.geom, it[0].plans[2]
-            ok = (it[0].kinds[2].bf16 and gm.k == 3 and gm.cin % 32 == 0 and gm.cout % 32 == 0 and not gm.shuffle2
+            gm, g = it.prep.ref.geom, it.prep.plans[2]
+            ok = (it.prep.kinds[2].bf16 and gm.k == 3 and gm.cin % 32 == 0 and gm.cout % 32 == 0 and not gm.shuffle2
                   and g.CoutPad >= gm.cout)
             (fast if ok else slow).append(it)
         res = {}
@@ -1029,11 +1045,10 @@ class WeightGradBatch:
         lib = L.lib()
         table = (L.WeightGradDesc * len(items))()
         res = {}
-        dev = items[0][1].device
-        for i, (p, red, want_w, want_b) in enumerate(items):
+        dev = items[0].red.device
+        for t, (p, red, want_w, want_b) in zip(table, items):
             g = p.plans[2]
             gm = p.ref.geom
-            t = table[i]
             gw = torch.empty_like(p.ref.weight) if want_w else None
             gb = torch.empty_like(p.ref.bias) if (want_b and p.ref.bias is not None) else None
             t.dwpk, t.w_orig, t.grad = red.data_ptr(), p.ref.weight.data_ptr(), _ptr(gw)
@@ -1046,7 +1061,7 @@ class WeightGradBatch:
             res[id(p.ref)] = (gw, gb)
         tab = _table_to_device(table, dev)
         if is_fast:
-            mco, mci = max(it[0].ref.geom.cout for it in items), max(it[0].ref.geom.cin for it in items)
+            mco, mci = max(it.prep.ref.geom.cout for it in items), max(it.prep.ref.geom.cin for it in items)
             work = torch.empty((len(items) * ((mco + 31) // 32) * (mci // 32),), dtype=torch.float32, device=dev)
             L.check(lib.sisr_weights_grad_fast(tab.data_ptr(), len(items), work.data_ptr(), mco, mci, _stream()), 'sisr_weights_grad_fast')
         else:
@@ -1099,8 +1114,10 @@ class BackwardBook:
         p = self.P[id(ref)]
         want_w, want_b = ref.weight.requires_grad, ref.bias is not None and ref.bias.requires_grad
         if want_w or want_b:
-            red = self.wb.add(p, x_op, dy_op)
-            self.wg.add(p, red if red is not None else conv_wgrad(p, x_op, dy_op, defer=self.slabs), want_w, want_b)
+            w = _wgrad_launch(p, x_op, dy_op)
+            if self.wb.offer(w) is None:                # (the batch declines: that same record, in a launch of its own)
+                _launch_wgrad(w, defer=self.slabs)
+            self.wg.add(p, w.red, want_w, want_b)
         if not need_dgrad:
             return None
         if bnb is None:
@@ -1194,9 +1211,8 @@ def bn_backward(dy, x, consts, gamma, slope=None, part=None, slabs=None):
     else:
         job = slabs.pop() if slabs is not None else None
         if job is not None:                     # this launch also sums the slabs of the weight gradient computed before it
-            slab, red, n_slabs, stride, lead = job
-            L.check(lib.sisr_bn_bwd_finalize_slab(C.byref(d), slab.data_ptr(), red.data_ptr(), n_slabs, stride, lead, _stream()),
-                    'sisr_bn_bwd_finalize_slab')
+            L.check(lib.sisr_bn_bwd_finalize_slab(C.byref(d), job.slab.data_ptr(), job.red.data_ptr(), job.n_slabs, job.stride, job.lead,
+                                                  _stream()), 'sisr_bn_bwd_finalize_slab')
         else:
             L.check(lib.sisr_bn_bwd_finalize(C.byref(d), _stream()), 'sisr_bn_bwd_finalize')
     return q, dgamma, dbeta, dslope

@@ -27,6 +27,7 @@ from gpu_helpers import FakeConv, assert_within, nchw, nhwc, pkg
 pytestmark = pytest.mark.gpu
 BF16, F32 = torch.bfloat16, torch.float32
 TANH_ULPS = 2.5        # measured on an MI355X over the to-image and generic cases below: at most 1.21 fp32 ulps of the result; doubled
+ROUTE_FAMILY = ['generic', 'deep', 'toimage', 'trunk', 'thin']      # run.family by _lib.ROUTE_* (enum SisrRoute)
 
 
 @pytest.fixture(scope='module')
@@ -178,15 +179,13 @@ def test_forward(E, L, run, monkeypatch):
     y, sp, cp = E.conv_forward(p, op, stats=stats, **kw)
     # ---- the route
     probe = _probe(E, p, 0, op, y, y_mode=kw.get('y_mode'), epi=kw.get('epi', 0), stats=stats)
-    trunk, thin, toimage = (lib.sisr_conv2d_trunk_eligible(C.byref(probe)), lib.sisr_conv2d_thin_eligible(C.byref(probe)),
-                            lib.sisr_conv2d_toimage_eligible(C.byref(probe)))
+    route = (lib.sisr_conv2d_bf16_route if p.kinds[0].bf16 else lib.sisr_conv2d_f32_route)(C.byref(probe))
     if run.family == 'deep':
         assert p.kinds[0] == E.Kind.DEEP
         rows = p.plans[0].deep.tiles_x * p.plans[0].deep.tiles_q
-    elif run.family == 'thin':
-        assert p.kinds[0] == E.Kind.F32 and thin == 1
     else:
-        assert p.kinds[0] == E.Kind.BF16 and (trunk == 1) == (run.family == 'trunk') and (toimage == 1) == (run.family == 'toimage')
+        assert p.kinds[0] == (E.Kind.F32 if run.family == 'thin' else E.Kind.BF16) and ROUTE_FAMILY[route] == run.family
+        assert route != L.ROUTE_TRUNK or lib.sisr_conv2d_trunk_eligible(C.byref(probe)) == 1              # (1: its forward role)
         rows = p.plans[0].plan.n_tiles
         if run.family == 'trunk' and not run.shuffle2:
             rows = B.TRUNK_WALK[run.shape][0]
@@ -300,16 +299,10 @@ def _wg_setup(E, L, run, monkeypatch, slab_bf16='0'):
     g = E._copy_struct(p.plans[2])
     x_op.fill(g)
     g_op.fill(g, g=True)
-    lib = L.lib()
-    if not p.kinds[2].bf16:
-        route = 'thin' if lib.sisr_wgrad_thin_eligible(C.byref(g)) else 'f32'
-    elif lib.sisr_wgrad_trunk_eligible(C.byref(g)):
-        route = 'trunk'
-    elif lib.sisr_wgrad_toimage_eligible(C.byref(g)):
-        route = 'toimage'
-    else:
-        route = 'deep' if g.deep.enabled and lib.sisr_wgrad_deep_eligible(C.byref(g)) else 'generic'
-    return case, ref, p, x_op, g_op, route
+    bf16 = p.kinds[2].bf16
+    route = ROUTE_FAMILY[(L.lib().sisr_wgrad_bf16_route if bf16 else L.lib().sisr_wgrad_f32_route)(C.byref(g))]
+    # (of the fp32 dispatcher's kernels only the thin one belongs to this family)
+    return case, ref, p, x_op, g_op, route if bf16 or route == 'thin' else 'f32'
 
 
 def _unpack(E, p, ref, red):
@@ -348,8 +341,7 @@ def test_weight_gradient(E, L, run, monkeypatch):
     assert route == run.family, 'the launch ran on the %s kernel' % route
     before = E.KERNEL_COUNTS.get('wgrad_deep', 0)
     red = E.conv_wgrad(p, x_op, g_op)
-    if run.family in ('deep', 'generic'):
-        assert E.KERNEL_COUNTS.get('wgrad_deep', 0) == before + (run.family == 'deep')
+    assert E.KERNEL_COUNTS.get('wgrad_deep', 0) == before + (run.family == 'deep')
     if run.tag == 'padded':
         assert p.plans[2].Cout == 4
     gw, gb = _unpack(E, p, ref, red)
@@ -429,3 +421,55 @@ def test_deep_weight_gradients_of_three_layers_in_one_launch(E, L, stride, monke
     wb.run(pending)
     assert E.KERNEL_COUNTS.get('wgrad_deep_batch', 0) == before + 1 and len(pending.jobs) == 3
     _check_batch(E, members, reds, pending)
+
+
+def _wg_run(family, shape, xpro, gpro, tag=''):
+    r, = [r for r in B.WG_RUNS if (r.family, r.shape, r.xpro, r.gpro, r.tier, r.storage, r.tag) == (family, shape, xpro, gpro, 'grid', 'bf16', tag)]
+    return r
+
+
+# one backward pass over layers of every route: a trunk layer small enough (1,024 pixels) to join wgrad_deep.hip's batch, a
+# wgrad_deep.hip layer with the same batch key, the last conv on its own kernel and on the padded copy of its gradient, a 1 x 1 conv
+BOOK_RUNS = [B.TRUNK_BATCH[0], _wg_run('deep', B.DEEP_WG[0], B.AFFINE_ACT, B.BNBWD), _wg_run('toimage', B.WG_THIN[0], B.ACT, B.TANH_BWD),
+             _wg_run('generic', B.PADDED, B.NONE, B.TANH_BWD, 'padded'), _wg_run('generic', B.GENERIC[5], B.AFFINE_ACT, B.BNACT_BWD)]
+FAMILY_KNOBS = ('SISR_TRUNK', 'SISR_DEEP', 'SISR_WGRAD_DEEP', 'SISR_THIN', 'SISR_PERSIST_MAX_WG')
+
+
+def _book_gradients(E, L, monkeypatch, own_batch_slabs):
+    """BOOK_RUNS through ONE engine.BackwardBook, every member prepared and handed over under the knobs of its own family
+    -> [(run, case, plan, weight gradient, bias gradient)]"""
+    members = []
+    for r in BOOK_RUNS:
+        for k in FAMILY_KNOBS:
+            monkeypatch.delenv(k, raising=False)
+        case, ref, p, x_op, g_op, route = _wg_setup(E, L, r, monkeypatch)
+        assert route == r.family
+        ref.weight.requires_grad_(True)
+        ref.bias.requires_grad_(True)
+        members.append((r, case, ref, p, x_op, g_op))
+    book = E.BackwardBook({id(ref): p for _, _, ref, p, _, _ in members}, [m[2] for m in members], [], None, own_batch_slabs)
+    before = E.KERNEL_COUNTS.get('wgrad_deep_batch', 0)
+    for r, case, ref, p, x_op, g_op in members:
+        for k in FAMILY_KNOBS:
+            monkeypatch.delenv(k, raising=False)
+        _env(monkeypatch, r.family, r.storage, r.shape)
+        assert book.conv_bwd(ref, x_op, g_op, need_dgrad=False) is None
+    # the two layers wgrad_deep.hip's batch keeps; the other three were launched, their slab sums wait
+    assert len(book.wb.items) == 2 and len(book.wb.trunk) == 0 and len(book.wg.items) == 5
+    assert [w.prep for w in book.wb.items] == [members[0][3], members[1][3]]
+    for k in FAMILY_KNOBS:                             # (the batch plans its members' shares at the flush: not under SISR_WGRAD_DEEP=0)
+        monkeypatch.delenv(k, raising=False)
+    book.flush('final')
+    assert E.KERNEL_COUNTS.get('wgrad_deep_batch', 0) == before + 1 and book.wb.items == [] and book.slabs.jobs == []
+    return [(r, case, p.plans[2], book.grads[id(ref.weight)].cpu(), book.grads[id(ref.bias)].cpu()) for r, case, ref, p, _, _ in members]
+
+
+def test_one_backward_book_over_every_route(E, L, monkeypatch):
+    """engine.BackwardBook.conv_bwd builds ONE launch record per weight gradient and either the batch keeps it or it is launched as it
+    is: members of different routes through one book, every gradient equal to its float64 reference bit for bit (grid operands, fp32
+    slabs); a second book -- its batch's slab sums in the common list instead of their own -- gives the same bits"""
+    first = _book_gradients(E, L, monkeypatch, True)
+    for r, case, plan, gw, gb in first:
+        _check_wg(r, case, gw, gb, plan)
+    for (r, _, _, gw, gb), (_, _, _, gw2, gb2) in zip(first, _book_gradients(E, L, monkeypatch, False)):
+        assert torch.equal(gw, gw2) and torch.equal(gb, gb2), '%r: two books differ' % r

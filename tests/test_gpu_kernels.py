@@ -392,7 +392,7 @@ def test_bn_backward_finish_carries_a_slab_reduction(E, L):
         want = E.bn_backward(x, x, consts, gamma, slope=slope, part=part)
         pend = E.PendingSlabs()
         red = torch.full((stride,), float('nan'), device='cuda')
-        pend.jobs.append((slab, red, n_slabs, stride, 0))
+        pend.jobs.append(E.SlabJob(slab, red, n_slabs, stride, 0))
         got = E.bn_backward(x, x, consts, gamma, slope=slope, part=part, slabs=pend)
         assert pend.jobs == []
         assert torch.equal(red, want_red)
@@ -412,7 +412,7 @@ def test_bn_backward_finish_carries_a_slab_reduction(E, L):
         assert maxrel(red, want_red) < 1e-5
         pend = E.PendingSlabs()
         red2 = torch.full((stride,), float('nan'), device='cuda')
-        pend.jobs.append((slab, red2, n_slabs, stride, lead))
+        pend.jobs.append(E.SlabJob(slab, red2, n_slabs, stride, lead))
         E.bn_backward(x, x, consts, gamma, slope=slope, part=part, slabs=pend)
         assert torch.equal(red2, red)
 
@@ -434,7 +434,7 @@ def test_several_slab_reductions_in_one_launch(E, L):
         ref = torch.empty(stride, device='cuda')
         L.check(lib.sisr_slab_reduce_f32(slab.data_ptr(), ref.data_ptr(), n_slabs, stride, lead, st), 'slab_reduce')
         red = torch.full((stride,), float('nan'), device='cuda')
-        pend.jobs.append((slab, red, n_slabs, stride, lead))
+        pend.jobs.append(E.SlabJob(slab, red, n_slabs, stride, lead))
         want.append((red, ref))
     pend.flush()
     assert pend.jobs == []

@@ -9,10 +9,15 @@ print byte-identical JSON.
 --weights prints how engine._layout_weights lays the packed weight images of the layer list out, per build and with / without the
 data gradient: every image's (buffer, offset, fp32 slots rounded up to the 16 bytes the next piece starts on) and the sizes of
 the buffers.  Two trees that lay out alike print byte-identical JSON.
-usage: python tools/plan_digest.py [--routes | --weights] [root of the tree whose package is digested; default: this one]"""
+--wgrad prints which launch engine.WgradDeepBatch().add keeps every layer's weight gradient for -- alone, wgrad_deep.hip's batch or the
+persistent trunk kernel's, with the key of its group in the batch -- over the x prologues none / affine-act and the gradient prologues
+of the layer (operands of one-element host tensors: add() reads their address, type and modes only).  Run it under each batching
+switch (SISR_WGRAD_BATCH=0, SISR_WGRAD_BATCH_TRUNK_PIXELS=0, ...): two trees that batch alike print byte-identical JSON.
+usage: python tools/plan_digest.py [--routes | --weights | --wgrad] [root of the tree whose package is digested; default: this one]"""
 import ctypes as C, hashlib, importlib, itertools, json, os, sys, types
-ROUTES, WEIGHTS = '--routes' in sys.argv[1:], '--weights' in sys.argv[1:]
-_args = [a for a in sys.argv[1:] if a not in ('--routes', '--weights')]
+MODES = ('--routes', '--weights', '--wgrad')
+ROUTES, WEIGHTS, WGRAD = (m in sys.argv[1:] for m in MODES)
+_args = [a for a in sys.argv[1:] if a not in MODES]
 ROOT = os.path.abspath(_args[0] if _args else os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 sys.path.insert(0, ROOT)
 sys.path.insert(1, os.path.dirname(os.path.abspath(__file__)))
@@ -129,6 +134,39 @@ def weights(need_dgrad):
     return {'layers': layers, 'sizes': sizes}
 
 
+def wgrad_batches(geom, g, kinds, n, h, w):
+    """{x prologue, gradient prologue: 'alone' | 'deep <group key>' | 'trunk <group key>'}"""
+    import torch
+    L = E.L
+    prep = types.SimpleNamespace(plans=(None, None, g), kinds=kinds, ref=types.SimpleNamespace(geom=geom))
+    ho, wo = geom.out_hw(h, w)
+    one = lambda dt: torch.zeros(1, dtype=dt)
+    c = one(torch.float32)
+    x = one(torch.float32 if geom.cin == 3 else E.act_dtype(geom.cin))
+    x_mode = L.X_NCHW if geom.cin == 3 else L.X_NHWC                     # (the 3-channel image is NCHW fp32)
+    if geom.shuffle2:                                                     # the upscale conv: the gradient behind the PixelShuffle
+        g_mode, g_t, gpros = L.X_UNSHUFFLE2, one(E.act_dtype(geom.cout // 4)), (L.PRO_ACT_BWD,)
+    elif geom.cout == 3:                                                  # the last conv: the NCHW fp32 image gradient
+        g_mode, g_t, gpros = L.X_NCHW, c, (L.PRO_TANH_BWD,)
+    else:
+        g_mode, g_t, gpros = L.X_NHWC, one(E.act_dtype(geom.cout)), (L.PRO_NONE, L.PRO_BNBWD, L.PRO_BNACT_BWD, L.PRO_ACT_BWD)
+    res = {}
+    for pro, gpro in itertools.product((L.PRO_NONE, L.PRO_AFFINE_ACT), gpros):
+        x_op = E.Operand(x, (n, h, w, geom.cin), pro=pro, mode=x_mode, pa=c, pd=c, slope=1.0)
+        g_op = E.Operand(g_t, (n, ho, wo, geom.cout), pro=gpro, mode=g_mode, x2=g_t, pa=c, pb=c, pd=c, ps=c, pt=c, slope=0.2)
+        wb = E.WgradDeepBatch()
+        red = wb.add(prep, x_op, g_op)
+        assert (red is None) == (not wb.items and not wb.trunk) and len(wb.items) + len(wb.trunk) <= 1
+        # (a member is (prepared layer, filled descriptor, ...): the keys are the engine's own)
+        where = 'alone'
+        for m in wb.items:
+            where = 'deep %s' % (tuple(int(v) for v in E._deep_batch_key(m[1])),)
+        for m in wb.trunk:
+            where = 'trunk %s' % (tuple(int(v) for v in E._trunk_batch_key(m[0], m[1])),)
+        res['pro %d gpro %d' % (pro, gpro)] = where
+    return res
+
+
 out = {}
 for build in ('fp32', 'bf16x3', 'bf16'):
     E.set_precision(build)
@@ -139,5 +177,5 @@ for build in ('fp32', 'bf16x3', 'bf16'):
         geom = E.ConvGeom(cin, cout, k, stride, shuffle2=shuffle2, deep_dgrad=deep_dgrad)
         f, d, g, kinds = geom.plans(n, h, w)
         out['%s %d>%d k%d s%d%s%s %dx%dx%d' % (build, cin, cout, k, stride, ' up' * shuffle2, ' vgg' * deep_dgrad, n, h, w)] = \
-            routes(geom, f, d, g, kinds) if ROUTES else {'f': sha(f), 'd': dgrad(d), 'g': sha(g), 'kinds': [int(v) for v in kinds]}
+            routes(geom, f, d, g, kinds) if ROUTES else wgrad_batches(geom, g, kinds, n, h, w) if WGRAD else {'f': sha(f), 'd': dgrad(d), 'g': sha(g), 'kinds': [int(v) for v in kinds]}
 print(json.dumps(out, indent=1, sort_keys=True))
