@@ -500,6 +500,41 @@ int sisr_eltwise_res_affine(const float *x1, const float *slope1_p, float slope1
  * not followed by... BatchNorm-free sites: model_generator.py:34,48) ; work: [grid] floats */
 int sisr_prelu_slope_grad(const float *dy, const float *pre, int64_t n, float *work, float *out,
                           int32_t dt /* dy, pre */, void *stream);
+/* The whole backward of the generator's last conv (model_generator.py:52-53: 3x3, 64 -> 3, stride 1, pad 1, + Tanh) with fp32
+ * tensors in ONE pass over the two big tensors (toimage_bwd.hip): the upscale stage's pre-activation `pre` is read once, the
+ * gradient `g` wrt its activated value is written once, and the weight / bias gradient slabs and the PReLU-slope gradient of that
+ * stage come out of the same tiles -- instead of sisr_conv2d_wgrad_f32 + sisr_conv2d_f32 (data gradient) + sisr_prelu_slope_grad:
+ *   dyt     = dy * (1 - out^2)   (out: the saved tanh output; NULL: dyt = dy)
+ *   g[p][ci] = sum_(co,ky,kx) W[co][ci][ky][kx] * dyt[co][p + (1 - ky, 1 - kx)]        zero outside the image
+ *   slab / bias_slab: what the weight-gradient kernel of wgrad_toimage.hip writes for x = lrelu(pre, slope), the same slab count
+ *   dslope[0] = sum_(pre <= 0) g * pre        (accumulated in double; dslope_part: one DOUBLE partial per workgroup, added in a
+ *                                              fixed order by a one-workgroup finishing launch and rounded once to fp32)
+ * `wpk` is the layer's packed fp32 FORWARD image [chunk][ky][cout][kx * w_PS + cl] (row length w_KROWP, w_CoutPad couts, chunks
+ * of w_CK channels); CK .. slab_elems describe the slab as SisrWgradDesc's plan fields do.  sisr_toimage_bwd_f32_parts(d) =
+ * workgroups of the launch = rows of `slab` (slab_stride floats each) = doubles of `dslope_part`.  Eligible: that geometry,
+ * H % 8 == 0, W % 32 == 0, fp32 tensors (pre_bf16 = g_bf16 = 0), N * H * W * 256 < 2^31; SISR_TOIMAGE_BWD=0 (and SISR_THIN=0)
+ * answer 0 and the caller keeps the three separate kernels. */
+typedef struct SisrToImageBwdDesc {
+    const float *pre;                        /* [N,H,W,64] NHWC                                               */
+    const float *dy, *out;                   /* [N,3,H,W] NCHW image gradient, saved tanh output or NULL      */
+    const float *wpk;
+    const float *slope_p;                    /* device scalar slope (PReLU weight); NULL: slope               */
+    float *g;                                /* [N,H,W,64] NHWC                                               */
+    float *slab, *bias_slab;
+    void *dslope_part;                       /* [parts] doubles, 8-byte aligned                               */
+    float *dslope;
+    int32_t N, H, W, Cin, Cout;
+    int32_t KH, KW, stride, pad_y, pad_x;
+    int32_t pre_bf16, g_bf16;                /* storage type of pre and g (0: fp32, 1: bf16 -- not eligible)  */
+    int32_t w_CK, w_PS, w_KROWP, w_CoutPad;
+    int32_t CK, PS, KROWP, n_chunk, CoutPad, slab_elems;
+    float slope;
+    int64_t slab_stride;
+} SisrToImageBwdDesc;
+int sisr_toimage_bwd_f32_eligible(const SisrToImageBwdDesc *d);
+int sisr_toimage_bwd_f32_parts(const SisrToImageBwdDesc *d);
+int sisr_toimage_bwd_f32(const SisrToImageBwdDesc *d, void *stream);
+int sisr_toimage_bwd_desc_bytes(void);       /* sizeof(SisrToImageBwdDesc): a binding verifies its mirror with it */
 /* y = a + b (same shape) */
 int sisr_add(const float *a, const float *b, float *y, int64_t n, int32_t dt /* a, b, y */, void *stream);
 

@@ -113,6 +113,13 @@ class BnBwdDesc(C.Structure):
                  ('grid', _i32), ('dy_bf16', _i32), ('x_bf16', _i32)])
 
 
+class ToImageBwdDesc(C.Structure):
+    _fields_ = ([(n, _f) for n in ('pre', 'dy', 'out', 'wpk', 'slope_p', 'g', 'slab', 'bias_slab', 'dslope_part', 'dslope')] +
+                [(n, _i32) for n in ('N', 'H', 'W', 'Cin', 'Cout', 'KH', 'KW', 'stride', 'pad_y', 'pad_x', 'pre_bf16', 'g_bf16',
+                                     'w_CK', 'w_PS', 'w_KROWP', 'w_CoutPad', 'CK', 'PS', 'KROWP', 'n_chunk', 'CoutPad', 'slab_elems')] +
+                [('slope', _f32), ('slab_stride', _i64)])
+
+
 _SIGS = {
     'sisr_conv2d_plan': [C.POINTER(ConvDesc)],
     'sisr_conv2d_f32': [C.POINTER(ConvDesc), _f],
@@ -172,6 +179,10 @@ _SIGS = {
     'sisr_bn_bwd_finalize_slab': [C.POINTER(BnBwdDesc), _f, _f, _i32, _i64, _i64, _f],
     'sisr_eltwise_res_affine': [_f, _f, _f32, _f, _f, _f, _f, _i64, _i32, _i32, _f],
     'sisr_prelu_slope_grad': [_f, _f, _i64, _f, _f, _i32, _f],
+    'sisr_toimage_bwd_f32_eligible': [C.POINTER(ToImageBwdDesc)],
+    'sisr_toimage_bwd_f32_parts': [C.POINTER(ToImageBwdDesc)],
+    'sisr_toimage_bwd_f32': [C.POINTER(ToImageBwdDesc), _f],
+    'sisr_toimage_bwd_desc_bytes': [],
     'sisr_add': [_f, _f, _f, _i64, _i32, _f],
     'sisr_adam_blocks': [_i64],
     'sisr_adam_step': [_f, _i32, _i64] + [C.c_double] * 7 + [_f],
@@ -259,6 +270,8 @@ def lib():
     if n != 8 or list(sizes[:8]) != mine:
         raise RuntimeError('libsisr_hip.so does not match the Python mirror of sisr_hip.h: %s vs %s'
                            % (list(sizes[:8]), mine))
+    if L.sisr_toimage_bwd_desc_bytes() != C.sizeof(ToImageBwdDesc):
+        raise RuntimeError('libsisr_hip.so does not match the Python mirror of SisrToImageBwdDesc')
     _lib = L
     return L
 

@@ -897,6 +897,54 @@ def conv_wgrad(prep, x_op, dy_op, defer=None):
     return _launch_wgrad(_wgrad_launch(prep, x_op, dy_op), defer)
 
 
+def _toimage_bwd_desc(prep, x_op, dy_op):
+    """the SisrToImageBwdDesc of the generator's last conv `prep` for x_op = lrelu(pre, slope) and the NCHW image gradient dy_op
+    (outputs unbound): geometry and slab layout from the planned weight gradient, the weight image's layout from the forward plan"""
+    g, f = prep.plans[2], prep.plans[0].plan
+    d = L.ToImageBwdDesc()
+    for n in ('N', 'H', 'W', 'Cin', 'Cout', 'KH', 'KW', 'stride', 'pad_y', 'pad_x', 'CK', 'PS', 'KROWP', 'n_chunk', 'CoutPad',
+              'slab_elems', 'slab_stride'):
+        setattr(d, n, getattr(g, n))
+    d.w_CK, d.w_PS, d.w_KROWP, d.w_CoutPad = f.CK, f.PS, f.KROWP, f.CoutPad
+    d.pre, d.pre_bf16 = x_op.x1.data_ptr(), _bf(x_op.x1)
+    d.g_bf16 = int(act_dtype(g.Cin) == torch.bfloat16)
+    d.slope_p, d.slope = _slope(x_op.slope)
+    d.dy, d.out = dy_op.x1.data_ptr(), _ptr(dy_op.x2) if dy_op.pro == L.PRO_TANH_BWD else None
+    d.wpk = prep.wpk_fwd.data_ptr()
+    return d
+
+
+def toimage_backward(prep, x_op, dy_op, defer=None):
+    """The whole backward of the generator's last conv in one launch (toimage_bwd.hip): x_op = lrelu(pre, slope), the lazy activation
+    of the last upscale stage; dy_op = the NCHW image gradient (prologue none / tanh-backward).  -> (g, dslope, red): the gradient wrt
+    the activated input, the gradient of `slope` [1] and the buffer the reduced packed weight gradient WILL be in (its slabs are bound
+    and their sum launched or deferred exactly as _launch_wgrad does) -- or None where the kernel does not take the layer (an odd
+    shape, bf16 tensors, SISR_TOIMAGE_BWD=0): the caller keeps conv_wgrad + conv_dgrad + prelu_slope_grad."""
+    lib = L.lib()
+    if any(k.bf16 for k in prep.kinds) or _dgrad_shape(prep.plans[1]) != DG_CONV:
+        return None
+    if x_op.pro != L.PRO_ACT or x_op.mode != L.X_NHWC or dy_op.mode != L.X_NCHW or dy_op.pro not in (L.PRO_NONE, L.PRO_TANH_BWD):
+        return None
+    d = _toimage_bwd_desc(prep, x_op, dy_op)
+    if tuple(x_op.dims) != (d.N, d.H, d.W, d.Cin) or lib.sisr_toimage_bwd_f32_eligible(C.byref(d)) != 1:
+        return None
+    w = _wgrad_launch(prep, x_op, dy_op)
+    job = _bind_slabs(w, L.check_count(lib.sisr_toimage_bwd_f32_parts(C.byref(d)), 'sisr_toimage_bwd_f32_parts'))
+    dev = w.red.device
+    g = torch.empty(tuple(x_op.dims), dtype=torch.float32, device=dev)
+    part = torch.empty((job.n_slabs,), dtype=torch.float64, device=dev)
+    dslope = torch.empty((1,), dtype=torch.float32, device=dev)
+    d.slab, d.bias_slab, d.g = w.g.slab, w.g.bias_slab, g.data_ptr()
+    d.dslope_part, d.dslope = part.data_ptr(), dslope.data_ptr()
+    L.check(lib.sisr_toimage_bwd_f32(C.byref(d), _stream()), 'sisr_toimage_bwd_f32')
+    _count('toimage_bwd')
+    if defer is not None and _on('SISR_FUSE_SLABRED'):
+        defer.jobs.append(job)
+    else:
+        _reduce_slabs(job)
+    return g, dslope, w.red
+
+
 def _deep_batch_key(g):
     """members of one sisr_wgrad_deep_batch launch share the stride (a template argument) and whether the gradient prologue reads
     a second tensor -- the library checks operand_needs_x2(gpro_mode) of every member against the first's"""
@@ -1125,6 +1173,20 @@ class BackwardBook:
         if can_fuse_bn_backward(p):
             return conv_dgrad(p, dy_op, res=res, y_mode=y_mode, bnb=bnb)
         return conv_dgrad(p, dy_op, res=res, y_mode=y_mode), None
+
+    def toimage_bwd(self, ref, x_op, dy_op):
+        """conv_bwd of the generator's last conv AND the slope gradient of the PReLU whose lazy activation x_op is, in one launch
+        (toimage_backward) -> (data gradient, slope gradient), or None where that kernel does not take the layer"""
+        p = self.P[id(ref)]
+        want_w, want_b = ref.weight.requires_grad, ref.bias is not None and ref.bias.requires_grad
+        if not (want_w or want_b):
+            return None
+        r = toimage_backward(p, x_op, dy_op, defer=self.slabs)
+        if r is None:
+            return None
+        g, dslope, red = r
+        self.wg.add(p, red, want_w, want_b)
+        return g, dslope
 
 
 class LazyBN:

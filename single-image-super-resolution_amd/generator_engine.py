@@ -181,19 +181,28 @@ def run_backward(sv, grad_out, need_dx, sink=None, params=()):
     n = sv.x.shape[0]
     # ---- end conv + tanh (or, for forward_no_end, the NCHW -> NHWC change of the incoming gradient) --------
     ho, wo = sv.out.shape[2], sv.out.shape[3]
+    slope_done = None                                       # upscale stage whose slope gradient came out of the end conv's backward
     if topo.end is None:
         # no `end` conv: the incoming gradient is that of the last upscale stage's activation -- or, with no stage at all
         # (the bare trunk, model_generator_progressive.py:40-44), of the trunk's BatchNorm output itself
         g = E.nchw_to_nhwc(grad_out, sv.out.shape[1] * ho * wo, n, ho, wo, sv.out.shape[1])
     else:
         dy = Operand(grad_out, (n, ho, wo, sv.out.shape[1]), pro=L.PRO_TANH_BWD, mode=L.X_NCHW, x2=sv.out)
-        g = conv_bwd(topo.end, sv.end_in, dy)              # grad wrt the (activated) input of `end`
+        # where the last stage's slope wants a gradient, one kernel reads that stage's pre-activation once for the weight gradient,
+        # the data gradient and the slope gradient (engine.toimage_backward); anything it does not take keeps the three kernels
+        last = len(topo.stages) - 1
+        fused = book.toimage_bwd(topo.end, sv.end_in, dy) if last >= 0 and topo.stages[last][1].requires_grad else None
+        if fused is not None:
+            g, grads[id(topo.stages[last][1])] = fused
+            slope_done = last
+        else:
+            g = conv_bwd(topo.end, sv.end_in, dy)          # grad wrt the (activated) input of `end`
     # ---- upscale stages, last to first ---------------------------------------------------------------
     part = None
     for k in range(len(topo.stages) - 1, -1, -1):
         ref, slope = topo.stages[k]
         pre = sv.stage_pre[k]
-        if slope.requires_grad:
+        if slope.requires_grad and k != slope_done:
             grads[id(slope)] = E.prelu_slope_grad(g, pre)
         hk, wk, cq = pre.shape[1] // 2, pre.shape[2] // 2, pre.shape[3]
         dy = Operand(g, (n, hk, wk, 4 * cq), pro=L.PRO_ACT_BWD, mode=L.X_UNSHUFFLE2, x2=pre, slope=slope)
