@@ -655,6 +655,42 @@ int sisr_patch_draws_host(int64_t t, uint64_t seed, int32_t rank, int32_t world,
 int sisr_patch_gather(const unsigned char *data, int32_t M, int32_t H0, int32_t W0, int32_t C, const int32_t *draws_dev,
                       int32_t B, int32_t h, int32_t w, float mean, float stdv, void *dst, int32_t dst_kind, void *stream);
 
+/* ---- the same source over images of MIXED sizes, and a shuffled epoch.  One uint8 buffer holds M images, image i as
+ *      [H][W][C] row-interleaved bytes from byte `offset` on (any offset; gaps between images are allowed); the table of M
+ *      records lives in device memory beside it.  The host validates a table once (patches.PackedImages); the kernels do not
+ *      trust it: a byte outside the buffer is never loaded. */
+typedef struct SisrImageRec {
+    int64_t offset;            /* first byte of the image inside the buffer                     */
+    int32_t H, W;
+} SisrImageRec;
+/* sisr_patch_draw / sisr_patch_draws_host with the offsets drawn inside the DRAWN image: the same four Philox words,
+ *          index as the order says   y0 = mulhi32(r1, H_i - h + 1)   x0 = mulhi32(r2, W_i - w + 1)   ops = r3 & ops_mask
+ *      with H_i, W_i from table[index]; table NULL: every image is H0 x W0 (with a table H0 and W0 are not read).  A NULL table or
+ *      a table of equal sizes with order 0 or 1 gives sisr_patch_draw's table bit for bit.
+ *      order 2 = permuted (these two entry points only, with or without a table): every image at most once per epoch, in a new
+ *      random order each epoch.  nb = M / (B * world) batches per epoch (nb == 0: SISR_E_BADARG), epoch e = t / nb, position
+ *      p = ((t mod nb) * world + rank) * B + b, index = sigma_e(p), where sigma_e is a bijection of [0, M) that depends on
+ *      (seed, e) alone -- never on rank or b: the ranks of an epoch hold disjoint images; the M - nb * B * world images that
+ *      sigma_e puts last sit the epoch out.  sigma_e is the swap-or-not shuffle (Hoang, Morris, Rogaway, CRYPTO 2012), 24 rounds,
+ *      no cycle walking, any M; round r = 0 .. 23, with Philox keyed by the seed:
+ *          K = mulhi32(philox(e low, e high, r, 0xFFFFFFFF)[0], M)      x' = (K + M - x) mod M
+ *          if (philox(e low, e high, max(x, x'), 0xFFFFFFFE - r)[0] & 1)  x = x'
+ *      (word 3 of a sample's counter is its rank < 2^31, so no counter is used twice).
+ *      The host entry point also refuses a table with an image smaller than the window; the device one cannot see its table and
+ *      gives such an image offset 0 (the gather then clamps). */
+int sisr_patch_draw_table(int64_t *step_dev, uint64_t seed, int32_t rank, int32_t world, int32_t order, int32_t B, int32_t M,
+                          int32_t H0, int32_t W0, const SisrImageRec *table_dev /* NULL: uniform H0 x W0 */, int32_t h, int32_t w,
+                          int32_t ops_mask, int32_t *draws_dev, void *stream);
+int sisr_patch_draws_table_host(int64_t t, uint64_t seed, int32_t rank, int32_t world, int32_t order, int32_t B, int32_t M,
+                                int32_t H0, int32_t W0, const SisrImageRec *table_host /* may be NULL */, int32_t h, int32_t w,
+                                int32_t ops_mask, int32_t *draws_host);
+/* sisr_patch_gather with base address and row pitch from table_dev[index]: the same tiles, the same two destination kinds, the
+ * same two fp32 expressions.  index is clamped into [0, M) and y0, x0 into the drawn image's own range; offsets are 64-bit; a
+ * byte at an offset outside [0, data_bytes) is not loaded and reads as 0. */
+int sisr_patch_gather_table(const unsigned char *data, int64_t data_bytes, const SisrImageRec *table_dev, int32_t M, int32_t C,
+                            const int32_t *draws_dev, int32_t B, int32_t h, int32_t w, float mean, float stdv, void *dst,
+                            int32_t dst_kind, void *stream);
+
 /* ---- image-quality metrics: per-image PSNR and SSIM of two NCHW fp32 batches (the reference reports neither: its to-do list,
  *      README.md:88).  View applied on load: `crop` pixels stripped from every side; C == 3 with luma != 0: the BT.601 full-range
  *      plane Y = 0.299 R + 0.587 G + 0.114 B instead of the three planes.  PSNR = 10 log10(data_range^2 / mse), +inf for equal
@@ -760,7 +796,7 @@ int sisr_ema_update(const SisrEmaDesc *table_dev, int32_t n, int64_t total_block
 int sisr_ema_swap(const SisrEmaDesc *table_dev, int32_t n, int64_t total_blocks, void *stream);
 
 /* sizeof() of the descriptor structs in declaration order (Conv, Wgrad, Weight, WeightGrad,
- * BnBwd, ConvPlan, DeepPlan, WgradDeepPlan) so a binding can verify its mirror of this header; returns the count. */
+ * BnBwd, ConvPlan, DeepPlan, WgradDeepPlan, ImageRec) so a binding can verify its mirror of this header; returns the count. */
 int sisr_struct_sizes(int32_t *out, int32_t cap);
 int sisr_device_info(int32_t *n_cu, int32_t *lds_per_cu, char *arch, int32_t arch_len);
 int sisr_mfma_selftest(float *out_dev /* >= 32*32 floats */, void *stream);

@@ -106,6 +106,10 @@ class EmaDesc(C.Structure):
     _fields_ = [('ema', _f), ('src', _f), ('numel', _i64), ('block_start', _i64), ('mode', _i32), ('pad', _i32)]
 
 
+class ImageRec(C.Structure):
+    _fields_ = [('offset', _i64), ('H', _i32), ('W', _i32)]
+
+
 class BnBwdDesc(C.Structure):
     _fields_ = ([(n, _f) for n in ('dy', 'x', 'scale', 'shift', 'mean', 'invstd', 'gamma', 'work',
                                    'qa', 'qb', 'qd', 'dgamma', 'dbeta', 'dslope')] +
@@ -214,6 +218,9 @@ _SIGS = {
     'sisr_patch_draw': [_f, C.c_uint64] + [_i32] * 10 + [_f, _f],
     'sisr_patch_draws_host': [_i64, C.c_uint64] + [_i32] * 10 + [_f],
     'sisr_patch_gather': [_f, _i32, _i32, _i32, _i32, _f, _i32, _i32, _i32, _f32, _f32, _f, _i32, _f],
+    'sisr_patch_draw_table': [_f, C.c_uint64] + [_i32] * 7 + [_f] + [_i32] * 3 + [_f, _f],
+    'sisr_patch_draws_table_host': [_i64, C.c_uint64] + [_i32] * 7 + [_f] + [_i32] * 3 + [_f],
+    'sisr_patch_gather_table': [_f, _i64, _f, _i32, _i32, _f, _i32, _i32, _i32, _f32, _f32, _f, _i32, _f],
     'sisr_bicubic_fwd': [_f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _f],
     'sisr_bicubic_bwd': [_f, _f, _f, _i32, _i32, _i32, _i32, _i32, _f],
     'sisr_image_metrics_ws_floats': [_i32, _i32, _i32, _i32, _i32, _i32],
@@ -264,12 +271,13 @@ def lib():
     L.sisr_weight_image_bytes.restype = C.c_int64
     L.sisr_version.restype = C.c_char_p
     L.sisr_version.argtypes = []
-    sizes = (_i32 * 8)()
-    n = L.sisr_struct_sizes(sizes, 8)
-    mine = [C.sizeof(t) for t in (ConvDesc, WgradDesc, WeightDesc, WeightGradDesc, BnBwdDesc, ConvPlan, DeepPlan, WgradDeepPlan)]
-    if n != 8 or list(sizes[:8]) != mine:
+    sizes = (_i32 * 9)()
+    n = L.sisr_struct_sizes(sizes, 9)
+    mine = [C.sizeof(t) for t in (ConvDesc, WgradDesc, WeightDesc, WeightGradDesc, BnBwdDesc, ConvPlan, DeepPlan, WgradDeepPlan,
+                                  ImageRec)]
+    if n != 9 or list(sizes[:9]) != mine:
         raise RuntimeError('libsisr_hip.so does not match the Python mirror of sisr_hip.h: %s vs %s'
-                           % (list(sizes[:8]), mine))
+                           % (list(sizes[:9]), mine))
     if L.sisr_toimage_bwd_desc_bytes() != C.sizeof(ToImageBwdDesc):
         raise RuntimeError('libsisr_hip.so does not match the Python mirror of SisrToImageBwdDesc')
     _lib = L

@@ -9,7 +9,17 @@ One batch of 16 HR 96 / LR 48 pairs out of a 64-image stand-in dataset of CelebA
   crop           DevicePatchSource(crop=(96, 96), hflip=True): random crops and flips, no resize;
   resize_graph / crop_graph   the same two replayed from a graph.GraphedStep.
 After a warm-up the variants alternate, every repetition between its own pair of device events; medians are reported.  The outputs
-of host and resize are compared bit for bit first.  Facts for DESIGN.md section 12, not a condition.  Refuses to run without a GPU."""
+of host and resize are compared bit for bit first.  Facts for DESIGN.md section 12, not a condition.  Refuses to run without a GPU.
+
+python tools/probe_patchsrc.py --ragged [--out profiles/patchsrc_ragged_probe.json]
+the crop source over a packed store (patches.RaggedPatchSource) beside the uniform one, same batch and window, same alternation:
+  crop_a/_b      DevicePatchSource(crop=(96, 96), hflip=True) as above, through sisr_patch_draw / sisr_patch_gather, twice;
+  ragged_equal   RaggedPatchSource over the same 64 images packed one after the other;
+  ragged_mixed   RaggedPatchSource over 64 images of mixed sizes (96 .. 351 pixels a side, the same number of images);
+  crop_permuted / ragged_permuted   the first and the third in order='permuted' (24 rounds of the shuffle in the draw launch).
+Two alternations: the six issued eagerly, then the same six replayed from a graph.GraphedStep each (a replay leaves the queue
+empty behind it, which an eager variant next in turn would pay for).  The batches of crop and ragged_equal are compared bit for
+bit first."""
 import argparse
 import json
 import os
@@ -29,8 +39,10 @@ B, M, SHAPE, HR, LR = 16, 64, (218, 178, 3), (96, 96), (48, 48)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=200)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'patchsrc_probe.json'))
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--ragged', action='store_true')
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, 'profiles', 'patchsrc_ragged_probe.json' if args.ragged else 'patchsrc_probe.json')
     if not torch.cuda.is_available():
         sys.exit('probe_patchsrc: no GPU: nothing is measured without one')
     if args.reps < 200:
@@ -40,6 +52,8 @@ def main():
     gen = torch.Generator().manual_seed(3)
     host = torch.randint(0, 256, (M,) + SHAPE, dtype=torch.uint8, generator=gen)
     dataset = host.cuda()
+    if args.ragged:
+        return ragged(args, P, G, host, dataset)
     pinned = host[:B].clone().pin_memory()
     staged = torch.empty_like(pinned, device='cuda')
     pipe = P.PatchPipeline(HR, LR)
@@ -69,6 +83,38 @@ def main():
     print(json.dumps(res))
     if not same:
         sys.exit('probe_patchsrc: the host-fed path and the device source disagree on the same images')
+
+
+def ragged(args, P, G, host, dataset):
+    sizes = [(96 + (37 * i) % 256, 96 + (91 * i) % 256) for i in range(M)]
+    gen = torch.Generator().manual_seed(4)
+    mixed = P.PackedImages.from_images([torch.randint(0, 256, (h, w, 3), dtype=torch.uint8, generator=gen) for h, w in sizes], 'cuda')
+    equal = P.PackedImages.from_images(list(host), 'cuda')
+    crop = lambda **kw: P.DevicePatchSource(dataset, B, LR, crop=HR, hflip=True, seed=1, **kw)
+    rag = lambda store, **kw: P.RaggedPatchSource(store, B, LR, crop=HR, hflip=True, seed=1, **kw)
+    a, b = crop()(), rag(equal)()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]))
+    make = lambda: dict(crop_a=crop(), ragged_equal=rag(equal), ragged_mixed=rag(mixed), crop_permuted=crop(order='permuted'),
+                        ragged_permuted=rag(mixed, order='permuted'), crop_b=crop())
+    med = lambda variants: {k: round(statistics.median(v), 2) for k, v in alternate(variants, args.reps).items()}
+    eager = med(make())
+    graph = med({k: G.GraphedStep(lambda src=src: src()) for k, src in make().items()})
+    spread = lambda t: round(abs(t['crop_a'] - t['crop_b']), 2)
+    res = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, reps=args.reps, batch=B, window=list(HR), lr=list(LR),
+               uniform_dataset=[M] + list(SHAPE), mixed_sizes=dict(images=M, min=[min(s[0] for s in sizes), min(s[1] for s in sizes)],
+                                                                  max=[max(s[0] for s in sizes), max(s[1] for s in sizes)],
+                                                                  bytes=mixed.data.numel()),
+               crop_and_ragged_equal_outputs_bit_equal=same,
+               what='medians of per-repetition device-event times in microseconds; two alternations in one process: the variants '
+                    'issued eagerly, then each replayed from a GraphedStep; crop_a and crop_b are the same source twice',
+               eager_median_us=eager, eager_crop_spread_us=spread(eager), graph_median_us=graph, graph_crop_spread_us=spread(graph))
+    with open(args.out, 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+    print(json.dumps(res))
+    if not same:
+        sys.exit('probe_patchsrc: the uniform and the packed source disagree on the same images')
 
 
 if __name__ == '__main__':
