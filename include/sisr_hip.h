@@ -691,6 +691,40 @@ int sisr_patch_gather_table(const unsigned char *data, int64_t data_bytes, const
                             const int32_t *draws_dev, int32_t B, int32_t h, int32_t w, float mean, float stdv, void *dst,
                             int32_t dst_kind, void *stream);
 
+/* ---- whole-image super-resolution in tiles: an image of any size is cut into overlapping windows of one
+ *      shape, the generator runs over them as a batch and the SR tiles are stitched.  The table rows are sisr_patch_gather's
+ *      (index, y0, x0, ops); tiles are numbered row-major over the outer product of the two axis plans. ------------------------- */
+/* HOST, no HIP call: the plan of one axis of extent L (LR pixels) for windows of extent T with `halo` pixels of context on every
+ * interior side.  L <= T: one window [0, L).  Otherwise core = T - 2 halo >= 1 (else SISR_E_BADARG), n = ceil((L - 2 halo) / core),
+ * origins a_i = min(i core, L - T) (strictly increasing; a window that reaches a border is flush with it) and ownership boundaries
+ * b_i = (a_{i+1} + a_i + T) / 2 for i < n - 1, b_{n-1} = L: window i owns [b_{i-1}, b_i) with b_{-1} = 0, and every owned pixel is
+ * at least `halo` away from each window edge that is not an image border.  Returns n; a_out / b_out (`cap` entries each) may both
+ * be NULL for the count alone; n > cap: SISR_E_TOOBIG.  SISR_E_BADARG for L < 1, T < 1, halo < 0, one NULL array, cap < 1. */
+int sisr_tile_axis(int32_t L, int32_t T, int32_t halo, int32_t *a_out, int32_t *b_out, int32_t cap);
+/* sisr_patch_gather for ONE fp32 source: tile b = src[:, y0 : y0 + th, x0 : x0 + tw] (src [C][H][W], already normalised) after
+ * hflip, vflip, transposition as row b of table_dev says -> dst [n][C][th][tw], bit-copied.  Same clamping: y0, x0 into range, bit 2
+ * ignored while th != tw, the index ignored; nothing outside src is read.  SISR_E_BADARG before any HIP call for null pointers,
+ * sizes < 1, a window larger than the image, C outside 1..4; SISR_E_TOOBIG for n or th / 32 above 65535. */
+int sisr_tile_gather_f32(const float *src, int32_t C, int32_t H, int32_t W, const int32_t *table_dev, int32_t n, int32_t th,
+                         int32_t tw, float *dst, void *stream);
+/* tiles: [E ny nx][C][scale th][scale tw] fp32, member e of the self-ensemble at rows e ny nx ... with the ops of its table rows
+ * (the planner writes ops = e); ay / by, ax / bx: the two axis plans in DEVICE memory.  dst_kind 0: [C][scale H][scale W] fp32;
+ * 1: [scale H][scale W][C] uint8.  Output pixel (Y, X), per axis at LR position p = (Y + 0.5) / scale and feather f:
+ *     r_i = clamp(min(dL, dR), 0, 1)   dL = (p - (b_{i-1} - f)) / 2f (first tile: +inf)   dR = ((b_i + f) - p) / 2f (last: +inf)
+ *     w_i = r_i / sum_j r_j            (f = 0: r_i is the indicator of the owned interval)
+ * the 2-D weight is the product of the two axes'; 0 <= f <= halo keeps a weight's support inside its window.
+ *     v_e = sum over the tiles with weight, ascending, of w * tile[inverse ops (Y - scale a_y, X - scale a_x)]
+ *     v   = (sum_e v_e) (1 / E), e ascending; f = 0 and E = 1: the owning tile's value, copied
+ * (the inverse of "hflip, vflip, transposition" is "transposition, vflip, hflip").  fp32: v.  uint8: p = (v stdv + mean) 255 in
+ * fp32, q = floor(p + 0.5) clamped to [0, 255], NaN -> 0.  One launch, no atomics, plain vector stores: deterministic, capturable.
+ * Origins are clamped into the image and tile coordinates into the tile: no table can make the kernel touch memory outside
+ * tiles / dst.  SISR_E_BADARG before any HIP call for null pointers, sizes < 1, th > H or tw > W, scale not in {1, 2, 4, 8}, E not
+ * in {1, 8}, E = 8 with th != tw, C outside 1..4, f outside [0, halo] (NaN included), an unknown dst_kind. */
+int sisr_tile_stitch(const float *tiles, const int32_t *table_dev, const int32_t *ay_dev, const int32_t *by_dev, int32_t ny,
+                     const int32_t *ax_dev, const int32_t *bx_dev, int32_t nx, int32_t C, int32_t H, int32_t W, int32_t th,
+                     int32_t tw, int32_t scale, int32_t halo, float feather, int32_t E, float mean, float stdv, void *dst,
+                     int32_t dst_kind, void *stream);
+
 /* ---- image-quality metrics: per-image PSNR and SSIM of two NCHW fp32 batches (the reference reports neither: its to-do list,
  *      README.md:88).  View applied on load: `crop` pixels stripped from every side; C == 3 with luma != 0: the BT.601 full-range
  *      plane Y = 0.299 R + 0.587 G + 0.114 B instead of the three planes.  PSNR = 10 log10(data_range^2 / mse), +inf for equal

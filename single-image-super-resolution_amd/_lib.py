@@ -221,6 +221,9 @@ _SIGS = {
     'sisr_patch_draw_table': [_f, C.c_uint64] + [_i32] * 7 + [_f] + [_i32] * 3 + [_f, _f],
     'sisr_patch_draws_table_host': [_i64, C.c_uint64] + [_i32] * 7 + [_f] + [_i32] * 3 + [_f],
     'sisr_patch_gather_table': [_f, _i64, _f, _i32, _i32, _f, _i32, _i32, _i32, _f32, _f32, _f, _i32, _f],
+    'sisr_tile_axis': [_i32, _i32, _i32, _f, _f, _i32],
+    'sisr_tile_gather_f32': [_f, _i32, _i32, _i32, _f, _i32, _i32, _i32, _f, _f],
+    'sisr_tile_stitch': [_f, _f, _f, _f, _i32, _f, _f, _i32] + [_i32] * 7 + [_f32, _i32, _f32, _f32, _f, _i32, _f],
     'sisr_bicubic_fwd': [_f, _f, _i32, _i32, _i32, _i32, _i32, _i32, _f],
     'sisr_bicubic_bwd': [_f, _f, _f, _i32, _i32, _i32, _i32, _i32, _f],
     'sisr_image_metrics_ws_floats': [_i32, _i32, _i32, _i32, _i32, _i32],
