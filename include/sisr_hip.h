@@ -691,6 +691,48 @@ int sisr_patch_gather_table(const unsigned char *data, int64_t data_bytes, const
                             const int32_t *draws_dev, int32_t B, int32_t h, int32_t w, float mean, float stdv, void *dst,
                             int32_t dst_kind, void *stream);
 
+/* ---- randomised blur + noise degradation: y = clamp(bicubic(x (*) k) + sigma_n z), per-sample k and sigma_n.
+ *      x [N][C][H][W] fp32, 1 <= C <= 4; k [N][K][K] fp32, K odd in 1..21, R = (K - 1) / 2; y [N][C][h][w], any h, w >= 1.
+ *        blur      b[n,c,y,x] = sum_{dy,dx in [-R,R]} k[n][dy+R][dx+R] x[n,c,clamp(y+dy,0,H-1),clamp(x+dx,0,W-1)]   (correlation,
+ *                  replicate border; k is used as given, not renormalised)
+ *        resample  r = bicubic(b) exactly as sisr_bicubic_fwd (align_corners, A = -0.75, scale (in-1)/(out-1), clamped taps)
+ *        noise     y = r + sigma_n[n] z, then with `clamp` the clamp to [-1, 1]; a NULL sigma_n: no noise
+ *      Random numbers: Philox4x32-10 keyed by the seed as the patch source's, word 3 of the counter tagged (patch-source counters
+ *      carry ranks < 2^31 or tags >= 0xFFFFFFE7 there).  u_i = ((r_i >> 8) + 0.5) 2^-24 in fp32.
+ *        parameters of sample b at step t: counter {t low, t high, b, 0xFE010000 | rank}, 0 <= rank < 65536:
+ *            sigma1 = lo + (hi - lo) u0   sigma2 = anisotropic ? lo + (hi - lo) u1 : sigma1   theta = pi u2   sigma_n = nlo + (nhi - nlo) u3
+ *            weight(dy, dx) = exp(-(u^2 / sigma1^2 + v^2 / sigma2^2) / 2), u = cos(theta) dx + sin(theta) dy, v = -sin(theta) dx + cos(theta) dy,
+ *            divided by the sum of the K^2 weights, added in fp32 in index order
+ *        noise of output element e (flat index over [N][C][h][w]): group g = e / 4, counter {t low, t high, g, 0xFE020000 | rank}:
+ *            z0, z1 = sqrt(-2 ln u0) (cos, sin)(2 pi u1), z2, z3 likewise from u2, u3; element e takes z[e mod 4]
+ *            (logf / log1pf / cosf / sinf / sqrtf; ln u is taken from the exact 1 - u above 1/2).  N C h w >= 2^34: SISR_E_TOOBIG.
+ *      Every entry point returns SISR_E_BADARG before any HIP call for null pointers, sizes < 1, K even or outside 1..21, C outside
+ *      1..4, sigma lo > hi or lo <= 0, a negative noise bound or nlo > nhi, rank outside [0, 65536). ---------------------------------- */
+/* One workgroup: t = *step_dev; kernels_dev [B][K][K], noise_sigma_dev [B], drawn_step_dev[0] = t; *step_dev = t + 1 (an ordinary
+ * store by one thread behind a barrier: a captured launch advances on every replay). */
+int sisr_degrade_draw(int64_t *step_dev, uint64_t seed, int32_t rank, int32_t B, int32_t K, float sigma_lo, float sigma_hi,
+                      int32_t anisotropic, float noise_lo, float noise_hi, float *kernels_dev, float *noise_sigma_dev,
+                      int64_t *drawn_step_dev, void *stream);
+/* HOST: the same arithmetic (one __host__ __device__ text) for step t >= 0 into host memory, no GPU involved.  params_host (may be
+ * NULL): [B][4] = sigma1, sigma2, theta, sigma_n. */
+int sisr_degrade_params_host(int64_t t, uint64_t seed, int32_t rank, int32_t B, int32_t K, float sigma_lo, float sigma_hi,
+                             int32_t anisotropic, float noise_lo, float noise_hi, float *kernels_host, float *noise_sigma_host,
+                             float *params_host);
+/* HOST: z of output elements first .. first + count - 1 at step t, no GPU involved */
+int sisr_degrade_noise_host(int64_t t, uint64_t seed, int32_t rank, int64_t first, int64_t count, float *z_host);
+/* One launch: one workgroup per tile of LR pixels and (n, c) stages the HR footprint in LDS (the sample's kernel arrives by
+ * scalar loads), blurs the pixels the tile's taps read, resamples, adds the noise of step *step_dev (read only with a non-NULL noise_sigma) and clamps.
+ * The tile shrinks with the HR / LR ratio so that the LDS stays under 64 KB; every ratio is served (a 1 x 1 tile always fits).
+ * SISR_E_TOOBIG also for N C or the rows of tiles above 65535 (sisr_degrade_bwd: N C or H / 32 above 65535). */
+int sisr_degrade_fwd(const float *x, const float *kernels, const float *noise_sigma /* [N] or NULL */, const int64_t *step_dev,
+                     uint64_t seed, int32_t rank, float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t K, int32_t h,
+                     int32_t w, int32_t clamp, void *stream);
+/* dx = B^T R^T (dy * m), m = [-1 < y_saved < 1] (NULL: m = 1); no gradient for the kernels or the noise.  Gather form, fixed
+ * order, no atomics.  The transpose of the replicate border folds the padded coordinates onto the border pixel: row 0 collects
+ * padded rows -R .. 0, row H - 1 rows H - 1 .. H - 1 + R, likewise in x; H or W below R is fine. */
+int sisr_degrade_bwd(const float *dy, const float *y_saved, const float *kernels, float *dx, int32_t N, int32_t C, int32_t H,
+                     int32_t W, int32_t K, int32_t h, int32_t w, void *stream);
+
 /* ---- whole-image super-resolution in tiles: an image of any size is cut into overlapping windows of one
  *      shape, the generator runs over them as a batch and the SR tiles are stitched.  The table rows are sisr_patch_gather's
  *      (index, y0, x0, ops); tiles are numbered row-major over the outer product of the two axis plans. ------------------------- */

@@ -9,7 +9,7 @@ reference's own module names; ``install()`` additionally patches ``utils.lr_from
 from . import _lib  # noqa: F401
 
 
-def install(fused_adam=False, fused_losses=False):
+def install(fused_adam=False, fused_losses=False, degradation=None):
     """Register this package's model modules under the reference's top-level module names, so the
     reference's ``train.py`` / ``config.py`` import them unchanged, and point ``utils.lr_from_hr`` -- the one hot
     function of the reference's ``utils`` module (utils.py:22-31; called at train.py:46,96, config.py:272) -- at the
@@ -18,7 +18,9 @@ def install(fused_adam=False, fused_losses=False):
     only when no ``utils`` module is importable at all (this repository's own tests) is the package's ``utils``
     registered under that name.  ``fused_adam=True`` also points ``torch.optim.Adam`` (what config.py:293-294
     instantiates) at the fused multi-tensor Adam of ``optim.py``; ``fused_losses=True`` points ``torch.nn.BCELoss`` (what
-    config.py:107 instantiates) at the fused ``losses.BCELoss``."""
+    config.py:107 instantiates) at the fused ``losses.BCELoss``; ``degradation=`` a ``degrade.Degrader`` makes the patched
+    ``utils.lr_from_hr`` that object's method -- a blur kernel and a noise level drawn per sample and per call
+    -- instead of the bicubic kernel; the default None leaves the bicubic path as it is."""
     import importlib
     import sys
     if fused_adam:
@@ -33,8 +35,9 @@ def install(fused_adam=False, fused_losses=False):
     try:
         ref_utils = importlib.import_module('utils')          # the reference's utils.py, when it is on the path
     except ImportError:
-        sys.modules['utils'] = ours
-        return
+        sys.modules['utils'] = ref_utils = ours
     if ref_utils is not ours:
         ref_utils.lr_from_hr = ours.lr_from_hr
         ref_utils._subsampling_interpolation = ours._subsampling_interpolation
+    if degradation is not None:
+        ref_utils.lr_from_hr = degradation.lr_from_hr

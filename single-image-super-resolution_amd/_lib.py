@@ -221,6 +221,11 @@ _SIGS = {
     'sisr_patch_draw_table': [_f, C.c_uint64] + [_i32] * 7 + [_f] + [_i32] * 3 + [_f, _f],
     'sisr_patch_draws_table_host': [_i64, C.c_uint64] + [_i32] * 7 + [_f] + [_i32] * 3 + [_f],
     'sisr_patch_gather_table': [_f, _i64, _f, _i32, _i32, _f, _i32, _i32, _i32, _f32, _f32, _f, _i32, _f],
+    'sisr_degrade_draw': [_f, C.c_uint64, _i32, _i32, _i32, _f32, _f32, _i32, _f32, _f32, _f, _f, _f, _f],
+    'sisr_degrade_params_host': [_i64, C.c_uint64, _i32, _i32, _i32, _f32, _f32, _i32, _f32, _f32, _f, _f, _f],
+    'sisr_degrade_noise_host': [_i64, C.c_uint64, _i32, _i64, _i64, _f],
+    'sisr_degrade_fwd': [_f, _f, _f, _f, C.c_uint64, _i32, _f] + [_i32] * 8 + [_f],
+    'sisr_degrade_bwd': [_f, _f, _f, _f] + [_i32] * 7 + [_f],
     'sisr_tile_axis': [_i32, _i32, _i32, _f, _f, _i32],
     'sisr_tile_gather_f32': [_f, _i32, _i32, _i32, _f, _i32, _i32, _i32, _f, _f],
     'sisr_tile_stitch': [_f, _f, _f, _f, _i32, _f, _f, _i32] + [_i32] * 7 + [_f32, _i32, _f32, _f32, _f, _i32, _f],

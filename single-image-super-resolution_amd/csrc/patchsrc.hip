@@ -8,22 +8,9 @@
 // The random numbers are Philox4x32-10 (Salmon et al., SC'11) keyed by the seed and counted by (t, b, rank): one text for host
 // and device (sisr_patch_draws_host is the same arithmetic without a GPU).  No atomics, plain vector stores, nothing read back.
 #include "sisr_dev.h"
+#include "sisr_philox.h"
 
 #include <algorithm>
-
-// ---- Philox4x32-10 -------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ uint32_t patch_mulhi32(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
-
-__host__ __device__ __forceinline__ void philox4x32_10(const uint32_t ctr[4], uint32_t k0, uint32_t k1, uint32_t out[4]) {
-    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3];
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = patch_mulhi32(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = patch_mulhi32(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 #define PATCH_ORDER_RANDOM 0
 #define PATCH_ORDER_SEQUENTIAL 1
