@@ -807,7 +807,9 @@ int sisr_bce_bwd(const float *p, const float *t_vec, float t_scalar, int64_t n, 
  * One launch performs torch.optim.Adam's update (amsgrad=False, maximize=False; config.py:292-294, stepped at
  * train.py:75,108) for every parameter of a network.  Table in DEVICE memory; block_start = running sum of
  * sisr_adam_blocks(numel) over the preceding entries; total_blocks = that sum over all entries.  The caller passes
- * lr (after any LambdaLR factor, config.py:170-180) and the bias corrections 1 - beta^t of the step being taken. */
+ * lr (after any LambdaLR factor, config.py:170-180) and the bias corrections 1 - beta^t of the step being taken.
+ * Tensors need only 4-byte alignment: 16-byte accesses are used when numel % 4 == 0 and every pointer the launch touches
+ * (p, m, v and g for the steps, g for the sum of squares) is 16-byte aligned. */
 typedef struct SisrAdamDesc {
     float *p, *m, *v;          /* parameter, exp_avg, exp_avg_sq (updated in place)            */
     const float *g;            /* gradient                                                      */

@@ -51,7 +51,6 @@ static int mse_grid(int64_t tiles) {
 template <typename V>
 __global__ void __launch_bounds__(SISR_BLOCK) mse_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                                  int64_t nv, int head, int tail, float* __restrict__ part) {
-    __shared__ float red[SISR_BLOCK / 64];
     constexpr int E = (int)(sizeof(V) / sizeof(float));
     const int tid = threadIdx.x;
     const V* av = reinterpret_cast<const V*>(a);
@@ -76,38 +75,22 @@ __global__ void __launch_bounds__(SISR_BLOCK) mse_partial_kernel(const float* __
 #pragma unroll
         for (int u = 0; u < MSE_UNROLL; ++u) { const V d = x[u] - y[u]; acc[u] += d * d; }
     }
-    float s = lanes_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
+    float s[1] = {lanes_sum((acc[0] + acc[1]) + (acc[2] + acc[3]))};
     static_assert(MSE_UNROLL == 4, "the accumulators are folded pairwise above");
     if (blockIdx.x == 0) {                     // the <= 3 + 3 elements around the aligned body
-        if (tid < head) { const float d = a[tid - head] - b[tid - head]; s += d * d; }
-        if (tid < tail) { const float d = a[nv * E + tid] - b[nv * E + tid]; s += d * d; }
+        if (tid < head) { const float d = a[tid - head] - b[tid - head]; s[0] += d * d; }
+        if (tid < tail) { const float d = a[nv * E + tid] - b[nv * E + tid]; s[0] += d * d; }
     }
-    s = wave_sum(s);
-    if ((tid & 63) == 0) red[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) {
-        float t = red[0];
-#pragma unroll
-        for (int w = 1; w < SISR_BLOCK / 64; ++w) t += red[w];
-        part[blockIdx.x] = t;
-    }
+    block_partial_sum(s);
+    if (tid == 0) part[blockIdx.x] = s[0];
 }
 
-// one workgroup: the partials added in a fixed order in double (thread t takes partials t, t + 256, ...; the 256 sums are
-// folded pairwise through LDS); out = weight * sum / n
+// one workgroup: the partials added in a fixed order in double (fold_partials_double); out = weight * sum / n
 __global__ void __launch_bounds__(SISR_BLOCK) mse_finish_kernel(const float* __restrict__ part, int count, double n, float weight,
                                                                 float* __restrict__ out) {
-    __shared__ double red[SISR_BLOCK];
-    const int tid = threadIdx.x;
-    double s = 0.0;
-    for (int i = tid; i < count; i += SISR_BLOCK) s += (double)part[i];
-    red[tid] = s;
-    __syncthreads();
-    for (int o = SISR_BLOCK / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) out[0] = (float)((double)weight * red[0] / n);
+    double s[1];
+    fold_partials_double(count, s, [&](int64_t i, double* acc) { acc[0] += (double)part[i]; });
+    if (threadIdx.x == 0) out[0] = (float)((double)weight * s[0] / n);
 }
 
 // same tiling as the forward; da / db: either may be null.  c is formed in double from the fp32 weight and the fp32 upstream
@@ -162,26 +145,18 @@ __global__ void __launch_bounds__(SISR_BLOCK) mse_bwd_kernel(const float* __rest
 __global__ void __launch_bounds__(SISR_BLOCK) bce_fwd_kernel(const float* __restrict__ p, const float* __restrict__ tv, float ts,
                                                              int64_t n, float weight, float* __restrict__ loss,
                                                              float* __restrict__ mean_p) {
-    __shared__ double red[2][SISR_BLOCK];
-    const int tid = threadIdx.x;
-    double s = 0.0, sp = 0.0;
-    for (int64_t i = tid; i < n; i += SISR_BLOCK) {
+    double s[2];          // sum of the losses, sum of p
+    fold_partials_double(n, s, [&](int64_t i, double* acc) {
         const float v = p[i], t = tv ? tv[i] : ts;
         float l1 = logf(v), l0 = log1pf(-v);
         l1 = l1 < -100.f ? -100.f : l1;        // (not fmaxf: a NaN must stay a NaN)
         l0 = l0 < -100.f ? -100.f : l0;
-        s += (double)(-(t * l1 + (1.f - t) * l0));
-        sp += (double)v;
-    }
-    red[0][tid] = s; red[1][tid] = sp;
-    __syncthreads();
-    for (int o = SISR_BLOCK / 2; o > 0; o >>= 1) {
-        if (tid < o) { red[0][tid] += red[0][tid + o]; red[1][tid] += red[1][tid + o]; }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        if (loss) loss[0] = (float)((double)weight * red[0][0] / (double)n);
-        if (mean_p) mean_p[0] = (float)(red[1][0] / (double)n);
+        acc[0] += (double)(-(t * l1 + (1.f - t) * l0));
+        acc[1] += (double)v;
+    });
+    if (threadIdx.x == 0) {
+        if (loss) loss[0] = (float)((double)weight * s[0] / (double)n);
+        if (mean_p) mean_p[0] = (float)(s[1] / (double)n);
     }
 }
 

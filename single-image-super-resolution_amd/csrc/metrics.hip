@@ -60,7 +60,6 @@ __global__ void __launch_bounds__(SISR_BLOCK) metrics_tile_kernel(const float* _
                                                                   int do_ssim, float* __restrict__ part) {
     __shared__ float sa[MT_SH * MT_SW], sb[MT_SH * MT_SW];
     __shared__ float hm[5][MT_SH * MT_TW];
-    __shared__ float red[2][SISR_BLOCK / 64];
     const int tid = threadIdx.x;
     const int tiles = g.tiles_y * g.tiles_x, per_image = g.planes * tiles;
     const int n = blockIdx.x / per_image, r = blockIdx.x - n * per_image;
@@ -71,7 +70,8 @@ __global__ void __launch_bounds__(SISR_BLOCK) metrics_tile_kernel(const float* _
     const int own_h = ty == g.tiles_y - 1 ? MT_SH : MT_TH, own_w = tx == g.tiles_x - 1 ? MT_SW : MT_TW;
     const int64_t plane_elems = (int64_t)g.H * g.W;
     const int64_t base = ((int64_t)n * g.C + (g.luma ? 0 : plane)) * plane_elems;
-    float sq = 0.f;
+    float ss_sq[2] = {0.f, 0.f};          // sum of SSIM values, sum of squared differences
+    float &ss = ss_sq[0], &sq = ss_sq[1];
     for (int i = tid; i < MT_SH * MT_SW; i += SISR_BLOCK) {
         const int ly = i / MT_SW, lx = i - ly * MT_SW;
         const int y = y0 + ly, x = x0 + lx;
@@ -90,7 +90,6 @@ __global__ void __launch_bounds__(SISR_BLOCK) metrics_tile_kernel(const float* _
         sa[i] = va;
         sb[i] = vb;
     }
-    float ss = 0.f;
     if (do_ssim) {
         __syncthreads();
         // horizontal pass: every staged row, MT_TW window columns (lanes on consecutive columns: conflict-free LDS reads)
@@ -128,39 +127,24 @@ __global__ void __launch_bounds__(SISR_BLOCK) metrics_tile_kernel(const float* _
             }
         }
     }
-    ss = wave_sum(ss);
-    sq = wave_sum(sq);
-    if ((tid & 63) == 0) { red[0][tid >> 6] = ss; red[1][tid >> 6] = sq; }
-    __syncthreads();
+    block_partial_sum(ss_sq);
     if (tid == 0) {
-        float s0 = red[0][0], s1 = red[1][0];
-#pragma unroll
-        for (int w = 1; w < SISR_BLOCK / 64; ++w) { s0 += red[0][w]; s1 += red[1][w]; }
-        part[2 * (int64_t)blockIdx.x] = s0;
-        part[2 * (int64_t)blockIdx.x + 1] = s1;
+        part[2 * (int64_t)blockIdx.x] = ss;
+        part[2 * (int64_t)blockIdx.x + 1] = sq;
     }
 }
 
-// one workgroup per image: the image's partials added in a fixed order in double (thread t takes partials t, t + 256, ...; the
-// 256 sums are folded pairwise through LDS)
+// one workgroup per image: the image's partials added in a fixed order in double (fold_partials_double)
 __global__ void __launch_bounds__(SISR_BLOCK) metrics_finish_kernel(const float* __restrict__ part, int per_image, double n_ssim,
                                                                     double n_pix, double range2, float* __restrict__ psnr,
                                                                     float* __restrict__ ssim) {
-    __shared__ double red[2][SISR_BLOCK];
-    const int tid = threadIdx.x;
     const float* p = part + 2 * (int64_t)blockIdx.x * per_image;
-    double s0 = 0.0, s1 = 0.0;
-    for (int i = tid; i < per_image; i += SISR_BLOCK) { s0 += (double)p[2 * i]; s1 += (double)p[2 * i + 1]; }
-    red[0][tid] = s0; red[1][tid] = s1;
-    __syncthreads();
-    for (int o = SISR_BLOCK / 2; o > 0; o >>= 1) {
-        if (tid < o) { red[0][tid] += red[0][tid + o]; red[1][tid] += red[1][tid + o]; }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        if (ssim) ssim[blockIdx.x] = (float)(red[0][0] / n_ssim);
+    double s[2];
+    fold_partials_double(per_image, s, [&](int64_t i, double* acc) { acc[0] += (double)p[2 * i]; acc[1] += (double)p[2 * i + 1]; });
+    if (threadIdx.x == 0) {
+        if (ssim) ssim[blockIdx.x] = (float)(s[0] / n_ssim);
         if (psnr) {
-            const double mse = red[1][0] / n_pix;
+            const double mse = s[1] / n_pix;
             psnr[blockIdx.x] = mse > 0.0 ? (float)(10.0 * log10(range2 / mse)) : INFINITY;
         }
     }

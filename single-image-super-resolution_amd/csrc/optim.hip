@@ -6,7 +6,7 @@
 // HBM-bound: 4 reads + 3 writes of 4 bytes per parameter.  The descriptor table lives in device memory; a workgroup
 // finds its tensor by a binary search over the per-tensor first-block indices.
 //
-// Two families share the update (adam_update_block):
+// Two families share the update (AdamUpdate):
 //   host state    adam_step_kernel: lr and the bias corrections arrive as launch arguments (sisr_adam_step);
 //   device state  the step count of every tensor, the learning rate and the guards live in device memory, so the launches
 //                 below can sit inside a captured HIP graph and still advance from replay to replay:
@@ -44,91 +44,120 @@ __device__ __forceinline__ int adam_find_tensor(const Desc* __restrict__ table, 
     return lo;
 }
 
-// the update of one workgroup's ADAM_CHUNK elements of tensor t, starting at element `base`.  CLIP: g is multiplied by coef
-// before the weight decay is added (the gradient tensor itself is only read)
-template <bool CLIP>
-__device__ __forceinline__ void adam_update_block(const SisrAdamDesc& t, int64_t base, float coef, float step_size, float omb1,
-                                                  float beta2, float omb2, float eps, float wd, float inv_sqrt_bc2) {
-    if ((t.numel & 3) == 0) {
-        const int64_t n4 = t.numel >> 2;
+// THE block mapping: workgroup blockIdx.x owns ADAM_CHUNK elements of table row `row` (copied to t), starting at element `base`
+template <typename Desc> struct Chunk { int row; Desc t; int64_t base; };
+template <typename Desc> __device__ __forceinline__ Chunk<Desc> chunk_of_block(const Desc* __restrict__ table, int n) {
+    const int row = adam_find_tensor(table, n, (int64_t)blockIdx.x);
+    const Desc t = table[row];
+    return {row, t, ((int64_t)blockIdx.x - t.block_start) * ADAM_CHUNK};
+}
+
+// THE rule of the 16-byte path: whole 16-byte items only, and every tensor the kernel touches starts on a 16-byte line (a
+// parameter or a gradient may be a view at an odd element offset); everything else takes the 4-byte path
+template <typename... P>
+__device__ __forceinline__ bool chunk_vec_ok(int64_t numel, const P*... ptrs) {
+    return ((numel & 3) | ((... | reinterpret_cast<uintptr_t>(ptrs)) & 15)) == 0;
+}
+
+template <int W> using fvec = float __attribute__((ext_vector_type(W)));
+template <int W> using uvec = unsigned __attribute__((ext_vector_type(W)));
+
+// THE walk over a chunk, in items of W elements (4: the 16-byte path, 4 items per thread; 1: 16 items per thread) at stride
+// SISR_BLOCK.  Op: Item<W> = what a thread holds of one item, load<W>(i, item), apply<W>(i, item) = arithmetic and stores.  A thread
+// issues the loads of G items before the first of them is applied; G == 1 loads and applies an item under ONE bounds test (with
+// two, loads stay pending across a branch and the compiler's wait counting then waits between the 16-byte loads of the Adam step)
+template <int W, int G, typename Op>
+__device__ __forceinline__ void chunk_walk_items(int64_t numel, int64_t base, Op& op) {
+    constexpr int SHIFT = W == 4 ? 2 : 0, UNROLL = W == 4 ? 4 : 1;          // (the 4-byte path stays a loop)
+    const int64_t ni = numel >> SHIFT, i0 = (base >> SHIFT) + threadIdx.x;
+#pragma unroll UNROLL
+    for (int k = 0; k < 16 / W; k += G) {
+        typename Op::template Item<W> x[G];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int64_t i = (base >> 2) + k * SISR_BLOCK + threadIdx.x;
-            if (i < n4) {
-                f32x4 p = reinterpret_cast<const f32x4*>(t.p)[i], g = reinterpret_cast<const f32x4*>(t.g)[i];
-                f32x4 m = reinterpret_cast<const f32x4*>(t.m)[i], v = reinterpret_cast<const f32x4*>(t.v)[i];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float gg = (CLIP ? g[j] * coef : g[j]) + wd * p[j];
-                    m[j] = m[j] + (gg - m[j]) * omb1;
-                    v[j] = v[j] * beta2 + omb2 * gg * gg;
-                    p[j] -= step_size * (m[j] / (sqrtf(v[j]) * inv_sqrt_bc2 + eps));
-                }
-                reinterpret_cast<f32x4*>(t.p)[i] = p;
-                reinterpret_cast<f32x4*>(t.m)[i] = m;
-                reinterpret_cast<f32x4*>(t.v)[i] = v;
+        for (int u = 0; u < G; ++u) {
+            const int64_t i = i0 + (k + u) * SISR_BLOCK;
+            if (i < ni) {
+                op.template load<W>(i, x[u]);
+                if (G == 1) op.template apply<W>(i, x[u]);
             }
         }
-    } else {
-        for (int k = 0; k < 16; ++k) {
-            const int64_t i = base + k * SISR_BLOCK + threadIdx.x;
-            if (i < t.numel) {
-                const float gg = (CLIP ? t.g[i] * coef : t.g[i]) + wd * t.p[i];
-                const float m = t.m[i] + (gg - t.m[i]) * omb1;
-                const float v = t.v[i] * beta2 + omb2 * gg * gg;
-                t.m[i] = m; t.v[i] = v;
-                t.p[i] -= step_size * (m / (sqrtf(v) * inv_sqrt_bc2 + eps));
-            }
+#pragma unroll
+        for (int u = 0; u < G; ++u) {
+            const int64_t i = i0 + (k + u) * SISR_BLOCK;
+            if (G > 1 && i < ni) op.template apply<W>(i, x[u]);
         }
     }
+}
+template <int G, typename Op>
+__device__ __forceinline__ void chunk_walk(bool vec, int64_t numel, int64_t base, Op& op) {
+    if (vec) chunk_walk_items<4, G>(numel, base, op); else chunk_walk_items<1, G>(numel, base, op);
+}
+
+// a * b + c * d.  Written as that sum, the compiler may fuse either product into the addition or neither, and its pick moves with
+// the code around the line (it differed between the two loops of one kernel).  A resumed run must keep its bits, so the update's
+// two such sums say which product is fused (FUSE 1: a * b, 2: c * d, 0: none; the other is rounded first): what each path always did
+template <int FUSE>
+__device__ __forceinline__ float sum_of_products(float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+    const float ab = a * b, cd = c * d;
+    return FUSE == 1 ? fmaf(a, b, cd) : FUSE == 2 ? fmaf(c, d, ab) : ab + cd;
+}
+
+// the Adam update.  CLIP: g is multiplied by coef before the weight decay is added (the gradient tensor itself is only read)
+template <bool CLIP>
+struct AdamUpdate {
+    const SisrAdamDesc& t;
+    float coef, step_size, omb1, beta2, omb2, eps, wd, inv_sqrt_bc2;
+    template <int W> struct Item { fvec<W> p, g, m, v; };
+    template <int W> __device__ __forceinline__ void load(int64_t i, Item<W>& x) const {
+        x.p = reinterpret_cast<const fvec<W>*>(t.p)[i]; x.g = reinterpret_cast<const fvec<W>*>(t.g)[i];
+        x.m = reinterpret_cast<const fvec<W>*>(t.m)[i]; x.v = reinterpret_cast<const fvec<W>*>(t.v)[i];
+    }
+    template <int W> __device__ __forceinline__ void apply(int64_t i, Item<W>& x) const {
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const float gg = CLIP ? sum_of_products<W == 4 ? 2 : 1>(x.g[j], coef, wd, x.p[j]) : x.g[j] + wd * x.p[j];
+            x.m[j] = x.m[j] + (gg - x.m[j]) * omb1;
+            x.v[j] = sum_of_products<W == 4 ? 1 : 0>(x.v[j], beta2, omb2 * gg, gg);
+            x.p[j] -= step_size * (x.m[j] / (sqrtf(x.v[j]) * inv_sqrt_bc2 + eps));
+        }
+        reinterpret_cast<fvec<W>*>(t.p)[i] = x.p; reinterpret_cast<fvec<W>*>(t.m)[i] = x.m; reinterpret_cast<fvec<W>*>(t.v)[i] = x.v;
+    }
+};
+template <bool CLIP>
+__device__ __forceinline__ void adam_update_chunk(const Chunk<SisrAdamDesc>& c, AdamUpdate<CLIP> op) {
+    chunk_walk<1>(chunk_vec_ok(c.t.numel, c.t.p, c.t.m, c.t.v, c.t.g), c.t.numel, c.base, op);          // item by item
 }
 
 __global__ void __launch_bounds__(SISR_BLOCK) adam_step_kernel(const SisrAdamDesc* __restrict__ table, int n, float step_size,
                                                                 float omb1, float beta2, float omb2, float eps, float wd,
                                                                 float inv_sqrt_bc2) {
-    const SisrAdamDesc t = table[adam_find_tensor(table, n, (int64_t)blockIdx.x)];
-    const int64_t base = ((int64_t)blockIdx.x - t.block_start) * ADAM_CHUNK;
-    adam_update_block<false>(t, base, 1.f, step_size, omb1, beta2, omb2, eps, wd, inv_sqrt_bc2);
+    const Chunk<SisrAdamDesc> c = chunk_of_block(table, n);
+    adam_update_chunk<false>(c, {c.t, 1.f, step_size, omb1, beta2, omb2, eps, wd, inv_sqrt_bc2});
 }
 
 // ---- device-state family ------------------------------------------------------------------------------------------------
 
+struct GradSumsq {
+    const float* g;
+    double s[1];
+    template <int W> struct Item { fvec<W> g; };
+    template <int W> __device__ __forceinline__ void load(int64_t i, Item<W>& x) const { x.g = reinterpret_cast<const fvec<W>*>(g)[i]; }
+    template <int W> __device__ __forceinline__ void apply(int64_t, Item<W>& x) {
+#pragma unroll
+        for (int j = 0; j < W; ++j) s[0] += (double)x.g[j] * (double)x.g[j];
+    }
+};
+
 // part[blockIdx.x] = sum of g^2 over the workgroup's chunk, squared and accumulated in double (|g| ~ 1e19 overflows an fp32
-// square; the kernel waits for HBM either way)
+// square; the kernel waits for HBM either way): per thread in item order, then block_partial_sum
 __global__ void __launch_bounds__(SISR_BLOCK) adam_sumsq_kernel(const SisrAdamDesc* __restrict__ table, int n,
                                                                  double* __restrict__ part) {
-    __shared__ double red[SISR_BLOCK / 64];
-    const SisrAdamDesc t = table[adam_find_tensor(table, n, (int64_t)blockIdx.x)];
-    const int64_t base = ((int64_t)blockIdx.x - t.block_start) * ADAM_CHUNK;
-    double s = 0.0;
-    if ((t.numel & 3) == 0) {
-        const int64_t n4 = t.numel >> 2;
-        f32x4 g[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int64_t i = (base >> 2) + k * SISR_BLOCK + threadIdx.x;
-            g[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (i < n4) g[k] = reinterpret_cast<const f32x4*>(t.g)[i];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s += (double)g[k][j] * (double)g[k][j];
-    } else {
-        for (int k = 0; k < 16; ++k) {
-            const int64_t i = base + k * SISR_BLOCK + threadIdx.x;
-            if (i < t.numel) { const double g = (double)t.g[i]; s += g * g; }
-        }
-    }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = red[0];
-#pragma unroll
-        for (int w = 1; w < SISR_BLOCK / 64; ++w) r += red[w];
-        part[blockIdx.x] = r;
-    }
+    const Chunk<SisrAdamDesc> c = chunk_of_block(table, n);
+    GradSumsq op = {c.t.g, {0.0}};
+    chunk_walk<4>(chunk_vec_ok(c.t.numel, c.t.g), c.t.numel, c.base, op);
+    block_partial_sum(op.s);
+    if (threadIdx.x == 0) part[blockIdx.x] = op.s[0];
 }
 
 // One thread per tensor, ceil(n / 256) workgroups.  With partials (n_part > 0) EVERY workgroup adds all of them in the same
@@ -141,20 +170,13 @@ __global__ void __launch_bounds__(SISR_BLOCK) adam_prepare_kernel(float* const* 
                                                                    const double* __restrict__ part, int64_t n_part, double max_norm,
                                                                    int skip_nonfinite, int write_ctrl, float* __restrict__ ctrl,
                                                                    float* __restrict__ consts) {
-    __shared__ double red[SISR_BLOCK];
     const int tid = threadIdx.x;
     float norm_f = 0.f, coef = 1.f;
     int skip = 0;
     if (n_part > 0) {
-        double s = 0.0;
-        for (int64_t i = tid; i < n_part; i += SISR_BLOCK) s += part[i];
-        red[tid] = s;
-        __syncthreads();
-        for (int o = SISR_BLOCK / 2; o > 0; o >>= 1) {
-            if (tid < o) red[tid] += red[tid + o];
-            __syncthreads();
-        }
-        const double norm = sqrt(red[0]);
+        double s[1];
+        fold_partials_double(n_part, s, [&](int64_t i, double* a) { a[0] += part[i]; });
+        const double norm = sqrt(s[0]);
         norm_f = (float)norm;
         if (max_norm >= 0.0) {
             const double c = max_norm / (norm + 1e-6);          // torch.nn.utils.clip_grad_norm_
@@ -183,10 +205,8 @@ __global__ void __launch_bounds__(SISR_BLOCK) adam_step_dev_kernel(const SisrAda
                                                                     const float* __restrict__ consts, const float* __restrict__ ctrl,
                                                                     float omb1, float beta2, float omb2, float eps, float wd) {
     if (reinterpret_cast<const int*>(ctrl)[ADAM_CTRL_SKIP]) return;          // before any store
-    const int ti = adam_find_tensor(table, n, (int64_t)blockIdx.x);
-    const SisrAdamDesc t = table[ti];
-    const int64_t base = ((int64_t)blockIdx.x - t.block_start) * ADAM_CHUNK;
-    adam_update_block<true>(t, base, ctrl[ADAM_CTRL_COEF], consts[2 * ti], omb1, beta2, omb2, eps, wd, consts[2 * ti + 1]);
+    const Chunk<SisrAdamDesc> c = chunk_of_block(table, n);
+    adam_update_chunk<true>(c, {c.t, ctrl[ADAM_CTRL_COEF], consts[2 * c.row], omb1, beta2, omb2, eps, wd, consts[2 * c.row + 1]});
 }
 
 extern "C" int64_t sisr_adam_blocks(int64_t numel) { return numel <= 0 ? 0 : (numel + ADAM_CHUNK - 1) / ADAM_CHUNK; }
@@ -247,13 +267,6 @@ extern "C" int sisr_adam_step_dev(const SisrAdamDesc* table_dev, int32_t n, int6
 #define EMA_CTRL_OMD 0                        // fp32  1 - decay of this update
 #define EMA_CTRL_ACTIVE 1                     // int32 0: the followed optimizer skipped its step, the update stores nothing
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// 16-byte accesses need every element of both tensors on a 16-byte line: a parameter may be a view at an odd element offset
-__device__ __forceinline__ bool ema_vec_ok(const SisrEmaDesc& t) {
-    return (t.numel & 3) == 0 && ((reinterpret_cast<uintptr_t>(t.ema) | reinterpret_cast<uintptr_t>(t.src)) & 15) == 0;
-}
-
 // an element whose live value equals its average keeps its bits (e + omd * 0 would turn a -0 into +0)
 __device__ __forceinline__ float ema_value(float e, float p, float omd) {
     const float d = p - e;
@@ -275,83 +288,49 @@ __global__ void __launch_bounds__(64) ema_prepare_kernel(int* __restrict__ count
     *count = n + 1;
 }
 
-// one workgroup per ADAM_CHUNK elements; all loads of a thread are issued before its first store
+// the three per-item bodies: average, bit copy live -> shadow, bit exchange
+struct EmaAverage {
+    const SisrEmaDesc& t;
+    float omd;
+    template <int W> struct Item { fvec<W> e, p; };
+    template <int W> __device__ __forceinline__ void load(int64_t i, Item<W>& x) const {
+        x.e = reinterpret_cast<const fvec<W>*>(t.ema)[i]; x.p = reinterpret_cast<const fvec<W>*>(t.src)[i];
+    }
+    template <int W> __device__ __forceinline__ void apply(int64_t i, Item<W>& x) const {
+#pragma unroll
+        for (int j = 0; j < W; ++j) x.e[j] = ema_value(x.e[j], x.p[j], omd);
+        reinterpret_cast<fvec<W>*>(t.ema)[i] = x.e;
+    }
+};
+template <bool SWAP>
+struct EmaBits {
+    const SisrEmaDesc& t;
+    template <int W> struct Item { uvec<W> e, p; };
+    template <int W> __device__ __forceinline__ void load(int64_t i, Item<W>& x) const {
+        if (SWAP) x.e = reinterpret_cast<const uvec<W>*>(t.ema)[i];
+        x.p = reinterpret_cast<const uvec<W>*>(t.src)[i];
+    }
+    template <int W> __device__ __forceinline__ void apply(int64_t i, Item<W>& x) const {
+        reinterpret_cast<uvec<W>*>(t.ema)[i] = x.p;
+        if (SWAP) reinterpret_cast<uvec<W>*>(t.src)[i] = x.e;
+    }
+};
+// all loads of a thread's four 16-byte items are issued before its first store
+template <typename Op>
+__device__ __forceinline__ void ema_walk(const Chunk<SisrEmaDesc>& c, Op op) {
+    chunk_walk<4>(chunk_vec_ok(c.t.numel, c.t.ema, c.t.src), c.t.numel, c.base, op);
+}
+
 __global__ void __launch_bounds__(SISR_BLOCK) ema_update_kernel(const SisrEmaDesc* __restrict__ table, int n,
                                                                  const float* __restrict__ ctrl) {
     if (reinterpret_cast<const int*>(ctrl)[EMA_CTRL_ACTIVE] == 0) return;          // before any store
-    const float omd = ctrl[EMA_CTRL_OMD];
-    const SisrEmaDesc t = table[adam_find_tensor(table, n, (int64_t)blockIdx.x)];
-    const int64_t base = ((int64_t)blockIdx.x - t.block_start) * ADAM_CHUNK;
-    if (ema_vec_ok(t)) {
-        const int64_t n4 = t.numel >> 2;
-        const int64_t i0 = (base >> 2) + threadIdx.x;
-        if (t.mode == 0) {
-            f32x4 e[4], p[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int64_t i = i0 + k * SISR_BLOCK;
-                if (i < n4) { e[k] = reinterpret_cast<const f32x4*>(t.ema)[i]; p[k] = reinterpret_cast<const f32x4*>(t.src)[i]; }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int64_t i = i0 + k * SISR_BLOCK;
-                if (i < n4) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) e[k][j] = ema_value(e[k][j], p[k][j], omd);
-                    reinterpret_cast<f32x4*>(t.ema)[i] = e[k];
-                }
-            }
-        } else {
-            u32x4 p[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int64_t i = i0 + k * SISR_BLOCK;
-                if (i < n4) p[k] = reinterpret_cast<const u32x4*>(t.src)[i];
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int64_t i = i0 + k * SISR_BLOCK;
-                if (i < n4) reinterpret_cast<u32x4*>(t.ema)[i] = p[k];
-            }
-        }
-    } else if (t.mode == 0) {
-        for (int k = 0; k < 16; ++k) {
-            const int64_t i = base + k * SISR_BLOCK + threadIdx.x;
-            if (i < t.numel) t.ema[i] = ema_value(t.ema[i], t.src[i], omd);
-        }
-    } else {
-        for (int k = 0; k < 16; ++k) {
-            const int64_t i = base + k * SISR_BLOCK + threadIdx.x;
-            if (i < t.numel) reinterpret_cast<unsigned*>(t.ema)[i] = reinterpret_cast<const unsigned*>(t.src)[i];
-        }
-    }
+    const Chunk<SisrEmaDesc> c = chunk_of_block(table, n);
+    if (c.t.mode == 0) ema_walk(c, EmaAverage{c.t, ctrl[EMA_CTRL_OMD]}); else ema_walk(c, EmaBits<false>{c.t});
 }
 
 __global__ void __launch_bounds__(SISR_BLOCK) ema_swap_kernel(const SisrEmaDesc* __restrict__ table, int n) {
-    const SisrEmaDesc t = table[adam_find_tensor(table, n, (int64_t)blockIdx.x)];
-    const int64_t base = ((int64_t)blockIdx.x - t.block_start) * ADAM_CHUNK;
-    if (ema_vec_ok(t)) {
-        const int64_t n4 = t.numel >> 2;
-        const int64_t i0 = (base >> 2) + threadIdx.x;
-        u32x4 e[4], p[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int64_t i = i0 + k * SISR_BLOCK;
-            if (i < n4) { e[k] = reinterpret_cast<const u32x4*>(t.ema)[i]; p[k] = reinterpret_cast<const u32x4*>(t.src)[i]; }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int64_t i = i0 + k * SISR_BLOCK;
-            if (i < n4) { reinterpret_cast<u32x4*>(t.ema)[i] = p[k]; reinterpret_cast<u32x4*>(t.src)[i] = e[k]; }
-        }
-    } else {
-        unsigned* ema = reinterpret_cast<unsigned*>(t.ema);
-        unsigned* src = reinterpret_cast<unsigned*>(t.src);
-        for (int k = 0; k < 16; ++k) {
-            const int64_t i = base + k * SISR_BLOCK + threadIdx.x;
-            if (i < t.numel) { const unsigned e = ema[i], p = src[i]; ema[i] = p; src[i] = e; }
-        }
-    }
+    const Chunk<SisrEmaDesc> c = chunk_of_block(table, n);
+    ema_walk(c, EmaBits<true>{c.t});
 }
 
 extern "C" int sisr_ema_prepare(int32_t* count_dev, double decay, double warmup, const int32_t* skip_flag_dev, float* ctrl,

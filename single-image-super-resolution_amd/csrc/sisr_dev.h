@@ -123,6 +123,52 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
     return t;
 }
 
+// a workgroup's partial sums for SISR_BLOCK threads, N values at a time: wave_sum, one LDS slot per wave, thread 0 adds the waves
+// in index order.  Result in v, valid in thread 0 only
+template <typename T, int N>
+__device__ __forceinline__ void block_partial_sum(T (&v)[N]) {
+    __shared__ T red[N][SISR_BLOCK / 64];
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = wave_sum(v[j]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) red[j][threadIdx.x >> 6] = v[j];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            v[j] = red[j][0];
+#pragma unroll
+            for (int w = 1; w < SISR_BLOCK / 64; ++w) v[j] += red[j][w];
+        }
+    }
+}
+
+// fixed-order sums in double over `count` terms by ONE workgroup of SISR_BLOCK threads, N sums at a time: thread t takes terms
+// t, t + 256, ... (term(i, a) adds term i to a[0 .. N)), then the 256 sums are folded pairwise through LDS (halving).  Result in
+// s, valid in all threads
+template <int N, typename Term>
+__device__ __forceinline__ void fold_partials_double(int64_t count, double (&s)[N], Term term) {
+    __shared__ double red[N][SISR_BLOCK];
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < N; ++j) s[j] = 0.0;
+    for (int64_t i = tid; i < count; i += SISR_BLOCK) term(i, s);
+#pragma unroll
+    for (int j = 0; j < N; ++j) red[j][tid] = s[j];
+    __syncthreads();
+    for (int o = SISR_BLOCK / 2; o > 0; o >>= 1) {
+        if (tid < o) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) red[j][tid] += red[j][tid + o];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) s[j] = red[j][0];
+}
+
 // raw buffer resource over [p, p + bytes): loads / stores take 32-bit byte offsets, out-of-range ones are dropped
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t sisr_rsrc(const void* p, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);

@@ -92,13 +92,11 @@ class WeightEMA:
 
     def _build_table(self):
         """(re)writes the table IN PLACE: a captured launch holds its address"""
-        lib = L.lib()
         rows = [r for r in self._fused if r[1].numel() > 0]
         table = (L.EmaDesc * len(rows))()
-        blocks = 0
         for d, (_, live, shadow, mode) in zip(table, rows):
-            d.ema, d.src, d.numel, d.block_start, d.mode = shadow.data_ptr(), live.data_ptr(), live.numel(), blocks, mode
-            blocks += lib.sisr_adam_blocks(live.numel())
+            d.ema, d.src, d.numel, d.mode = shadow.data_ptr(), live.data_ptr(), live.numel(), mode
+        blocks = E._fill_block_starts(table)
         staged = E._table_to_device(table, self._count.device)
         if self._table is None:
             self._table = staged

@@ -552,6 +552,16 @@ def table_bytes_staged():
     return _TABLE_BYTES[0]
 
 
+def _fill_block_starts(table):
+    """The block mapping of the multi-tensor launches (csrc/optim.hip) for a ctypes table (AdamDesc / EmaDesc rows) whose
+    ``numel`` fields are set: every row's ``block_start`` = the blocks of the rows before it.  Returns the total."""
+    lib, blocks = L.lib(), 0
+    for row in table:
+        row.block_start = blocks
+        blocks += lib.sisr_adam_blocks(row.numel)
+    return blocks
+
+
 def _table_to_device(table, dev):
     """Descriptor table -> device without a host synchronisation: staged in pinned memory and copied
     asynchronously on the current stream.  Eager mode uses a 4 MB pinned ring in two halves: when a half is full an

@@ -126,7 +126,7 @@ class Adam(torch.optim.Adam):
                                'a stream capture -- run a warm-up step first (graph.GraphedStep does)')
         lib = L.lib()
         params = [p for g in self.param_groups for p in g['params']]
-        blocks = sum(lib.sisr_adam_blocks(p.numel()) for p in params)
+        blocks = E._fill_block_starts((L.AdamDesc * len(params))(*[L.AdamDesc(numel=p.numel()) for p in params]))
         ctrl = torch.zeros(4, dtype=torch.float32, device=device)
         self._dev = {
             'index': {p: i for i, p in enumerate(params)},
@@ -191,6 +191,37 @@ class Adam(torch.optim.Adam):
         return self._dev[key]
 
     # ---- steps ----------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _refuse(p):
+        E.require_gpu_tensor(p, 'fused Adam parameter')
+        if p.grad.is_sparse or p.grad.dtype != torch.float32 or not p.is_contiguous():
+            raise RuntimeError('fused Adam: dense contiguous fp32 parameters and gradients expected')
+
+    def _table(self, gi, plist):
+        """(device table, total blocks, gradients) of group gi's launch over plist.  The staged buffer holds the descriptor table
+        and, in capturable mode, the step-count pointers behind it (48 n bytes in: 8-byte aligned).  It holds raw pointers of
+        parameters, gradients, both moment tensors and step counts: all of them are the cache key (load_state_dict() replaces
+        the moments of the host-state optimizer at unchanged parameter / gradient addresses).  The returned gradients keep
+        contiguous copies alive until the launch is issued."""
+        grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in plist]
+        states = [self.state[p] for p in plist]
+        rows = [(p.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(), g.data_ptr(), p.numel())          # AdamDesc
+                for p, st, g in zip(plist, states, grads)]
+        steps = [st['step'].data_ptr() for st in states] if self._capturable else []
+        key = (rows, steps)
+        capturing = self._capturable and torch.cuda.is_current_stream_capturing()
+        cached = None if capturing else self._tables.get(gi)
+        if cached is None or cached[0] != key:
+            table = (L.AdamDesc * len(rows))(*[L.AdamDesc(*r) for r in rows])
+            blocks = E._fill_block_starts(table)
+            staged = E._table_to_device(bytes(table) + bytes((C.c_void_p * len(steps))(*steps)), plist[0].device)
+            cached = (key, staged, blocks)
+            if capturing:
+                self._captured.append(cached)          # the graph re-reads the staged table on every replay
+            else:
+                self._tables[gi] = cached
+        return cached[1], cached[2], grads
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -207,9 +238,7 @@ class Adam(torch.optim.Adam):
             for p in group['params']:
                 if p.grad is None:
                     continue
-                E.require_gpu_tensor(p, 'fused Adam parameter')
-                if p.grad.is_sparse or p.grad.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError('fused Adam: dense contiguous fp32 parameters and gradients expected')
+                self._refuse(p)
                 st = self.state[p]
                 if len(st) == 0:          # same state layout as torch.optim.Adam
                     st['step'] = torch.tensor(0.0, dtype=torch.float32)
@@ -219,24 +248,8 @@ class Adam(torch.optim.Adam):
                 by_step.setdefault(int(st['step'].item()), []).append(p)     # 'step' lives on the host: no sync
             beta1, beta2 = group['betas']
             for t, plist in by_step.items():
-                grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in plist]
-                # the table holds raw pointers of parameters, gradients AND both moment tensors: load_state_dict()
-                # replaces the moments (same parameter / gradient addresses), so they are part of the key
-                key = (gi, tuple(p.data_ptr() for p in plist), tuple(g.data_ptr() for g in grads),
-                       tuple(self.state[p]['exp_avg'].data_ptr() for p in plist),
-                       tuple(self.state[p]['exp_avg_sq'].data_ptr() for p in plist))
-                cached = self._tables.get(gi)
-                if cached is None or cached[0] != key:
-                    table = (L.AdamDesc * len(plist))()
-                    blocks = 0
-                    for d, p, g in zip(table, plist, grads):
-                        st = self.state[p]
-                        d.p, d.m, d.v, d.g = p.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(), g.data_ptr()
-                        d.numel, d.block_start = p.numel(), blocks
-                        blocks += lib.sisr_adam_blocks(p.numel())
-                    cached = (key, E._table_to_device(table, plist[0].device), blocks)
-                    self._tables[gi] = cached
-                L.check(lib.sisr_adam_step(cached[1].data_ptr(), len(plist), cached[2], float(group['lr']), beta1, beta2,
+                table, blocks, grads = self._table(gi, plist)
+                L.check(lib.sisr_adam_step(table.data_ptr(), len(plist), blocks, float(group['lr']), beta1, beta2,
                                            group['eps'], group['weight_decay'], 1.0 - math.pow(beta1, t),
                                            1.0 - math.pow(beta2, t), E._stream()), 'sisr_adam_step')
                 del grads
@@ -251,9 +264,7 @@ class Adam(torch.optim.Adam):
         for group in self.param_groups:      # refusals first: nothing below may look for a device on behalf of a CPU tensor
             for p in group['params']:
                 if p.grad is not None:
-                    E.require_gpu_tensor(p, 'fused Adam parameter')
-                    if p.grad.is_sparse or p.grad.dtype != torch.float32 or not p.is_contiguous():
-                        raise RuntimeError('fused Adam: dense contiguous fp32 parameters and gradients expected')
+                    self._refuse(p)
         capturing = torch.cuda.is_current_stream_capturing()
         work = []
         for gi, group in enumerate(self.param_groups):
@@ -267,29 +278,7 @@ class Adam(torch.optim.Adam):
                 if len(st) == 0:          # torch.optim.Adam(capturable=True)'s state layout
                     m, v = self._moments_of(p)
                     st['step'], st['exp_avg'], st['exp_avg_sq'] = d['steps'][d['index'][p]], m, v
-            grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in plist]
-            key = (tuple(p.data_ptr() for p in plist), tuple(g.data_ptr() for g in grads),
-                   tuple(self.state[p]['exp_avg'].data_ptr() for p in plist),
-                   tuple(self.state[p]['exp_avg_sq'].data_ptr() for p in plist),
-                   tuple(self.state[p]['step'].data_ptr() for p in plist))
-            cached = None if capturing else self._tables.get(gi)
-            if cached is None or cached[0] != key:
-                table = (L.AdamDesc * len(plist))()
-                steps = (C.c_void_p * len(plist))()
-                blocks = 0
-                for i, (t, p, g) in enumerate(zip(table, plist, grads)):
-                    st = self.state[p]
-                    t.p, t.m, t.v, t.g = p.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(), g.data_ptr()
-                    t.numel, t.block_start = p.numel(), blocks
-                    steps[i] = st['step'].data_ptr()
-                    blocks += lib.sisr_adam_blocks(p.numel())
-                # one staged buffer: the descriptor table, then the step-count pointers (48 n bytes in: 8-byte aligned)
-                cached = (key, E._table_to_device(bytes(table) + bytes(steps), plist[0].device), blocks)
-                if capturing:
-                    self._captured.append(cached)
-                else:
-                    self._tables[gi] = cached
-            work.append((gi, group, plist, grads, cached))
+            work.append((gi, group, plist) + self._table(gi, plist))
         if not work:
             return
         E.invalidate_weight_caches()      # the step kernel rewrites parameters behind torch's version counters
@@ -298,19 +287,19 @@ class Adam(torch.optim.Adam):
         d, stream = self._dev, E._stream()
         n_part = 0
         if guard:
-            for gi, group, plist, grads, cached in work:
-                L.check(lib.sisr_adam_grad_sumsq(cached[1].data_ptr(), len(plist), cached[2],
+            for gi, group, plist, table, blocks, grads in work:
+                L.check(lib.sisr_adam_grad_sumsq(table.data_ptr(), len(plist), blocks,
                                                  d['partials'].data_ptr() + 8 * n_part, stream), 'sisr_adam_grad_sumsq')
-                n_part += cached[2]
+                n_part += blocks
         max_norm = -1.0 if self._max_grad_norm is None else self._max_grad_norm
-        for k, (gi, group, plist, grads, cached) in enumerate(work):
+        for k, (gi, group, plist, table, blocks, grads) in enumerate(work):
             lr, lr_f64 = self._lr_scalar(gi, group, plist[0].device)
             beta1, beta2 = group['betas']
-            L.check(lib.sisr_adam_prepare(cached[1].data_ptr() + C.sizeof(L.AdamDesc) * len(plist), len(plist), lr.data_ptr(),
+            L.check(lib.sisr_adam_prepare(table.data_ptr() + C.sizeof(L.AdamDesc) * len(plist), len(plist), lr.data_ptr(),
                                           int(lr_f64), beta1, beta2, d['partials'].data_ptr() if n_part else None, n_part, max_norm,
                                           int(self._skip_nonfinite), int(k == 0), d['ctrl'].data_ptr(), d['consts'][gi].data_ptr(),
                                           stream), 'sisr_adam_prepare')
-        for gi, group, plist, grads, cached in work:
+        for gi, group, plist, table, blocks, grads in work:
             beta1, beta2 = group['betas']
-            L.check(lib.sisr_adam_step_dev(cached[1].data_ptr(), len(plist), cached[2], d['consts'][gi].data_ptr(), d['ctrl'].data_ptr(),
+            L.check(lib.sisr_adam_step_dev(table.data_ptr(), len(plist), blocks, d['consts'][gi].data_ptr(), d['ctrl'].data_ptr(),
                                            beta1, beta2, group['eps'], group['weight_decay'], stream), 'sisr_adam_step_dev')

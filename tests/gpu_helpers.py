@@ -67,6 +67,37 @@ class Buf:
         return self.body.cpu()
 
 
+class OffsetViews:
+    """Five parameters for the multi-tensor launches (test_gpu_optim.py, test_gpu_adam_capturable.py).  Two of them and one
+    gradient are views ONE element into their storage, 4-byte aligned and contiguous: 1024 elements; 4100 elements (one chunk of
+    the block mapping plus four: a second workgroup starts inside the misaligned tensor); an aligned 4096 whose GRADIENT is the
+    view; aligned controls of 4096 and 35.  Two sets from one seed hold the same values at the same offsets."""
+
+    def __init__(self, seed):
+        gen = torch.Generator().manual_seed(seed)
+        rand = lambda n: (torch.rand(n, generator=gen) - 0.5).cuda()          # noqa: E731
+        self.stores = [rand(1026), rand(4102), rand(4098)]                     # the last one: the gradient's
+        self.params = [torch.nn.Parameter(s[1:-1]) for s in self.stores[:2]] + [torch.nn.Parameter(rand(n)) for n in (4096, 4096, 35)]
+        self.grad_view = self.stores[2][1:-1]
+        for t in self.params[:2] + [self.grad_view]:
+            assert t.data_ptr() % 16 == 4 and t.is_contiguous()
+        for t in self.params[2:]:
+            assert t.data_ptr() % 16 == 0
+        self.edges = self._edges()
+
+    def _edges(self):
+        return [_bits(s[[0, -1]]) for s in self.stores]
+
+    def set_grads(self, gen, scale=1.0):
+        for k, p in enumerate(self.params):
+            g = ((torch.rand(p.shape, generator=gen) - 0.5) * scale).cuda()
+            p.grad = self.grad_view.copy_(g) if k == 2 else g
+
+    def edges_intact(self):
+        """the storage element in front of each view and the one behind it kept their bits"""
+        return all(torch.equal(a, b) for a, b in zip(self.edges, self._edges()))
+
+
 def run2(call, outs):
     """launch twice from the same pre-fill: status 0, guards intact, identical bits; leaves the second run's results in place"""
     first = None

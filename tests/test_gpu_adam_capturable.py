@@ -14,7 +14,7 @@ import copy
 import pytest
 import torch
 
-from gpu_helpers import maxrel, pkg
+from gpu_helpers import OffsetViews, maxrel, pkg
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-6
@@ -159,6 +159,40 @@ def test_global_norm_and_clipping_match_torch_adam_on_fp64_scaled_gradients(fact
     first = oa.grad_norm.clone()
     oa.step()                                                                   # same gradients again: the same bits
     assert torch.equal(oa.grad_norm, first)
+    assert int(oa.skipped_steps) == 0
+
+
+def test_capturable_adam_on_offset_views_matches_torch_adam_and_keeps_their_neighbours():
+    """parameters and a gradient that are only 4-byte aligned (gpu_helpers.OffsetViews) take the 4-byte path of the step kernel"""
+    a, b = OffsetViews(6), OffsetViews(6)
+    oa, ob = pkg('optim').Adam(a.params, lr=1e-3, weight_decay=0.01, capturable=True), torch.optim.Adam(b.params, lr=1e-3, weight_decay=0.01)
+    ga, gb = torch.Generator().manual_seed(8), torch.Generator().manual_seed(8)
+    for it in range(3):
+        a.set_grads(ga, 10.0 ** (it - 1)); b.set_grads(gb, 10.0 ** (it - 1))
+        oa.step(); ob.step()
+    _assert_same_state(oa, a.params, ob, b.params)
+    assert a.edges_intact()
+
+
+def test_clipped_adam_on_offset_views_matches_torch_adam_on_fp64_scaled_gradients():
+    """max_grad_norm=1.0: the sum-of-squares kernel reads the offset gradient (and the gradients of the offset parameters) too; the
+    comparison and the bounds of test_global_norm_and_clipping_match_torch_adam_on_fp64_scaled_gradients"""
+    a, b = OffsetViews(6), OffsetViews(6)
+    oa, ob = pkg('optim').Adam(a.params, lr=1e-3, weight_decay=0.01, max_grad_norm=1.0), torch.optim.Adam(b.params, lr=1e-3, weight_decay=0.01)
+    ga, gb = torch.Generator().manual_seed(8), torch.Generator().manual_seed(8)
+    for it in range(3):
+        a.set_grads(ga, 10.0 ** (it - 1)); b.set_grads(gb, 10.0 ** (it - 1))
+        norm = _norm64([p.grad for p in a.params])
+        coef = min(1.0, 1.0 / (norm + 1e-6))
+        assert coef < 1.0
+        for q in b.params:
+            q.grad = (q.grad.double() * coef).float()
+        kept = a.grad_view.clone()
+        oa.step(); ob.step()
+        assert abs(float(oa.grad_norm) - norm) <= 1e-6 * norm
+        assert torch.equal(a.grad_view, kept)                                   # the gradients are only read
+    _assert_same_state(oa, a.params, ob, b.params, tol_p=1e-6, tol_m=2e-6)
+    assert a.edges_intact()
     assert int(oa.skipped_steps) == 0
 
 

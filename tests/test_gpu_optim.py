@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_helpers import maxrel, pkg
+from gpu_helpers import OffsetViews, maxrel, pkg
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-6
@@ -102,6 +102,21 @@ def test_fused_adam_load_state_dict_with_static_gradient_tensors():
         assert maxrel(p, q) < TOL
         assert maxrel(oa.state[p]['exp_avg'], ob.state[q]['exp_avg']) < TOL
         assert maxrel(oa.state[p]['exp_avg_sq'], ob.state[q]['exp_avg_sq']) < TOL
+
+
+def test_fused_adam_on_offset_views_matches_torch_adam_and_keeps_their_neighbours():
+    """parameters and a gradient that are only 4-byte aligned (gpu_helpers.OffsetViews) take the 4-byte path of the step kernel"""
+    a, b = OffsetViews(6), OffsetViews(6)
+    oa, ob = pkg('optim').Adam(a.params, lr=1e-3, weight_decay=0.01), torch.optim.Adam(b.params, lr=1e-3, weight_decay=0.01)
+    ga, gb = torch.Generator().manual_seed(8), torch.Generator().manual_seed(8)
+    for it in range(3):
+        a.set_grads(ga, 10.0 ** (it - 1)); b.set_grads(gb, 10.0 ** (it - 1))
+        oa.step(); ob.step()
+    for k, (p, q) in enumerate(zip(a.params, b.params)):
+        assert maxrel(p, q) < TOL, k
+        assert maxrel(oa.state[p]['exp_avg'], ob.state[q]['exp_avg']) < TOL, k
+        assert maxrel(oa.state[p]['exp_avg_sq'], ob.state[q]['exp_avg_sq']) < TOL, k
+    assert a.edges_intact()
 
 
 def test_fused_adam_refuses_cpu_parameters():
