@@ -733,6 +733,49 @@ int sisr_degrade_fwd(const float *x, const float *kernels, const float *noise_si
 int sisr_degrade_bwd(const float *dy, const float *y_saved, const float *kernels, float *dx, int32_t N, int32_t C, int32_t H,
                      int32_t W, int32_t K, int32_t h, int32_t w, void *stream);
 
+/* ---- differentiable JPEG round trip: y = J(x), x and y [N][C][H][W] fp32, C in {1, 3}, any H, W >= 1;
+ *      tables [N][2][64] fp32 (luma, chroma; row-major 8 x 8, entries > 0).  All arithmetic of the forward in fp32:
+ *         1. p = (x + 1) 127.5 -- no rounding to 8 bits, no clamp of the input
+ *         2. C = 3: JFIF YCbCr   Y = .299 R + .587 G + .114 B   Cb = -.168735892 R - .331264108 G + .5 B + 128
+ *                                Cr = .5 R - .418687589 G - .081312411 B + 128;      C = 1: the plane is Y
+ *         3. pad on the right and at the bottom by edge replication to a multiple of the MCU: 8 x 8 pixels for SISR_JPEG_444 and
+ *            for C = 1, 16 x 16 for SISR_JPEG_420
+ *         4. SISR_JPEG_420: each chroma plane becomes the mean of its 2 x 2 pixels
+ *         5. per 8 x 8 block: subtract 128, c = D b D^T with the orthonormal DCT-II matrix D[k][n] = a_k cos((2n + 1) k pi / 16)
+ *         6. u = c / T with the sample's table (luma: tables[n][0], chroma: tables[n][1]), c^ = rintf(u) T
+ *         7. b^ = D^T c^ D, add 128; SISR_JPEG_420: every chroma value is replicated 2 x 2
+ *         8. R = Y + 1.402 (Cr - 128)   G = Y - .344136286 (Cb - 128) - .714136286 (Cr - 128)   B = Y + 1.772 (Cb - 128)
+ *            (the inverse of the matrix of step 2, written out to fp32)
+ *         9. with `clamp`: clamp to [0, 255];  crop to H x W;  y = p^ / 127.5 - 1
+ *      (the +128 of Cb / Cr and the -128 of step 5 cancel and are not executed).
+ *      Tables: libjpeg's, in integer arithmetic, from an integer quality q in [1, 100]: s = q < 50 ? 5000 / q : 200 - 2 q,
+ *      T[i] = clamp((base[i] s + 50) / 100, 1, 255), base = the two Annex K tables in row-major order.
+ *      Quality of sample b at step t: Philox4x32-10 keyed by the seed, counter {t low, t high, b, 0xFE030000 | rank},
+ *      u0 = ((r0 >> 8) + 0.5) 2^-24 in fp32 as above, q = min(qlo + (int)((qhi - qlo + 1) u0), qhi).
+ *      Every entry point returns SISR_E_BADARG before any HIP call for null pointers, sizes < 1, C outside {1, 3}, quality bounds
+ *      outside 1..100 or qlo > qhi, rank outside [0, 65536), unknown subsampling or grad codes; SISR_E_TOOBIG for N or Hp / 16
+ *      above 65535. ------------------------------------------------------------------------------------------------------------ */
+enum { SISR_JPEG_444 = 0, SISR_JPEG_420 = 1 };              /* subsampling (420 with C = 1 is 444) */
+enum { SISR_JPEG_GRAD_STE = 0, SISR_JPEG_GRAD_CUBIC = 1 };  /* surrogate derivative of the rounding */
+/* One workgroup: t = *drawn_step_dev is READ and not advanced (the launch shares the step sisr_degrade_draw stored there);
+ * quality_dev [B] int32, tables_dev [B][2][64]. */
+int sisr_jpeg_tables(const int64_t *drawn_step_dev, uint64_t seed, int32_t rank, int32_t B, int32_t qlo, int32_t qhi,
+                     int32_t *quality_dev, float *tables_dev, void *stream);
+/* HOST: the same arithmetic (one __host__ __device__ text) for step t >= 0 into host memory, no GPU involved. */
+int sisr_jpeg_tables_host(int64_t t, uint64_t seed, int32_t rank, int32_t B, int32_t qlo, int32_t qhi, int32_t *quality_host,
+                          float *tables_host);
+/* One launch: one workgroup per 16 x 64 pixel tile and sample; all planes of the tile pass through LDS, nothing intermediate
+ * touches HBM. */
+int sisr_jpeg_fwd(const float *x, const float *tables, float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t subsampling,
+                  int32_t clamp, void *stream);
+/* dx = J^T dy: every linear stage transposed (the pad's transpose folds the padded rows / columns onto row H - 1 / column W - 1),
+ * the clamp's mask [-1 < y_saved < 1] (NULL: no mask), the rounding's surrogate derivative s(u) per coefficient: SISR_JPEG_GRAD_STE
+ * s = 1; SISR_JPEG_GRAD_CUBIC s = 3 (u - rint u)^2 with u recomputed from x_saved and tables (both may be NULL under STE) in DOUBLE
+ * (u - rint u cancels: fp32 leaves s to 1e-4; s is continuous across a tie, so the forward's fp32 decisions do not matter).  No
+ * gradient for the tables.  Gather form, fixed order, no atomics. */
+int sisr_jpeg_bwd(const float *dy, const float *y_saved, const float *x_saved, const float *tables, float *dx, int32_t N, int32_t C,
+                  int32_t H, int32_t W, int32_t subsampling, int32_t grad, void *stream);
+
 /* ---- whole-image super-resolution in tiles: an image of any size is cut into overlapping windows of one
  *      shape, the generator runs over them as a batch and the SR tiles are stitched.  The table rows are sisr_patch_gather's
  *      (index, y0, x0, ops); tiles are numbered row-major over the outer product of the two axis plans. ------------------------- */

@@ -16,6 +16,8 @@ PRO_NONE, PRO_ACT, PRO_AFFINE_ACT, PRO_BNBWD, PRO_BNACT_BWD, PRO_ACT_BWD, PRO_TA
 X_NHWC, X_NCHW, X_UNSHUFFLE2 = range(3)
 Y_NHWC, Y_NCHW, Y_SHUFFLE2 = range(3)
 EPI_NONE, EPI_TANH = range(2)
+JPEG_444, JPEG_420 = range(2)                # subsampling codes of sisr_jpeg_fwd / sisr_jpeg_bwd
+JPEG_GRAD_STE, JPEG_GRAD_CUBIC = range(2)
 ROUTE_GENERIC, ROUTE_DEEP, ROUTE_TOIMAGE, ROUTE_TRUNK, ROUTE_THIN = range(5)      # enum SisrRoute: what the sisr_*_route calls answer
 
 _f = C.c_void_p      # device pointers travel as void*
@@ -226,6 +228,10 @@ _SIGS = {
     'sisr_degrade_noise_host': [_i64, C.c_uint64, _i32, _i64, _i64, _f],
     'sisr_degrade_fwd': [_f, _f, _f, _f, C.c_uint64, _i32, _f] + [_i32] * 8 + [_f],
     'sisr_degrade_bwd': [_f, _f, _f, _f] + [_i32] * 7 + [_f],
+    'sisr_jpeg_tables': [_f, C.c_uint64, _i32, _i32, _i32, _i32, _f, _f, _f],
+    'sisr_jpeg_tables_host': [_i64, C.c_uint64, _i32, _i32, _i32, _i32, _f, _f],
+    'sisr_jpeg_fwd': [_f, _f, _f] + [_i32] * 6 + [_f],
+    'sisr_jpeg_bwd': [_f, _f, _f, _f, _f] + [_i32] * 6 + [_f],
     'sisr_tile_axis': [_i32, _i32, _i32, _f, _f, _i32],
     'sisr_tile_gather_f32': [_f, _i32, _i32, _i32, _f, _i32, _i32, _i32, _f, _f],
     'sisr_tile_stitch': [_f, _f, _f, _f, _i32, _f, _f, _i32] + [_i32] * 7 + [_f32, _i32, _f32, _f32, _f, _i32, _f],

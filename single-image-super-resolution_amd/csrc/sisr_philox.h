@@ -1,6 +1,7 @@
-// sisr_philox.h -- the counter-based random numbers of the device-side samplers (patchsrc.hip, degrade.hip): one text for host and
+// sisr_philox.h -- the counter-based random numbers of the device-side samplers (patchsrc.hip, degrade.hip, jpeg.hip): one text for host and
 // device, so every draw has a host restatement that needs no GPU.  Word 3 of a counter says whose it is: a patch-source sample
-// carries its rank (< 2^31), the epoch permutation tags >= 0xFFFFFFE7, the degradation 0xFE01xxxx / 0xFE02xxxx (degrade.hip).
+// carries its rank (< 2^31), the epoch permutation tags >= 0xFFFFFFE7, the degradation 0xFE01xxxx / 0xFE02xxxx (degrade.hip), the
+// JPEG quality 0xFE03xxxx (jpeg.hip).
 #pragma once
 #include <stdint.h>
 

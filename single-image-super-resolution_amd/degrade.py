@@ -7,6 +7,7 @@ own -- and a generator trained against bicubic alone is known to fail on images 
 >>> d = Degrader(ksize=21, sigma=(0.2, 3.0), anisotropic=True, noise=(0., 0.05), seed=1)
 >>> img_lr = d(img_hr, (48, 48))                       # draw + forward: two launches, differentiable in img_hr, capturable
 >>> sisr.install(degradation=d)                        # the reference's utils.lr_from_hr now draws
+>>> d = Degrader(noise=(0., 0.05), jpeg=(30, 95))      # ... and ends with a JPEG round trip at a random quality (jpeg.py)
 
 ``degrade`` is the operator with the kernels given; ``gaussian_kernels`` builds fixed ones; ``expected_params`` / ``expected_noise``
 restate a step's draws on the host (no GPU) for audits and tests.
@@ -151,6 +152,11 @@ class Degrader:
                      for both axes); its orientation is uniform in [0, pi).  The kernel is normalised to sum 1.
     ``noise``        (lo, hi): the noise standard deviation is uniform in it; (0, 0) switches the noise off altogether.
     ``seed, rank``   key and stream of the Philox4x32-10 draws (rank < 65536: one stream per data-parallel rank).
+    ``jpeg``         None, or (qlo, qhi): the LR image additionally goes through ``jpeg.jpeg_roundtrip`` at a quality uniform in
+                     qlo .. qhi per sample, with ``jpeg_subsampling`` ('420' / '444') and the rounding surrogate ``jpeg_grad``
+                     ('ste' / 'cubic').  The call is then four launches -- sisr_degrade_draw, sisr_jpeg_tables (on the SAME step:
+                     the count advances once, ``state_dict`` is unchanged), sisr_degrade_fwd, sisr_jpeg_fwd -- still nothing read
+                     back; ``last_quality`` [N] int32 and ``last_tables`` [N, 2, 8, 8] are the latest call's.
 
     ``d(img_hr, image_size_lr)`` is two launches -- sisr_degrade_draw, sisr_degrade_fwd -- and reads nothing back: the step count is
     device memory that the draw advances, so a call captured by graph.GraphedStep degrades differently on every replay.  Every
@@ -158,17 +164,28 @@ class Degrader:
     ``fake``, keep their own kernels); ``last_kernels`` [N, K, K] and ``last_noise_sigma`` [N] are the latest call's.  ``step`` is
     the 0-dim int64 device tensor of draws made so far."""
 
-    def __init__(self, ksize=21, sigma=(0.2, 3.0), anisotropic=True, noise=(0., 0.), seed=0, rank=0, device=None):
+    def __init__(self, ksize=21, sigma=(0.2, 3.0), anisotropic=True, noise=(0., 0.), seed=0, rank=0, device=None, jpeg=None,
+                 jpeg_subsampling='420', jpeg_grad='ste'):
         self.ksize = _check_ksize(ksize, 'Degrader')
         self.sigma_lo, self.sigma_hi, self.noise_lo, self.noise_hi = _check_ranges(sigma, noise, 'Degrader')
         self.anisotropic, self.seed, self.rank = bool(anisotropic), int(seed), int(rank)
         if not 0 <= self.seed < 1 << 64 or not 0 <= self.rank < RANK_LIMIT:
             raise ValueError('Degrader: seed must be in [0, 2^64) and rank in [0, %d), got %d, %d' % (RANK_LIMIT, self.seed, self.rank))
+        self.jpeg = None
+        if jpeg is not None:
+            from . import jpeg as J
+            qlo, qhi = int(jpeg[0]), int(jpeg[1])
+            if not 1 <= qlo <= qhi <= 100:
+                raise ValueError('Degrader: jpeg = (qlo, qhi) needs 1 <= qlo <= qhi <= 100, got (%d, %d)' % (qlo, qhi))
+            if jpeg_subsampling not in J.SUBSAMPLING or jpeg_grad not in J.GRAD:
+                raise ValueError("Degrader: jpeg_subsampling is '444' or '420' and jpeg_grad 'ste' or 'cubic', got %r, %r"
+                                 % (jpeg_subsampling, jpeg_grad))
+            self.jpeg, self.jpeg_subsampling, self.jpeg_grad = (qlo, qhi), jpeg_subsampling, jpeg_grad
         dev = torch.device('cuda' if device is None else device)
         if dev.type != 'cuda':
             raise RuntimeError('Degrader: the draws live on the MI355X (got device %s); there is no CPU fallback' % dev)
         self.step = torch.zeros((), dtype=torch.int64, device=dev)
-        self.last_kernels = self.last_noise_sigma = self.last_drawn_step = None
+        self.last_kernels = self.last_noise_sigma = self.last_drawn_step = self.last_quality = self.last_tables = None
 
     def draw(self, n):
         """the tables of the next step for a batch of ``n``: -> (kernels, noise_sigma, drawn_step) on the device; advances ``step``"""
@@ -188,7 +205,23 @@ class Degrader:
             raise RuntimeError('Degrader: the batch is on %s, the draws on %s' % (img_hr.device, self.step.device))
         k, s, t = self.draw(int(img_hr.shape[0]))
         noisy = self.noise_hi > 0.0
-        return degrade(img_hr, image_size_lr, k, s if noisy else None, t if noisy else None, self.seed, self.rank, True)
+        if self.jpeg is None:
+            return degrade(img_hr, image_size_lr, k, s if noisy else None, t if noisy else None, self.seed, self.rank, True)
+        tables = self.draw_jpeg_tables(int(img_hr.shape[0]), t)          # before the forward: the draws of a step stay together
+        lr = degrade(img_hr, image_size_lr, k, s if noisy else None, t if noisy else None, self.seed, self.rank, True)
+        from .jpeg import jpeg_roundtrip
+        return jpeg_roundtrip(lr, tables, self.jpeg_subsampling, self.jpeg_grad, True)
+
+    def draw_jpeg_tables(self, n, drawn_step):
+        """the quantisation tables of step ``drawn_step`` (a 0-dim int64 device tensor, read and NOT advanced) for a batch of ``n``
+        -> tables [n, 2, 8, 8] on the device; ``last_quality`` holds the qualities"""
+        dev = self.step.device
+        q = torch.empty(n, dtype=torch.int32, device=dev)
+        tables = torch.empty((n, 2, 8, 8), dtype=torch.float32, device=dev)
+        L.check(L.lib().sisr_jpeg_tables(drawn_step.data_ptr(), self.seed, self.rank, n, self.jpeg[0], self.jpeg[1], q.data_ptr(),
+                                         tables.data_ptr(), _stream()), 'sisr_jpeg_tables')
+        self.last_quality, self.last_tables = q, tables
+        return tables
 
     def lr_from_hr(self, img_hr, image_size_lr, device='cpu'):
         """the reference's signature (utils.py:22-31; ``device`` is accepted and unused, as in utils.lr_from_hr)"""
