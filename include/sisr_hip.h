@@ -845,6 +845,29 @@ int sisr_bce_fwd(const float *p, const float *t_vec, float t_scalar, int64_t n, 
 int sisr_bce_bwd(const float *p, const float *t_vec, float t_scalar, int64_t n, float weight, const float *g,
                  float *dp, void *stream);
 
+/* ---- image-space loss: structural + pixel term of two NCHW fp32 batches, forward and backward.  The view
+ *      is the metrics' (crop, then luma for C == 3) and so is the SSIM; every term lives on the view:
+ *          loss[n] = w_ssim (1 - SSIM[n]) + w_pix mean_{C',H',W'} rho(a - b)
+ *          rho(d) = |d| (L1), sqrt(d^2 + eps^2) (Charbonnier), d^2 (MSE)
+ *      Fixed-order sums, no atomics, plain vector stores: bit-identical from call to call; nothing synchronises with the host.
+ *      The forward saves nothing: the backward recomputes the window moments from a and b.  SISR_E_UNSUPPORTED for C not in
+ *      {1, 3}; SISR_E_BADARG before any HIP call for N < 1, crop < 0, a view smaller than 11 x 11 with SSIM on (1 x 1 without),
+ *      a non-positive data_range, a negative eps, an unknown pix_kind, null pointers. ------------------------------------- */
+enum { SISR_PIX_L1 = 0, SISR_PIX_CHARBONNIER = 1, SISR_PIX_MSE = 2 };
+/* HOST: floats of workspace of the forward.  with_ssim != 0: one partial per 16 x 32 tile of window positions (the metrics' grid);
+ * with_ssim == 0: per 16 x 32 tile of view pixels */
+int sisr_image_loss_ws_floats(int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int32_t luma, int32_t with_ssim);
+/* loss: [N]; ssim / pix: [N] or NULL: SSIM[n] and the mean of rho.  The SSIM passes run when w_ssim != 0 or ssim != NULL, and
+ * `work` is sized by the query with that with_ssim.  Two launches: tiles -> `work`, then per image a fixed-order sum in double */
+int sisr_image_loss_fwd(const float *a, const float *b, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int32_t luma,
+                        float data_range, float w_ssim, float w_pix, int32_t pix_kind, float eps, float *work, float *loss,
+                        float *ssim, float *pix, void *stream);
+/* da / db: [N][C][H][W], either may be NULL (then not computed); g: [N] upstream gradients in DEVICE memory.  Every element is
+ * written: pixels of the cropped border get 0.  rho'(0) = 0 for L1.  The SSIM passes run when w_ssim != 0.  One launch */
+int sisr_image_loss_bwd(const float *a, const float *b, const float *g, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop,
+                        int32_t luma, float data_range, float w_ssim, float w_pix, int32_t pix_kind, float eps, float *da,
+                        float *db, void *stream);
+
 /* ---- misc ---------------------------------------------------------------------------------- */
 /* ---- optimizer: fused multi-tensor Adam --------------------------------------------------
  * One launch performs torch.optim.Adam's update (amsgrad=False, maximize=False; config.py:292-294, stepped at

@@ -8,6 +8,12 @@ launches: the MSE moves its two feature tensors (70.8 MB each at B16 / HR 96^2 u
 gradient) and saves nothing but its inputs.  ``bce_loss`` needs no label tensor, returns mean(p) -- the ``D_x`` / ``D_G_z``
 statistics -- from the same launch, and has no device-side range assertion: a NaN in gives a NaN out, never an abort.
 
+``image_loss`` (csrc/image_loss.hip) is the image-space term that SR trainers put beside those two: ``ssim_weight * (1 - SSIM) +
+pixel_weight * mean(rho(a - b))`` with rho L1, Charbonnier or MSE, on the crop / luma view and with the SSIM of ``metrics``; two
+launches forward, one backward, nothing saved but the inputs (the torch-op composition of SSIM alone is ten ``conv2d`` and about
+thirty elementwise launches with some fifteen saved image-size intermediates).  ``ssim_loss``, ``l1_loss`` and
+``charbonnier_loss`` are its one-term forms.
+
 Nothing here synchronises with the host: losses and statistics are 0-dim fp32 device tensors, bit-identical from call to call,
 and the launches can be captured by ``graph.GraphedStep``.  Opt-in: ``install(fused_losses=True)`` points ``torch.nn.BCELoss`` at
 ``BCELoss``; a trainer rebinds its ``content_loss_g`` / ``adversarial_loss_*`` to the functions below.
@@ -78,6 +84,105 @@ def feature_mse(a, b, weight=1.0):
     require_gpu_tensor(a, 'feature_mse input a')
     require_gpu_tensor(b, 'feature_mse input b')
     return _FeatureMSE.apply(a, b, float(weight))
+
+
+PIXEL_KINDS = {'l1': L.PIX_L1, 'charbonnier': L.PIX_CHARBONNIER, 'mse': L.PIX_MSE}
+SSIM_WINDOW = 11
+
+
+class _ImageLoss(torch.autograd.Function):
+    """-> (loss[N], ssim[N] or None, pix[N] or None); ``cfg`` = (N, C, H, W, crop, luma, data_range, w_ssim, w_pix, kind, eps)"""
+
+    @staticmethod
+    def forward(ctx, a, b, cfg, want_parts):
+        a, b = a.detach().contiguous(), b.detach().contiguous()
+        n, c, h, w, crop, luma, data_range, w_ssim, w_pix, kind, eps = cfg
+        lib, dev = L.lib(), a.device
+        with_ssim = int(w_ssim != 0.0 or want_parts)
+        ws = L.check_count(lib.sisr_image_loss_ws_floats(n, c, h, w, crop, luma, with_ssim), 'sisr_image_loss_ws_floats')
+        work = torch.empty(ws, dtype=torch.float32, device=dev)
+        loss = torch.empty(n, dtype=torch.float32, device=dev)
+        ssim = torch.empty(n, dtype=torch.float32, device=dev) if want_parts else None
+        pix = torch.empty(n, dtype=torch.float32, device=dev) if want_parts else None
+        L.check(lib.sisr_image_loss_fwd(a.data_ptr(), b.data_ptr(), n, c, h, w, crop, luma, data_range, w_ssim, w_pix, kind, eps,
+                                        work.data_ptr(), loss.data_ptr(), None if ssim is None else ssim.data_ptr(),
+                                        None if pix is None else pix.data_ptr(), _stream()), 'sisr_image_loss_fwd')
+        ctx.save_for_backward(a, b)            # the inputs themselves: the backward recomputes the window moments
+        ctx.cfg = cfg
+        if want_parts:
+            ctx.mark_non_differentiable(ssim, pix)
+        return loss, ssim, pix
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_ssim, _g_pix):
+        a, b = ctx.saved_tensors
+        n, c, h, w, crop, luma, data_range, w_ssim, w_pix, kind, eps = ctx.cfg
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        if da is not None or db is not None:
+            g = g.to(torch.float32).contiguous()
+            L.check(L.lib().sisr_image_loss_bwd(a.data_ptr(), b.data_ptr(), g.data_ptr(), n, c, h, w, crop, luma, data_range,
+                                                w_ssim, w_pix, kind, eps, None if da is None else da.data_ptr(),
+                                                None if db is None else db.data_ptr(), _stream()), 'sisr_image_loss_bwd')
+        return da, db, None, None
+
+
+def image_loss(a, b, ssim_weight=0.0, pixel_weight=1.0, pixel='l1', eps=1e-3, data_range=2.0, crop_border=0, luma=False,
+               reduction='mean', return_parts=False):
+    """``ssim_weight * (1 - SSIM[n]) + pixel_weight * mean(rho(a - b))`` per image of two fp32 [N, C, H, W] batches, C 1 or 3, on
+    the view of ``metrics`` (``crop_border`` pixels stripped from every side, then the BT.601 plane with ``luma``); SSIM is
+    ``metrics.ssim``'s, rho is ``|d|`` ('l1'), ``sqrt(d^2 + eps^2)`` ('charbonnier') or ``d^2`` ('mse').  -> 0-dim fp32 device
+    tensor (the mean over the batch), or [N] with ``reduction='none'``; with ``return_parts`` also the detached ``ssim[N]`` and
+    ``pix[N]`` (the SSIM passes then run whatever ``ssim_weight`` is).  Differentiable with respect to ``a``, ``b`` or both (only
+    what requires a gradient is computed; pixels of the cropped border get exact zeros), once.  The view needs 11 x 11 pixels
+    when SSIM is computed, 1 x 1 otherwise.  Non-contiguous inputs are made contiguous first; a bf16 caller casts."""
+    what = 'image_loss'
+    _validate_pair(a, b, what)
+    if a.dim() != 4:
+        raise ValueError('%s: two 4-D [N, C, H, W] tensors are expected, got %s' % (what, tuple(a.shape)))
+    n, c, h, w = a.shape
+    if c not in (1, 3):
+        raise ValueError('%s: 1 or 3 channels expected, got %d' % (what, c))
+    if pixel not in PIXEL_KINDS:
+        raise ValueError('%s: pixel is one of %s, got %r' % (what, sorted(PIXEL_KINDS), pixel))
+    if reduction not in ('mean', 'none'):
+        raise ValueError("%s: reduction is 'mean' or 'none', got %r" % (what, reduction))
+    if not float(eps) >= 0.0:
+        raise ValueError('%s: eps must not be negative, got %r' % (what, eps))
+    if not float(data_range) > 0.0:
+        raise ValueError('%s: data_range must be positive, got %r' % (what, data_range))
+    if isinstance(crop_border, bool) or crop_border != int(crop_border) or crop_border < 0:
+        raise ValueError('%s: crop_border must be a non-negative integer, got %r' % (what, crop_border))
+    crop = int(crop_border)
+    w_ssim, w_pix = float(ssim_weight), float(pixel_weight)
+    least = SSIM_WINDOW if (w_ssim != 0.0 or return_parts) else 1
+    if h - 2 * crop < least or w - 2 * crop < least:
+        raise ValueError('%s: %d x %d pixels remain after cropping %d from every side; %d x %d are needed'
+                         % (what, h - 2 * crop, w - 2 * crop, crop, least, least))
+    require_gpu_tensor(a, 'image_loss input a')
+    require_gpu_tensor(b, 'image_loss input b')
+    cfg = (n, c, h, w, crop, int(bool(luma)), float(data_range), w_ssim, w_pix, PIXEL_KINDS[pixel], float(eps))
+    loss, ssim, pix = _ImageLoss.apply(a, b, cfg, bool(return_parts))
+    if reduction == 'mean':
+        loss = loss.mean()
+    return (loss, ssim, pix) if return_parts else loss
+
+
+def ssim_loss(a, b, data_range=2.0, crop_border=0, luma=False, reduction='mean'):
+    """``1 - SSIM`` -> ``image_loss`` with the structural term alone"""
+    return image_loss(a, b, ssim_weight=1.0, pixel_weight=0.0, data_range=data_range, crop_border=crop_border, luma=luma,
+                      reduction=reduction)
+
+
+def l1_loss(a, b, crop_border=0, luma=False, reduction='mean'):
+    """``mean |a - b|`` per image -> ``image_loss`` with the L1 pixel term alone"""
+    return image_loss(a, b, pixel='l1', crop_border=crop_border, luma=luma, reduction=reduction)
+
+
+def charbonnier_loss(a, b, eps=1e-3, crop_border=0, luma=False, reduction='mean'):
+    """``mean sqrt((a - b)^2 + eps^2)`` per image -> ``image_loss`` with the Charbonnier pixel term alone"""
+    return image_loss(a, b, pixel='charbonnier', eps=eps, crop_border=crop_border, luma=luma, reduction=reduction)
 
 
 class _BCE(torch.autograd.Function):
