@@ -75,6 +75,7 @@ def operand(pro, x1, x2=None, pa=None, pb=None, pd=None, ps=None, pt=None, slope
       alt   the bf16 value farthest from q that the staging may hold instead; != q only on AMBIGUOUS elements
       alts  every candidate
       mag   sum of the magnitudes of the prologue's terms (what an fp32 rounding of v is relative to)
+      evals the two fp32 evaluations (2), (3) below before any bf16 rounding (what the fp32-tensor kernels stage: tests/f32_cases.py)
     How the compiler contracts a * b + c is its choice, so three evaluations are formed: (1) ONE rounding of the float64 value (the
     fully contracted limit) -> v; (2) every a * b + c one fused multiply-add, every other operation rounded (hipcc's default) -> q;
     (3) rounded after every operation (torch fp32).  An element where they stage different bf16 values -- the sign test of
@@ -116,7 +117,7 @@ def operand(pro, x1, x2=None, pa=None, pb=None, pd=None, ps=None, pt=None, slope
     mag = {NONE: lambda: da, ACT: lambda: da, ACT_BWD: lambda: da, AFFINE_ACT: lambda: k(pa) * da + k(pd),
            BNBWD: lambda: k(pa) * da + k(pb) * db + k(pd), BNACT_BWD: lambda: k(pa) * da + k(pb) * db + k(pd),
            TANH_BWD: lambda: da * (1 + db ** 2), RES_AFFINE: lambda: da + k(pa) * db + k(pd)}[pro]()
-    return NS(v=v, q=q, alt=alt, alts=[q] + alts, mag=mag, ambiguous=(q != alt))
+    return NS(v=v, q=q, alt=alt, alts=[q] + alts, mag=mag, ambiguous=(q != alt), evals=[e_fma, e_step])
 
 
 # ---- float64 references ------------------------------------------------------------------------------------------------------------
@@ -429,7 +430,8 @@ def wgrad_case(geom, xpro, gpro, tier, seed=0, coarse=True, x_rounded=True, g_ro
         go = operand(gpro, **kg)
     wshape = (cout, cin, k, k)
     if shuffle2:                                              # elementwise prologue first, then the view: original channel order 4 c + 2 i + j
-        go = NS(**{name: F.pixel_unshuffle(getattr(go, name), 2) for name in ('v', 'q', 'alt', 'mag')}, ambiguous=go.ambiguous)
+        go = NS(**{name: F.pixel_unshuffle(getattr(go, name), 2) for name in ('v', 'q', 'alt', 'mag')}, ambiguous=go.ambiguous,
+                evals=[F.pixel_unshuffle(e, 2) for e in go.evals])
     f = lambda a, g: conv_wgrad(a, g, wshape, stride, pad)
     ref = f(xo.q, go.q)
     s = f(xo.q.abs(), go.q.abs())
