@@ -24,6 +24,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 from .engine import _stream, require_gpu_tensor
+from .metrics import WINDOW, check_view
 
 
 def _check_tensor(t, what):
@@ -87,7 +88,6 @@ def feature_mse(a, b, weight=1.0):
 
 
 PIXEL_KINDS = {'l1': L.PIX_L1, 'charbonnier': L.PIX_CHARBONNIER, 'mse': L.PIX_MSE}
-SSIM_WINDOW = 11
 
 
 class _ImageLoss(torch.autograd.Function):
@@ -139,27 +139,15 @@ def image_loss(a, b, ssim_weight=0.0, pixel_weight=1.0, pixel='l1', eps=1e-3, da
     when SSIM is computed, 1 x 1 otherwise.  Non-contiguous inputs are made contiguous first; a bf16 caller casts."""
     what = 'image_loss'
     _validate_pair(a, b, what)
-    if a.dim() != 4:
-        raise ValueError('%s: two 4-D [N, C, H, W] tensors are expected, got %s' % (what, tuple(a.shape)))
+    w_ssim, w_pix = float(ssim_weight), float(pixel_weight)
+    crop = check_view(a, b, data_range, crop_border, least=WINDOW if (w_ssim != 0.0 or return_parts) else 1, what=what)
     n, c, h, w = a.shape
-    if c not in (1, 3):
-        raise ValueError('%s: 1 or 3 channels expected, got %d' % (what, c))
     if pixel not in PIXEL_KINDS:
         raise ValueError('%s: pixel is one of %s, got %r' % (what, sorted(PIXEL_KINDS), pixel))
     if reduction not in ('mean', 'none'):
         raise ValueError("%s: reduction is 'mean' or 'none', got %r" % (what, reduction))
     if not float(eps) >= 0.0:
         raise ValueError('%s: eps must not be negative, got %r' % (what, eps))
-    if not float(data_range) > 0.0:
-        raise ValueError('%s: data_range must be positive, got %r' % (what, data_range))
-    if isinstance(crop_border, bool) or crop_border != int(crop_border) or crop_border < 0:
-        raise ValueError('%s: crop_border must be a non-negative integer, got %r' % (what, crop_border))
-    crop = int(crop_border)
-    w_ssim, w_pix = float(ssim_weight), float(pixel_weight)
-    least = SSIM_WINDOW if (w_ssim != 0.0 or return_parts) else 1
-    if h - 2 * crop < least or w - 2 * crop < least:
-        raise ValueError('%s: %d x %d pixels remain after cropping %d from every side; %d x %d are needed'
-                         % (what, h - 2 * crop, w - 2 * crop, crop, least, least))
     require_gpu_tensor(a, 'image_loss input a')
     require_gpu_tensor(b, 'image_loss input b')
     cfg = (n, c, h, w, crop, int(bool(luma)), float(data_range), w_ssim, w_pix, PIXEL_KINDS[pixel], float(eps))

@@ -24,27 +24,30 @@ from .utils import lr_from_hr
 WINDOW = 11
 
 
-def _validate(a, b, data_range, crop_border):
-    """argument errors come before the device check: they are the caller's, whatever the tensors live on"""
+def check_view(a, b, data_range, crop_border, least=WINDOW, what='metrics'):
+    """The view rule of the metrics and of ``losses.image_loss``, stated once: two 4-D [N, C, H, W] tensors of one shape, C 1 or
+    3, ``crop_border`` a non-negative integer (no bool) that leaves ``least`` x ``least`` pixels (the SSIM window; 1 for a pixel
+    term alone), ``data_range`` > 0.  -> crop_border as an int.  Argument errors come before the device check: they are the
+    caller's, whatever the tensors live on"""
     for t in (a, b):
         if not isinstance(t, torch.Tensor) or t.dim() != 4:
-            raise ValueError('metrics take two 4-D [N, C, H, W] tensors, got %s'
-                             % (tuple(t.shape) if isinstance(t, torch.Tensor) else type(t),))
+            raise ValueError('%s: two 4-D [N, C, H, W] tensors are expected, got %s'
+                             % (what, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)))
     if a.shape != b.shape:
-        raise ValueError('metrics: the images differ in shape: %s vs %s' % (tuple(a.shape), tuple(b.shape)))
+        raise ValueError('%s: the images differ in shape: %s vs %s' % (what, tuple(a.shape), tuple(b.shape)))
     n, c, h, w = a.shape
     if n < 1:
-        raise ValueError('metrics: empty batch')
+        raise ValueError('%s: empty batch' % what)
     if c not in (1, 3):
-        raise ValueError('metrics: 1 or 3 channels expected, got %d' % c)
-    crop = int(crop_border)
-    if crop != crop_border or crop < 0:
-        raise ValueError('metrics: crop_border must be a non-negative integer, got %r' % (crop_border,))
-    if h - 2 * crop < WINDOW or w - 2 * crop < WINDOW:
-        raise ValueError('metrics: %d x %d pixels remain after cropping %d from every side; the SSIM window needs %d x %d'
-                         % (h - 2 * crop, w - 2 * crop, crop, WINDOW, WINDOW))
+        raise ValueError('%s: 1 or 3 channels expected, got %d' % (what, c))
     if not float(data_range) > 0.0:
-        raise ValueError('metrics: data_range must be positive, got %r' % (data_range,))
+        raise ValueError('%s: data_range must be positive, got %r' % (what, data_range))
+    if isinstance(crop_border, bool) or crop_border != int(crop_border) or crop_border < 0:
+        raise ValueError('%s: crop_border must be a non-negative integer, got %r' % (what, crop_border))
+    crop = int(crop_border)
+    if h - 2 * crop < least or w - 2 * crop < least:
+        raise ValueError('%s: %d x %d pixels remain after cropping %d from every side; %d x %d are needed'
+                         % (what, h - 2 * crop, w - 2 * crop, crop, least, least))
     return crop
 
 
@@ -56,7 +59,7 @@ def _native(t, what):
 
 
 def _run(a, b, data_range, crop_border, luma, want_psnr, want_ssim):
-    crop = _validate(a, b, data_range, crop_border)
+    crop = check_view(a, b, data_range, crop_border)
     a, b = _native(a, 'metrics input a'), _native(b, 'metrics input b')
     if a.device != b.device:
         raise ValueError('metrics: the images live on different devices: %s vs %s' % (a.device, b.device))

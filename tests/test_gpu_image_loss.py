@@ -5,9 +5,9 @@ definition evaluated in float64 on the CPU from the same fp32 inputs, with the g
 
 on the crop / luma view, SSIM with the separable 11-tap Gaussian (sigma 1.5) through F.conv2d at the "valid" positions.
 
-Inputs: the recipe of test_gpu_metrics._images (a smooth pattern per image and plane plus noise whose strength grows along x,
-never constant: a != b everywhere, so the L1 sign is never ambiguous).  Shapes: (1, 1, 11, 11) is one window position that every
-pixel's gradient comes from, (2, 3, 13, 17) a 3 x 7 region inside one tile, (2, 3, 45, 70) ragged tiles in both axes with a
+Inputs and definition: image_cases.py, shared with test_gpu_metrics.py (a smooth pattern per image and plane plus noise whose
+strength grows along x, never constant: a != b everywhere, so the L1 sign is never ambiguous).
+Shapes: (1, 1, 11, 11) is one window position that every pixel's gradient comes from, (2, 3, 13, 17) a 3 x 7 region inside one tile, (2, 3, 45, 70) ragged tiles in both axes with a
 backward halo that crosses tile seams, (1, 3, 96, 192) 6 x 6 position tiles and the 16th / 17th row and 32nd / 33rd column seams.
 The upstream gradient differs from image to image (reduction='none', (loss * g).sum()).
 
@@ -23,12 +23,12 @@ import torch.nn.functional as F
 
 from gpu_helpers import pkg
 from helpers import grads_close
+from image_cases import WINDOW, _definition, _images
 
 pytestmark = pytest.mark.gpu
 
 FWD_TOL = 2e-5
 GRAD_TOL = 1e-4
-WINDOW = 11
 
 SHAPES = [(1, 1, 11, 11), (2, 3, 13, 17), (2, 3, 45, 70), (1, 3, 96, 192)]
 VIEWS = [(0, False), (2, False), (4, True)]
@@ -48,60 +48,9 @@ VALUE_CASES = [(s, crop, luma, cfg) for s in SHAPES for crop, luma in VIEWS for 
                if min(s[2], s[3]) - 2 * crop >= _least(cfg)]
 
 
-@functools.lru_cache(maxsize=None)
-def _images(shape, seed=0):
-    """(a, b) fp32 CPU tensors in [-1, 1]; never modified"""
-    n, c, h, w = shape
-    y = torch.linspace(0, 1, h, dtype=torch.float64).view(1, 1, h, 1)
-    x = torch.linspace(0, 1, w, dtype=torch.float64).view(1, 1, 1, w)
-    i = torch.arange(n, dtype=torch.float64).view(n, 1, 1, 1)
-    k = torch.arange(c, dtype=torch.float64).view(1, c, 1, 1)
-    base = 0.8 * torch.sin(3 * (i + 1) * x + 2 * (k + 1) * y + i) * (0.3 + 0.7 * y)
-    noise = torch.randn(shape, dtype=torch.float64, generator=torch.Generator().manual_seed(1234 + seed))
-    a = base.clamp(-1, 1)
-    b = (base + noise * (0.02 + 0.25 * x)).clamp(-1, 1)
-    return a.float(), b.float()
-
-
 def _upstream(n):
     """a different upstream gradient for every image"""
     return 1.0 + 0.5 * torch.arange(n, dtype=torch.float64)
-
-
-def _view(t, crop, luma):
-    if crop:
-        t = t[:, :, crop:t.shape[2] - crop, crop:t.shape[3] - crop]
-    if luma and t.shape[1] == 3:
-        t = (0.299 * t[:, 0] + 0.587 * t[:, 1] + 0.114 * t[:, 2]).unsqueeze(1)
-    return t
-
-
-def _definition(a, b, ssim_weight=0.0, pixel_weight=1.0, pixel='l1', eps=1e-3, data_range=2.0, crop_border=0, luma=False):
-    """the loss as torch ops in the dtype of a and b -> (loss [N], ssim [N] or None, pix [N]); differentiable"""
-    a, b = _view(a, crop_border, luma), _view(b, crop_border, luma)
-    n, c, h, w = a.shape
-    d = a - b
-    rho = d.abs() if pixel == 'l1' else torch.sqrt(d * d + eps * eps) if pixel == 'charbonnier' else d * d
-    pix = rho.mean(dim=(1, 2, 3))
-    loss, ssim = pixel_weight * pix, None
-    if min(h, w) >= WINDOW:
-        g = torch.exp(-(torch.arange(WINDOW, dtype=torch.float64) - WINDOW // 2) ** 2 / (2 * 1.5 ** 2))
-        g = (g / g.sum()).to(a)
-
-        def win(t):
-            t = t.reshape(n * c, 1, h, w)
-            return F.conv2d(F.conv2d(t, g.view(1, 1, WINDOW, 1)), g.view(1, 1, 1, WINDOW))
-        c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
-        mu_a, mu_b = win(a), win(b)
-        var_a, var_b, cov = win(a * a) - mu_a ** 2, win(b * b) - mu_b ** 2, win(a * b) - mu_a * mu_b
-        m = ((2 * mu_a * mu_b + c1) * (2 * cov + c2)) / ((mu_a ** 2 + mu_b ** 2 + c1) * (var_a + var_b + c2))
-        assert m.shape[-2:] == (h - 10, w - 10)
-        ssim = m.reshape(n, -1).mean(dim=1)
-        if ssim_weight != 0.0:
-            loss = loss + ssim_weight * (1 - ssim)
-    else:
-        assert ssim_weight == 0.0
-    return loss, ssim, pix
 
 
 @functools.lru_cache(maxsize=None)
@@ -238,8 +187,8 @@ def test_non_contiguous_inputs_equal_their_contiguous_copies():
 
 
 def test_return_parts_and_reductions():
-    """ssim is the metric's value within 2e-5, not bit for bit: the loss has a tile kernel of its own (csrc/image_loss.hip), so
-    that csrc/metrics.hip keeps its arithmetic"""
+    """ssim is the metric's value bit for bit: the loss forward and the metric launch the same tile kernel (csrc/sisr_ssim.h)
+    and fold its partials in the same order"""
     Lo, M = pkg('losses'), pkg('metrics')
     shape, crop, luma = (2, 3, 45, 70), 2, False
     a, b = (t.cuda() for t in _images(shape))
@@ -249,7 +198,7 @@ def test_return_parts_and_reductions():
     want, want_ssim, want_pix = _definition(a64, b64, **kw)
     for t in (loss, ssim, pix):
         assert t.shape == (2,) and t.dtype == torch.float32 and t.is_cuda and not t.requires_grad
-    assert float((ssim - M.ssim(a, b, crop_border=crop, luma=luma)).abs().max()) <= FWD_TOL
+    assert torch.equal(ssim, M.ssim(a, b, crop_border=crop, luma=luma))
     assert float((ssim.double().cpu() - want_ssim).abs().max()) <= FWD_TOL
     assert float((pix.double().cpu() - want_pix).abs().max()) <= FWD_TOL
     assert float((loss.double().cpu() - want).abs().max()) <= 2.5 * FWD_TOL          # 0.5 and 2.0 times the two terms' bounds
@@ -263,6 +212,23 @@ def test_return_parts_and_reductions():
     assert torch.equal(Lo.ssim_loss(a, b, crop_border=crop), Lo.image_loss(a, b, ssim_weight=1.0, pixel_weight=0.0, crop_border=crop))
     assert torch.equal(Lo.l1_loss(a, b, luma=True), Lo.image_loss(a, b, pixel='l1', luma=True))
     assert torch.equal(Lo.charbonnier_loss(a, b, eps=1e-2), Lo.image_loss(a, b, pixel='charbonnier', eps=1e-2))
+
+
+@pytest.mark.parametrize('shape,crop,luma', [(s, crop, luma) for s in SHAPES for crop, luma in VIEWS
+                                             if min(s[2], s[3]) - 2 * crop >= WINDOW])
+def test_mse_parts_are_the_metrics_values(shape, crop, luma):
+    """pixel='mse' with return_parts runs the metric's own instantiation of the tile kernel: ssim equals metrics.ssim bit for
+    bit, and pix is the mean squared difference under metrics.psnr.  Both come from the same double sum; rounding pix to fp32 moves
+    the decibel value by at most 2.6e-7 dB and the fp32 psnr (below 64 dB) carries at most 1.9e-6 dB: 1e-5 dB leaves room for the
+    log10 of this float64 evaluation and nothing else"""
+    Lo, M = pkg('losses'), pkg('metrics')
+    a, b = (t.cuda() for t in _images(shape))
+    _, ssim, pix = Lo.image_loss(a, b, pixel='mse', crop_border=crop, luma=luma, reduction='none', return_parts=True)
+    psnr, m_ssim = M.psnr_ssim(a, b, crop_border=crop, luma=luma)
+    assert torch.equal(ssim, m_ssim) and torch.equal(ssim, M.ssim(a, b, crop_border=crop, luma=luma))
+    e_psnr = float((psnr.double() - 10.0 * torch.log10(2.0 ** 2 / pix.double())).abs().max())
+    print('image_loss mse parts %s crop %d luma %d: psnr - 10 log10(range^2 / pix) = %.3g dB' % (shape, crop, luma, e_psnr))
+    assert e_psnr <= 1e-5
 
 
 def test_launch_sequence_is_capturable_and_replays_on_new_contents():

@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from gpu_helpers import pkg
+from image_cases import _definition, _images
 
 pytestmark = pytest.mark.gpu
 
@@ -28,48 +29,10 @@ VIEWS = [(0, False), (2, False), (4, True)]
 VALUE_CASES = [(s, crop, luma) for s in SHAPES for crop, luma in VIEWS if min(s[2], s[3]) - 2 * crop >= 11]
 
 
-@functools.lru_cache(maxsize=None)
-def _images(shape, seed=0):
-    """(a, b) fp32 CPU tensors in [-1, 1]; never modified"""
-    n, c, h, w = shape
-    y = torch.linspace(0, 1, h, dtype=torch.float64).view(1, 1, h, 1)
-    x = torch.linspace(0, 1, w, dtype=torch.float64).view(1, 1, 1, w)
-    i = torch.arange(n, dtype=torch.float64).view(n, 1, 1, 1)
-    k = torch.arange(c, dtype=torch.float64).view(1, c, 1, 1)
-    base = 0.8 * torch.sin(3 * (i + 1) * x + 2 * (k + 1) * y + i) * (0.3 + 0.7 * y)
-    noise = torch.randn(shape, dtype=torch.float64, generator=torch.Generator().manual_seed(1234 + seed))
-    a = base.clamp(-1, 1)
-    b = (base + noise * (0.02 + 0.25 * x)).clamp(-1, 1)
-    return a.float(), b.float()
-
-
-def _view(t, crop, luma):
-    t = t.double()
-    if crop:
-        t = t[:, :, crop:t.shape[2] - crop, crop:t.shape[3] - crop]
-    if luma and t.shape[1] == 3:
-        t = (0.299 * t[:, 0] + 0.587 * t[:, 1] + 0.114 * t[:, 2]).unsqueeze(1)
-    return t
-
-
 def _reference(a, b, data_range, crop, luma):
-    """-> (psnr [N], ssim [N]) in float64"""
-    a, b = _view(a, crop, luma), _view(b, crop, luma)
-    n, c, h, w = a.shape
-    mse = ((a - b) ** 2).mean(dim=(1, 2, 3))
-    psnr = 10.0 * torch.log10(data_range ** 2 / mse)
-    g = torch.exp(-(torch.arange(11, dtype=torch.float64) - 5) ** 2 / (2 * 1.5 ** 2))
-    g = g / g.sum()
-
-    def win(t):
-        t = t.reshape(n * c, 1, h, w)
-        return F.conv2d(F.conv2d(t, g.view(1, 1, 11, 1)), g.view(1, 1, 1, 11))
-    c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
-    mu_a, mu_b = win(a), win(b)
-    var_a, var_b, cov = win(a * a) - mu_a ** 2, win(b * b) - mu_b ** 2, win(a * b) - mu_a * mu_b
-    m = ((2 * mu_a * mu_b + c1) * (2 * cov + c2)) / ((mu_a ** 2 + mu_b ** 2 + c1) * (var_a + var_b + c2))
-    assert m.shape[-2:] == (h - 10, w - 10)
-    return psnr, m.reshape(n, -1).mean(dim=1)
+    """-> (psnr [N], ssim [N]) in float64: the shared definition with the squared difference as its pixel term"""
+    _, ssim, mse = _definition(a.double(), b.double(), pixel='mse', data_range=data_range, crop_border=crop, luma=luma)
+    return 10.0 * torch.log10(data_range ** 2 / mse), ssim
 
 
 @functools.lru_cache(maxsize=None)
