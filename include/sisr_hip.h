@@ -868,7 +868,36 @@ int sisr_image_loss_bwd(const float *a, const float *b, const float *g, int32_t 
                         int32_t luma, float data_range, float w_ssim, float w_pix, int32_t pix_kind, float eps, float *da,
                         float *db, void *stream);
 
-/* ---- misc ---------------------------------------------------------------------------------- */
+/* ---- multi-scale SSIM of two NCHW fp32 batches, forward and backward.  The view is the metrics' (crop, then
+ *      luma for C == 3), applied once at the finest scale; level j + 1 is the 2 x 2 mean (stride 2, no padding: an odd last row /
+ *      column is dropped) of level j; window, "valid" positions, C1 and C2 are the metrics' at every level.  With M = levels and
+ *      cs = (2 s_ab + C2) / (s_a^2 + s_b^2 + C2), l = (2 mu_a mu_b + C1) / (mu_a^2 + mu_b^2 + C1) per window position:
+ *          t_j[n,p] = mean of cs (j < M - 1), mean of l cs (j = M - 1);   MS[n,p] = prod_j t_j^{w_j}, exactly 0 when a t_j <= 0;
+ *          ms[n] = mean_p MS[n,p]
+ *      Fixed-order sums, no atomics, plain vector stores: bit-identical from call to call; nothing synchronises with the host.
+ *      `weights`: HOST array of 5 floats, the first `levels` are used as given.  SISR_E_UNSUPPORTED for C not in {1, 3};
+ *      SISR_E_BADARG before any HIP call for N < 1, crop < 0, levels outside 1..5, a level smaller than 11 x 11 (the view needs
+ *      11 << (levels - 1) pixels a side), a data_range or a weight that is not positive and finite, null pointers;
+ *      SISR_E_TOOBIG past INT32_MAX floats or workgroups. --------------------------------------------------------------------- */
+/* HOST: floats of which = 0: one pyramid buffer (levels >= 1 of ONE input, [N][C'][H_j][W_j] each, level 1 first; 0 for one
+ * level); 1: the forward's partials (one pair per 16 x 32 tile of window positions, all levels); 2: the backward's gradient planes
+ * (two pyramid buffers: a's, then b's) */
+int sisr_ms_ssim_ws_floats(int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int32_t luma, int32_t levels, int32_t which);
+/* pyr_a / pyr_b: pyramid buffers, written (may be NULL for one level); part: the partials; terms: [levels][N][C'] = t_j[n,p];
+ * ms: [N].  levels + 1 launches: one tile kernel per level (it also writes the next level), then per image a fixed-order sum in
+ * double */
+int sisr_ms_ssim_fwd(const float *a, const float *b, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int32_t luma,
+                     float data_range, int32_t levels, const float *weights, float *pyr_a, float *pyr_b, float *part,
+                     float *terms, float *ms, void *stream);
+/* the gradient of sum_n g[n] (1 - ms[n]).  pyr_a / pyr_b / terms: as the forward left them; g: [N] upstream gradients in DEVICE
+ * memory; work: the gradient planes (may be NULL for one level); da / db: [N][C][H][W], either may be NULL (then not computed).
+ * Every element is written: pixels of the cropped border get 0, and so does every pixel of an (image, plane) with a term <= 0.
+ * `levels` launches, coarsest level first */
+int sisr_ms_ssim_bwd(const float *a, const float *b, const float *pyr_a, const float *pyr_b, const float *terms, const float *g,
+                     int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int32_t luma, float data_range, int32_t levels,
+                     const float *weights, float *work, float *da, float *db, void *stream);
+
+/* ---- misc---------------------------------------------------------------------------------- */
 /* ---- optimizer: fused multi-tensor Adam --------------------------------------------------
  * One launch performs torch.optim.Adam's update (amsgrad=False, maximize=False; config.py:292-294, stepped at
  * train.py:75,108) for every parameter of a network.  Table in DEVICE memory; block_start = running sum of

@@ -248,6 +248,9 @@ _SIGS = {
     'sisr_image_loss_ws_floats': [_i32] * 7,
     'sisr_image_loss_fwd': [_f, _f] + [_i32] * 6 + [_f32, _f32, _f32, _i32, _f32, _f, _f, _f, _f, _f],
     'sisr_image_loss_bwd': [_f, _f, _f] + [_i32] * 6 + [_f32, _f32, _f32, _i32, _f32, _f, _f, _f],
+    'sisr_ms_ssim_ws_floats': [_i32] * 8,
+    'sisr_ms_ssim_fwd': [_f, _f] + [_i32] * 6 + [_f32, _i32, C.POINTER(_f32), _f, _f, _f, _f, _f, _f],
+    'sisr_ms_ssim_bwd': [_f] * 6 + [_i32] * 6 + [_f32, _i32, C.POINTER(_f32), _f, _f, _f, _f],
     'sisr_struct_sizes': [C.POINTER(_i32), _i32],
     'sisr_device_info': [C.POINTER(_i32), C.POINTER(_i32), C.c_char_p, _i32],
     'sisr_mfma_selftest': [_f, _f],

@@ -14,6 +14,10 @@ launches forward, one backward, nothing saved but the inputs (the torch-op compo
 thirty elementwise launches with some fifteen saved image-size intermediates).  ``ssim_loss``, ``l1_loss`` and
 ``charbonnier_loss`` are its one-term forms.
 
+``ms_ssim_loss`` (csrc/ms_ssim.hip) is ``1 - MS-SSIM`` with the multi-scale SSIM of ``metrics.ms_ssim``: ``len(weights)`` scales,
+one launch per scale and a finish forward, one launch per scale backward; saved are the inputs, their pooled levels and the
+per-scale terms.
+
 Nothing here synchronises with the host: losses and statistics are 0-dim fp32 device tensors, bit-identical from call to call,
 and the launches can be captured by ``graph.GraphedStep``.  Opt-in: ``install(fused_losses=True)`` points ``torch.nn.BCELoss`` at
 ``BCELoss``; a trainer rebinds its ``content_loss_g`` / ``adversarial_loss_*`` to the functions below.
@@ -24,7 +28,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 from .engine import _stream, require_gpu_tensor
-from .metrics import WINDOW, check_view
+from .metrics import MS_SSIM_WEIGHTS, WINDOW, check_ms_ssim, check_view, ms_ssim_forward, weights5
 
 
 def _check_tensor(t, what):
@@ -171,6 +175,56 @@ def l1_loss(a, b, crop_border=0, luma=False, reduction='mean'):
 def charbonnier_loss(a, b, eps=1e-3, crop_border=0, luma=False, reduction='mean'):
     """``mean sqrt((a - b)^2 + eps^2)`` per image -> ``image_loss`` with the Charbonnier pixel term alone"""
     return image_loss(a, b, pixel='charbonnier', eps=eps, crop_border=crop_border, luma=luma, reduction=reduction)
+
+
+class _MsSsimLoss(torch.autograd.Function):
+    """-> 1 - ms_ssim [N]; ``cfg`` = (N, C, H, W, crop, luma, data_range, weights)"""
+
+    @staticmethod
+    def forward(ctx, a, b, cfg):
+        a, b = a.detach().contiguous(), b.detach().contiguous()
+        ms, terms, pyr_a, pyr_b = ms_ssim_forward(a, b, cfg)
+        ctx.save_for_backward(a, b, pyr_a, pyr_b, terms)      # the inputs, their pooled levels and the terms table: nothing else
+        ctx.cfg = cfg
+        return 1.0 - ms
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a, b, pyr_a, pyr_b, terms = ctx.saved_tensors
+        n, c, h, w, crop, luma, data_range, wts = ctx.cfg
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        if da is not None or db is not None:
+            lib = L.lib()
+            g = g.to(torch.float32).contiguous()
+            ws = L.check_count(lib.sisr_ms_ssim_ws_floats(n, c, h, w, crop, luma, len(wts), 2), 'sisr_ms_ssim_ws_floats')
+            work = torch.empty(ws, dtype=torch.float32, device=a.device)
+            L.check(lib.sisr_ms_ssim_bwd(a.data_ptr(), b.data_ptr(), pyr_a.data_ptr(), pyr_b.data_ptr(), terms.data_ptr(),
+                                         g.data_ptr(), n, c, h, w, crop, luma, data_range, len(wts), weights5(wts), work.data_ptr(),
+                                         None if da is None else da.data_ptr(), None if db is None else db.data_ptr(), _stream()),
+                    'sisr_ms_ssim_bwd')
+        return da, db, None
+
+
+def ms_ssim_loss(a, b, data_range=2.0, crop_border=0, luma=False, weights=MS_SSIM_WEIGHTS, reduction='mean'):
+    """``1 - MS-SSIM[n]`` per image of two fp32 [N, C, H, W] batches, C 1 or 3, with the multi-scale SSIM of ``metrics.ms_ssim``
+    (M = ``len(weights)`` scales on the crop / luma view; the view needs ``11 << (M - 1)`` pixels a side, so two or three scales fit
+    a 96 x 96 patch).  -> 0-dim fp32 device tensor (the mean over the batch), or [N] with ``reduction='none'``.  Differentiable
+    with respect to ``a``, ``b`` or both (only what requires a gradient is computed), once; pixels of the cropped border get exact
+    zeros, and so does every pixel of an (image, plane) whose score is 0 because a scale's term is not positive.  M + 1 launches
+    forward, M backward; saved: the inputs, their pooled levels and the terms table.  Non-contiguous inputs are made contiguous
+    first; a bf16 caller casts."""
+    what = 'ms_ssim_loss'
+    _validate_pair(a, b, what)
+    crop, wts = check_ms_ssim(a, b, data_range, crop_border, weights, what=what)
+    if reduction not in ('mean', 'none'):
+        raise ValueError("%s: reduction is 'mean' or 'none', got %r" % (what, reduction))
+    require_gpu_tensor(a, 'ms_ssim_loss input a')
+    require_gpu_tensor(b, 'ms_ssim_loss input b')
+    n, c, h, w = a.shape
+    loss = _MsSsimLoss.apply(a, b, (n, c, h, w, crop, int(bool(luma)), float(data_range), wts))
+    return loss.mean() if reduction == 'mean' else loss
 
 
 class _BCE(torch.autograd.Function):

@@ -12,8 +12,12 @@ full-range plane Y = 0.299 R + 0.587 G + 0.114 B of the normalised values) is ap
 PSNR = 10 log10(data_range^2 / mse), +inf for equal images; SSIM is Wang et al.'s with the 11 x 11 Gaussian window
 (sigma 1.5), "valid" window positions only, C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2, averaged over planes and
 positions.  ``data_range`` defaults to 2.0: the project's images are normalised to [-1, 1].
+``ms_ssim`` (csrc/ms_ssim.hip) is the multi-scale form with ``len(weights)`` scales; ``check_ms_ssim`` / ``ms_ssim_forward`` are
+shared with ``losses.ms_ssim_loss``, its differentiable counterpart.
 """
 import contextlib
+import ctypes
+import math
 
 import torch
 
@@ -22,6 +26,8 @@ from .engine import _stream, require_gpu_tensor
 from .utils import lr_from_hr
 
 WINDOW = 11
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang, Simoncelli, Bovik 2003: five scales, finest first
+MS_SSIM_MAX_SCALES = 5
 
 
 def check_view(a, b, data_range, crop_border, least=WINDOW, what='metrics'):
@@ -88,6 +94,72 @@ def ssim(a, b, data_range=2.0, crop_border=0, luma=False):
 def psnr_ssim(a, b, data_range=2.0, crop_border=0, luma=False):
     """-> (psnr Tensor[N], ssim Tensor[N]) from one launch sequence (a metric: inputs are detached)"""
     return _run(a, b, data_range, crop_border, luma, True, True)
+
+
+def check_ms_ssim(a, b, data_range, crop_border, weights, what='ms_ssim'):
+    """The argument rule of ``ms_ssim`` and of ``losses.ms_ssim_loss``, stated once: ``check_view``'s, fp32 tensors on one device, a
+    finite ``data_range``, 1 to 5 positive finite ``weights`` (one per scale), and a view of at least ``11 << (M - 1)`` pixels a
+    side for M scales.  -> (crop_border as an int, the weights as a tuple of floats).  All of it comes before the device check"""
+    crop = check_view(a, b, data_range, crop_border, what=what)
+    for t in (a, b):
+        if t.dtype != torch.float32:
+            raise ValueError('%s: fp32 expected, got %s' % (what, t.dtype))
+    if a.device != b.device:
+        raise ValueError('%s: the images live on different devices: %s vs %s' % (what, a.device, b.device))
+    if not math.isfinite(float(data_range)):
+        raise ValueError('%s: data_range must be finite, got %r' % (what, data_range))
+    try:
+        wts = tuple(float(x) for x in weights)
+    except TypeError:
+        raise ValueError('%s: weights is a sequence of 1 to %d numbers, got %r' % (what, MS_SSIM_MAX_SCALES, weights)) from None
+    if not 1 <= len(wts) <= MS_SSIM_MAX_SCALES:
+        raise ValueError('%s: 1 to %d weights (one per scale) are expected, got %d' % (what, MS_SSIM_MAX_SCALES, len(wts)))
+    for x in wts:
+        if not (x > 0.0 and math.isfinite(x)):
+            raise ValueError('%s: every weight must be positive and finite, got %r' % (what, wts))
+    side = min(a.shape[2], a.shape[3]) - 2 * crop
+    fits = max(m for m in range(1, MS_SSIM_MAX_SCALES + 1) if side >> (m - 1) >= WINDOW)
+    if len(wts) > fits:
+        raise ValueError('%s: %d scales need %d pixels a side, %d x %d remain after cropping %d from every side: at most %d scales fit'
+                         % (what, len(wts), WINDOW << (len(wts) - 1), a.shape[2] - 2 * crop, a.shape[3] - 2 * crop, crop, fits))
+    return crop, wts
+
+
+def ms_ssim_forward(a, b, cfg):
+    """The forward launches of csrc/ms_ssim.hip on detached contiguous fp32 device tensors; ``cfg`` = (N, C, H, W, crop, luma,
+    data_range, weights).  -> (ms [N], terms [M, N, C'], pyr_a, pyr_b): the pyramid buffers hold levels >= 1 of the two inputs"""
+    n, c, h, w, crop, luma, data_range, wts = cfg
+    lib, dev, m = L.lib(), a.device, len(wts)
+
+    def floats(which):
+        return L.check_count(lib.sisr_ms_ssim_ws_floats(n, c, h, w, crop, luma, m, which), 'sisr_ms_ssim_ws_floats')
+    pyr_a, pyr_b = (torch.empty(floats(0), dtype=torch.float32, device=dev) for _ in range(2))
+    part = torch.empty(floats(1), dtype=torch.float32, device=dev)
+    terms = torch.empty((m, n, 1 if (luma and c == 3) else c), dtype=torch.float32, device=dev)
+    ms = torch.empty(n, dtype=torch.float32, device=dev)
+    L.check(lib.sisr_ms_ssim_fwd(a.data_ptr(), b.data_ptr(), n, c, h, w, crop, luma, data_range, m, weights5(wts), pyr_a.data_ptr(),
+                                 pyr_b.data_ptr(), part.data_ptr(), terms.data_ptr(), ms.data_ptr(), _stream()), 'sisr_ms_ssim_fwd')
+    return ms, terms, pyr_a, pyr_b
+
+
+def weights5(wts):
+    """the host array of five floats that the entry points of csrc/ms_ssim.hip take"""
+    return (ctypes.c_float * MS_SSIM_MAX_SCALES)(*(tuple(wts) + (0.0,) * (MS_SSIM_MAX_SCALES - len(wts))))
+
+
+def ms_ssim(a, b, data_range=2.0, crop_border=0, luma=False, weights=MS_SSIM_WEIGHTS, return_terms=False):
+    """per-image multi-scale SSIM (Wang, Simoncelli, Bovik 2003) -> fp32 Tensor[N] on the inputs' device (a metric: inputs are
+    detached); with ``return_terms`` also ``terms [M, N, C']``.  M = ``len(weights)`` scales, ``weights`` used as given (not
+    renormalised): the view (``crop_border``, ``luma``) is applied once, every further scale is the 2 x 2 mean of the one before
+    (an odd last row / column is dropped), and with ``cs`` the contrast-structure factor and ``l`` the luminance factor of the
+    SSIM map, ``terms[j]`` is the mean of ``cs`` for j < M - 1 and of ``l cs`` (SSIM) for the last scale.  Per image and plane the
+    score is ``prod_j terms[j] ** weights[j]``, exactly 0 when a term is <= 0; the planes are averaged.  The view needs
+    ``11 << (M - 1)`` pixels a side (176 for the default five scales).  fp32 inputs; non-contiguous ones are made contiguous"""
+    crop, wts = check_ms_ssim(a, b, data_range, crop_border, weights)
+    a, b = _native(a, 'ms_ssim input a'), _native(b, 'ms_ssim input b')
+    n, c, h, w = a.shape
+    ms, terms, _, _ = ms_ssim_forward(a, b, (n, c, h, w, crop, int(bool(luma)), float(data_range), wts))
+    return (ms, terms) if return_terms else ms
 
 
 def evaluate_generator(net_g, img_hr, image_size_lr, crop_border=None, luma=False, ema=None):
