@@ -897,6 +897,35 @@ int sisr_ms_ssim_bwd(const float *a, const float *b, const float *pyr_a, const f
                      int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int32_t luma, float data_range, int32_t levels,
                      const float *weights, float *work, float *da, float *db, void *stream);
 
+/* ---- frequency-domain loss of two NCHW fp32 batches, forward and backward.  The view is the metrics'
+ *      (crop, then luma for C == 3): [N][C'][H'][W'].  With d = view(a) - view(b), D[kh, kw] = sum_{y,x} d[y, x]
+ *      exp(-2 pi i (kh y / H' + kw x / W')) and Wh = W' / 2 + 1:
+ *          L1, Charbonnier: loss[n] = mean over (C', kh < H', kw < Wh, {Re, Im}) of rho(.), rho(z) = |z|, sqrt(z^2 + eps^2)
+ *                           (the half spectrum as rfft2 returns it, unnormalised, no Hermitian doubling; rho'(0) = 0 for L1)
+ *          focal:           loss[n] = sum_p sum_{kh, kw < Wh} h |D|^(2 + alpha) / (max_p |D|^alpha (H' W')^2 C'), h = 1 for kw = 0 and
+ *                           (W' even) kw = W' / 2, otherwise 2: the focal frequency loss over the full ortho-normalised spectrum with
+ *                           the weight matrix |D|^alpha / max |D|^alpha per (n, plane) held constant for the gradient; a plane with
+ *                           a == b has loss 0 and gradient 0
+ *      A direct separable DFT with the twiddle tables in LDS: any view side 1 .. SISR_FREQ_MAX_SIDE.  Fixed-order sums, no atomics,
+ *      plain vector stores: bit-identical from call to call; nothing synchronises with the host.  SISR_E_UNSUPPORTED for C not in
+ *      {1, 3}; SISR_E_BADARG before any HIP call for N < 1, crop < 0, a view side outside 1 .. SISR_FREQ_MAX_SIDE, a negative eps,
+ *      alpha outside (0, 4], an unknown kind, null pointers; SISR_E_TOOBIG past INT32_MAX floats or workgroups. ------------------- */
+enum { SISR_FREQ_L1 = 0, SISR_FREQ_CHARBONNIER = 1, SISR_FREQ_FOCAL = 2 };
+#define SISR_FREQ_MAX_SIDE 256
+/* HOST: floats of which = 0: the forward's `work` (the row spectra [N][C'][H'][Wh][2], then one (sum, max) pair per workgroup of the
+ * column pass); 1: `spec`, the saved spectrum [N][C'][H'][Wh][2]; 2: `pmax`, the plane maxima [N][C']; 3: the backward's `work` */
+int sisr_freq_loss_ws_floats(int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int32_t luma, int32_t which);
+/* loss: [N].  spec: D itself, written when not NULL (all the backward needs: the inputs are not read again).  pmax: max |D|^2 per
+ * (n, plane), written for focal (not NULL then), untouched otherwise.  eps is read for Charbonnier, alpha for focal; both are
+ * checked for every kind.  Three launches: rows, columns + partial sums, then per image a fixed-order sum in double */
+int sisr_freq_loss_fwd(const float *a, const float *b, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, int32_t luma,
+                       int32_t kind, float eps, float alpha, float *work, float *spec, float *pmax, float *loss, void *stream);
+/* spec / pmax: as the forward left them; g: [N] upstream gradients in DEVICE memory; da / db: [N][C][H][W], either may be NULL
+ * (then not computed; db is -da bit for bit).  Every element is written: pixels of the cropped border get 0.  Two launches */
+int sisr_freq_loss_bwd(const float *spec, const float *pmax, const float *g, int32_t N, int32_t C, int32_t H, int32_t W,
+                       int32_t crop, int32_t luma, int32_t kind, float eps, float alpha, float *work, float *da, float *db,
+                       void *stream);
+
 /* ---- misc---------------------------------------------------------------------------------- */
 /* ---- optimizer: fused multi-tensor Adam --------------------------------------------------
  * One launch performs torch.optim.Adam's update (amsgrad=False, maximize=False; config.py:292-294, stepped at

@@ -19,6 +19,8 @@ EPI_NONE, EPI_TANH = range(2)
 JPEG_444, JPEG_420 = range(2)                # subsampling codes of sisr_jpeg_fwd / sisr_jpeg_bwd
 JPEG_GRAD_STE, JPEG_GRAD_CUBIC = range(2)
 PIX_L1, PIX_CHARBONNIER, PIX_MSE = range(3)  # pix_kind of sisr_image_loss_fwd / sisr_image_loss_bwd
+FREQ_L1, FREQ_CHARBONNIER, FREQ_FOCAL = range(3)   # kind of sisr_freq_loss_fwd / sisr_freq_loss_bwd
+FREQ_MAX_SIDE = 256                          # SISR_FREQ_MAX_SIDE: the longest view side the DFT kernels take
 ROUTE_GENERIC, ROUTE_DEEP, ROUTE_TOIMAGE, ROUTE_TRUNK, ROUTE_THIN = range(5)      # enum SisrRoute: what the sisr_*_route calls answer
 
 _f = C.c_void_p      # device pointers travel as void*
@@ -251,6 +253,9 @@ _SIGS = {
     'sisr_ms_ssim_ws_floats': [_i32] * 8,
     'sisr_ms_ssim_fwd': [_f, _f] + [_i32] * 6 + [_f32, _i32, C.POINTER(_f32), _f, _f, _f, _f, _f, _f],
     'sisr_ms_ssim_bwd': [_f] * 6 + [_i32] * 6 + [_f32, _i32, C.POINTER(_f32), _f, _f, _f, _f],
+    'sisr_freq_loss_ws_floats': [_i32] * 7,
+    'sisr_freq_loss_fwd': [_f, _f] + [_i32] * 7 + [_f32, _f32, _f, _f, _f, _f, _f],
+    'sisr_freq_loss_bwd': [_f, _f, _f] + [_i32] * 7 + [_f32, _f32, _f, _f, _f, _f],
     'sisr_struct_sizes': [C.POINTER(_i32), _i32],
     'sisr_device_info': [C.POINTER(_i32), C.POINTER(_i32), C.c_char_p, _i32],
     'sisr_mfma_selftest': [_f, _f],

@@ -18,6 +18,11 @@ thirty elementwise launches with some fifteen saved image-size intermediates).  
 one launch per scale and a finish forward, one launch per scale backward; saved are the inputs, their pooled levels and the
 per-scale terms.
 
+``frequency_loss`` (csrc/freq_loss.hip) is the frequency-domain term: the FFT-L1 / Charbonnier loss over the half spectrum or the
+focal frequency loss, from ONE direct separable DFT of ``a - b`` (view sides up to 256, any length); three launches forward, two
+backward; saved are the spectrum and the plane maxima, not the inputs.  ``fft_l1_loss`` and ``focal_frequency_loss`` are its
+one-term forms.
+
 Nothing here synchronises with the host: losses and statistics are 0-dim fp32 device tensors, bit-identical from call to call,
 and the launches can be captured by ``graph.GraphedStep``.  Opt-in: ``install(fused_losses=True)`` points ``torch.nn.BCELoss`` at
 ``BCELoss``; a trainer rebinds its ``content_loss_g`` / ``adversarial_loss_*`` to the functions below.
@@ -225,6 +230,102 @@ def ms_ssim_loss(a, b, data_range=2.0, crop_border=0, luma=False, weights=MS_SSI
     n, c, h, w = a.shape
     loss = _MsSsimLoss.apply(a, b, (n, c, h, w, crop, int(bool(luma)), float(data_range), wts))
     return loss.mean() if reduction == 'mean' else loss
+
+
+FREQ_KINDS = {'l1': L.FREQ_L1, 'charbonnier': L.FREQ_CHARBONNIER, 'focal': L.FREQ_FOCAL}
+
+
+class _FreqLoss(torch.autograd.Function):
+    """-> loss [N]; ``cfg`` = (N, C, H, W, crop, luma, kind, eps, alpha)"""
+
+    @staticmethod
+    def forward(ctx, a, b, cfg):
+        a, b = a.detach().contiguous(), b.detach().contiguous()
+        n, c, h, w, crop, luma, kind, eps, alpha = cfg
+        lib, dev = L.lib(), a.device
+        shape = (n, c, h, w, crop, luma)
+
+        def buf(which):
+            return torch.empty(L.check_count(lib.sisr_freq_loss_ws_floats(*shape, which), 'sisr_freq_loss_ws_floats'),
+                               dtype=torch.float32, device=dev)
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        work, loss = buf(0), torch.empty(n, dtype=torch.float32, device=dev)
+        spec = buf(1) if need else None                              # the spectrum D: written only when a gradient will be needed
+        pmax = buf(2) if kind == L.FREQ_FOCAL else None
+        L.check(lib.sisr_freq_loss_fwd(a.data_ptr(), b.data_ptr(), *shape, kind, eps, alpha, work.data_ptr(),
+                                       None if spec is None else spec.data_ptr(), None if pmax is None else pmax.data_ptr(),
+                                       loss.data_ptr(), _stream()), 'sisr_freq_loss_fwd')
+        if need:
+            ctx.save_for_backward(spec, pmax)  # D and the plane maxima: the inputs are NOT kept
+        ctx.cfg, ctx.dims = cfg, (a.shape, dev)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        spec, pmax = ctx.saved_tensors
+        n, c, h, w, crop, luma, kind, eps, alpha = ctx.cfg
+        shape, dev = ctx.dims
+        da = torch.empty(shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        db = torch.empty(shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        if da is not None or db is not None:
+            lib = L.lib()
+            g = g.to(torch.float32).contiguous()
+            ws = L.check_count(lib.sisr_freq_loss_ws_floats(n, c, h, w, crop, luma, 3), 'sisr_freq_loss_ws_floats')
+            work = torch.empty(ws, dtype=torch.float32, device=dev)
+            L.check(lib.sisr_freq_loss_bwd(spec.data_ptr(), None if pmax is None else pmax.data_ptr(), g.data_ptr(), n, c, h, w, crop,
+                                           luma, kind, eps, alpha, work.data_ptr(), None if da is None else da.data_ptr(),
+                                           None if db is None else db.data_ptr(), _stream()), 'sisr_freq_loss_bwd')
+        return da, db, None
+
+
+def frequency_loss(a, b, kind='l1', eps=1e-3, alpha=1.0, crop_border=0, luma=False, reduction='mean'):
+    """A frequency-domain loss per image of two fp32 [N, C, H, W] batches, C 1 or 3, on the view of ``metrics`` (``crop_border``
+    pixels stripped from every side, then the BT.601 plane with ``luma``: [N, C', H', W']), with ``D`` the unnormalised 2-D DFT of
+    ``view(a) - view(b)`` (one transform serves both images):
+
+    ``kind='l1'``: the mean of ``|Re D|`` and ``|Im D|`` over the half spectrum ``torch.fft.rfft2`` returns (BasicSR's ``FFTLoss``:
+    ``kw < W' // 2 + 1``, no Hermitian doubling; a component that is exactly 0 has gradient 0).  ``kind='charbonnier'``: the same
+    with ``sqrt(z^2 + eps^2)`` per component.  ``kind='focal'``: the focal frequency loss (Jiang et al., ICCV 2021) with
+    ``patch_factor=1`` and no ``log_matrix`` / ``ave_spectrum`` / ``batch_matrix``: the mean over the FULL ``norm='ortho'`` spectrum of
+    ``w * |D|^2 / (H' W')`` with ``w = |D|^alpha / max |D|^alpha`` per (image, plane), ``w`` a constant for the gradient; an (image,
+    plane) with ``a == b`` has loss 0 and an all-zero gradient.
+
+    -> 0-dim fp32 device tensor (the mean over the batch), or [N] with ``reduction='none'``.  Differentiable with respect to ``a``,
+    ``b`` or both (only what requires a gradient is computed; pixels of the cropped border get exact zeros; ``db`` is ``-da`` bit
+    for bit), once.  View sides 1 .. 256 (a direct separable DFT, csrc/freq_loss.hip: no power-of-two rule).  Three launches forward,
+    two backward; the backward does not read the inputs: saved are ``D`` (``N C' H' (W' // 2 + 1) 2`` floats, about one input's
+    size) and the plane maxima, and nothing at all when no gradient is required.  Non-contiguous inputs are made contiguous first; a
+    bf16 caller casts."""
+    what = 'frequency_loss'
+    _validate_pair(a, b, what)
+    crop = check_view(a, b, 1.0, crop_border, least=1, what=what)
+    n, c, h, w = a.shape
+    if kind not in FREQ_KINDS:
+        raise ValueError('%s: kind is one of %s, got %r' % (what, sorted(FREQ_KINDS), kind))
+    if reduction not in ('mean', 'none'):
+        raise ValueError("%s: reduction is 'mean' or 'none', got %r" % (what, reduction))
+    if not float(eps) >= 0.0:
+        raise ValueError('%s: eps must not be negative, got %r' % (what, eps))
+    if not 0.0 < float(alpha) <= 4.0:
+        raise ValueError('%s: alpha must lie in (0, 4], got %r' % (what, alpha))
+    if max(h, w) - 2 * crop > L.FREQ_MAX_SIDE:
+        raise ValueError('%s: %d x %d pixels remain after cropping; the kernels take view sides up to %d'
+                         % (what, h - 2 * crop, w - 2 * crop, L.FREQ_MAX_SIDE))
+    require_gpu_tensor(a, 'frequency_loss input a')
+    require_gpu_tensor(b, 'frequency_loss input b')
+    loss = _FreqLoss.apply(a, b, (n, c, h, w, crop, int(bool(luma)), FREQ_KINDS[kind], float(eps), float(alpha)))
+    return loss.mean() if reduction == 'mean' else loss
+
+
+def fft_l1_loss(a, b, crop_border=0, luma=False, reduction='mean'):
+    """``mean |rfft2(a) - rfft2(b)|`` over real and imaginary parts per image -> ``frequency_loss`` with ``kind='l1'``"""
+    return frequency_loss(a, b, kind='l1', crop_border=crop_border, luma=luma, reduction=reduction)
+
+
+def focal_frequency_loss(a, b, alpha=1.0, crop_border=0, luma=False, reduction='mean'):
+    """the focal frequency loss per image -> ``frequency_loss`` with ``kind='focal'``"""
+    return frequency_loss(a, b, kind='focal', alpha=alpha, crop_border=crop_border, luma=luma, reduction=reduction)
 
 
 class _BCE(torch.autograd.Function):
