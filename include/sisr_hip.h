@@ -733,6 +733,61 @@ int sisr_degrade_fwd(const float *x, const float *kernels, const float *noise_si
 int sisr_degrade_bwd(const float *dy, const float *y_saved, const float *kernels, float *dx, int32_t N, int32_t C, int32_t H,
                      int32_t W, int32_t K, int32_t h, int32_t w, void *stream);
 
+/* ---- second-order degradation: a draw from seven kernel families with a noise row and a final sinc filter
+ *      per sample, and the noise operator.  The blur and the resampling are sisr_degrade_fwd / sisr_degrade_bwd with these kernels.
+ *      An event of probability p happens when u <= p (u in (0, 1]: p = 1 always, p = 0 never).  Draws of sample b at step t, from
+ *      counters {t low, t high, b, tag | rank}, u_i as above:
+ *        0xFE04  u0 blur on (blur_prob); off: the delta kernel, exactly 1 at the centre
+ *                u1 k_eff = ksize_min + 2 min((int)(m u1), m - 1), m = (K - ksize_min) / 2 + 1: uniform over the odd sizes in
+ *                   ksize_min .. K; weights outside the centred k_eff x k_eff square are exactly 0
+ *                u2 family 6 = sinc (sinc_prob); u3 otherwise the first family i with kernel_probs[i] > 0 and
+ *                   u3 <= kernel_probs[0] + .. + kernel_probs[i] (fp32, added in index order): 0 iso, 1 aniso, 2 generalized_iso,
+ *                   3 generalized_aniso, 4 plateau_iso, 5 plateau_aniso
+ *        0xFE05  sigma1 = lo + (hi - lo) u0   sigma2 likewise from u1   theta = pi u2   (iso forms and sinc: sigma2 = sigma1, theta = 0)
+ *                beta = lo + (hi - lo) u3 in beta_g for families 2, 3, in beta_p for 4, 5; stored as 0 otherwise
+ *        0xFE06  omega = lo + (pi - lo) u0, lo = pi / 3 for k_eff < 13 and pi / 5 otherwise (sinc; stored as 0 otherwise)
+ *                u1 noise mode 1 = gaussian (gaussian_prob), else 2 = shot; 0 = none when noise_hi = shot_hi = 0
+ *                u2 grey flag (grey_prob)   amplitude = lo + (hi - lo) u3 in the mode's range
+ *        0xFE07  the final filter: u0 sinc (final_sinc_prob), else the delta kernel; u1 its k_eff, u2 its omega, as above
+ *      Unnormalised weight at (dy, dx), with u, v of the Gaussian draw above and q = u^2 / sigma1^2 + v^2 / sigma2^2 (fp32):
+ *        0, 1  exp(-q / 2)     2, 3  exp(-q^beta / 2)     4, 5  1 / (q^beta + 1)
+ *        6     omega J1(omega r) / (2 pi r), r = sqrt(dx^2 + dy^2), and omega^2 / (4 pi) at the centre -- in double, J1 from its
+ *              power series below 12 and Hankel's expansion above (1e-11), rounded to fp32; negative lobes are intended
+ *      divided by the sum of the K^2 weights in the fixed order of the Gaussian draw (lane partial sums, then the butterfly).
+ *      SISR_E_BADARG before any HIP call for null pointers (final_kernels may be NULL), B < 1, K even or outside 1..21, ksize_min
+ *      even or outside 1..K, a probability outside [0, 1], kernel_probs not summing to 1 within 1e-6, a reversed range, sigma or
+ *      beta lo <= 0, a negative noise bound, rank outside [0, 65536). ------------------------------------------------------------- */
+typedef struct SisrDegradeMix {
+    int32_t K, ksize_min;
+    float blur_prob, sinc_prob;
+    float kernel_probs[6];
+    float sigma_lo, sigma_hi, beta_g_lo, beta_g_hi, beta_p_lo, beta_p_hi;
+    float noise_lo, noise_hi, shot_lo, shot_hi;      /* amplitude ranges of the two noise modes */
+    float gaussian_prob, grey_prob, final_sinc_prob;
+} SisrDegradeMix;
+int sisr_degrade_mix_bytes(void);                    /* sizeof(SisrDegradeMix), for the Python mirror */
+/* One workgroup, the pattern of sisr_degrade_draw: t = *step_dev, *step_dev = t + 1, drawn_step_dev[0] = t.  kernels_dev [B][K][K],
+ * final_kernels_dev [B][K][K] or NULL, params_dev [B][8] = family, k_eff, sigma1, sigma2, theta, beta, omega, blur flag,
+ * noise_table_dev [B][4] = mode, grey flag, amplitude, 0. */
+int sisr_degrade_draw_mix(int64_t *step_dev, uint64_t seed, int32_t rank, int32_t B, const SisrDegradeMix *mix, float *kernels_dev,
+                          float *final_kernels_dev, float *params_dev, float *noise_table_dev, int64_t *drawn_step_dev, void *stream);
+/* HOST: the same text for step t >= 0 into host memory, no GPU involved. */
+int sisr_degrade_mix_host(int64_t t, uint64_t seed, int32_t rank, int32_t B, const SisrDegradeMix *mix, float *kernels_host,
+                          float *final_kernels_host, float *params_host, float *noise_table_host);
+/* y = clamp ? clamp(x + n, -1, 1) : x + n over x [N][C][h][w], C in 1..4, with the sample's row of noise_table [N][4]:
+ *   mode 0  n = 0      mode 1  n = a z      mode 2  n = (a / 8) sqrt(clip((v + 1) / 2, 0, 1)) z   (shot noise: the Gaussian
+ *   approximation of Poisson noise at 256 levels with scale a, in [-1, 1] units)
+ *   colour (grey flag 0): v the element, z of its flat index e, the stream of sisr_degrade_fwd (tag 0xFE02);
+ *   grey: v the pixel's luma (C = 3: 0.299 R + 0.587 G + 0.114 B, otherwise the channel mean), ONE z per pixel from its flat index
+ *   over [N][h][w] under tag 0xFE08, the same n in every channel.
+ * The step is read from *step_dev.  One thread per pixel, grid-stride.  N C h w >= 2^34: SISR_E_TOOBIG. */
+int sisr_degrade_noise_fwd(const float *x, const float *noise_table, const int64_t *step_dev, uint64_t seed, int32_t rank, float *y,
+                           int32_t N, int32_t C, int32_t h, int32_t w, int32_t clamp, void *stream);
+/* dx = dy [-1 < y_saved < 1] (NULL: dx = dy): n is a constant under autograd, for shot noise too. */
+int sisr_degrade_noise_bwd(const float *dy, const float *y_saved, float *dx, int32_t N, int32_t C, int32_t h, int32_t w, void *stream);
+/* HOST: z of pixels first .. first + count - 1 of the grey stream at step t, no GPU involved */
+int sisr_degrade_noise_grey_host(int64_t t, uint64_t seed, int32_t rank, int64_t first, int64_t count, float *z_host);
+
 /* ---- differentiable JPEG round trip: y = J(x), x and y [N][C][H][W] fp32, C in {1, 3}, any H, W >= 1;
  *      tables [N][2][64] fp32 (luma, chroma; row-major 8 x 8, entries > 0).  All arithmetic of the forward in fp32:
  *         1. p = (x + 1) 127.5 -- no rounding to 8 bits, no clamp of the input

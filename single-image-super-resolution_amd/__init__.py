@@ -20,7 +20,8 @@ def install(fused_adam=False, fused_losses=False, degradation=None):
     instantiates) at the fused multi-tensor Adam of ``optim.py``; ``fused_losses=True`` points ``torch.nn.BCELoss`` (what
     config.py:107 instantiates) at the fused ``losses.BCELoss``; ``degradation=`` a ``degrade.Degrader`` makes the patched
     ``utils.lr_from_hr`` that object's method -- a blur kernel and a noise level drawn per sample and per call
-    -- instead of the bicubic kernel (``Degrader(jpeg=(qlo, qhi))`` appends the JPEG round trip of ``jpeg.py``, DESIGN.md section 20);
+    -- instead of the bicubic kernel (``Degrader(jpeg=(qlo, qhi))`` appends the JPEG round trip of ``jpeg.py``, DESIGN.md section 20;
+    a ``degrade.HighOrderDegrader`` is taken the same way: Real-ESRGAN's second-order model, DESIGN.md section 25);
     the default None leaves the bicubic path as it is."""
     import importlib
     import sys

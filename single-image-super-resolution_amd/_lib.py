@@ -115,6 +115,12 @@ class ImageRec(C.Structure):
     _fields_ = [('offset', _i64), ('H', _i32), ('W', _i32)]
 
 
+class DegradeMix(C.Structure):
+    _fields_ = ([('K', _i32), ('ksize_min', _i32), ('blur_prob', _f32), ('sinc_prob', _f32), ('kernel_probs', _f32 * 6)] +
+                [(n, _f32) for n in ('sigma_lo', 'sigma_hi', 'beta_g_lo', 'beta_g_hi', 'beta_p_lo', 'beta_p_hi', 'noise_lo', 'noise_hi',
+                                     'shot_lo', 'shot_hi', 'gaussian_prob', 'grey_prob', 'final_sinc_prob')])
+
+
 class BnBwdDesc(C.Structure):
     _fields_ = ([(n, _f) for n in ('dy', 'x', 'scale', 'shift', 'mean', 'invstd', 'gamma', 'work',
                                    'qa', 'qb', 'qd', 'dgamma', 'dbeta', 'dslope')] +
@@ -231,6 +237,12 @@ _SIGS = {
     'sisr_degrade_noise_host': [_i64, C.c_uint64, _i32, _i64, _i64, _f],
     'sisr_degrade_fwd': [_f, _f, _f, _f, C.c_uint64, _i32, _f] + [_i32] * 8 + [_f],
     'sisr_degrade_bwd': [_f, _f, _f, _f] + [_i32] * 7 + [_f],
+    'sisr_degrade_mix_bytes': [],
+    'sisr_degrade_draw_mix': [_f, C.c_uint64, _i32, _i32, C.POINTER(DegradeMix), _f, _f, _f, _f, _f, _f],
+    'sisr_degrade_mix_host': [_i64, C.c_uint64, _i32, _i32, C.POINTER(DegradeMix), _f, _f, _f, _f],
+    'sisr_degrade_noise_fwd': [_f, _f, _f, C.c_uint64, _i32, _f] + [_i32] * 5 + [_f],
+    'sisr_degrade_noise_bwd': [_f, _f, _f] + [_i32] * 4 + [_f],
+    'sisr_degrade_noise_grey_host': [_i64, C.c_uint64, _i32, _i64, _i64, _f],
     'sisr_jpeg_tables': [_f, C.c_uint64, _i32, _i32, _i32, _i32, _f, _f, _f],
     'sisr_jpeg_tables_host': [_i64, C.c_uint64, _i32, _i32, _i32, _i32, _f, _f],
     'sisr_jpeg_fwd': [_f, _f, _f] + [_i32] * 6 + [_f],
@@ -306,6 +318,8 @@ def lib():
                            % (list(sizes[:9]), mine))
     if L.sisr_toimage_bwd_desc_bytes() != C.sizeof(ToImageBwdDesc):
         raise RuntimeError('libsisr_hip.so does not match the Python mirror of SisrToImageBwdDesc')
+    if L.sisr_degrade_mix_bytes() != C.sizeof(DegradeMix):
+        raise RuntimeError('libsisr_hip.so does not match the Python mirror of SisrDegradeMix')
     _lib = L
     return L
 

@@ -11,6 +11,11 @@ own -- and a generator trained against bicubic alone is known to fail on images 
 
 ``degrade`` is the operator with the kernels given; ``gaussian_kernels`` builds fixed ones; ``expected_params`` / ``expected_noise``
 restate a step's draws on the host (no GPU) for audits and tests.
+
+>>> d = HighOrderDegrader(mid_size=(136, 136), seed=1)  # Real-ESRGAN's two stages: seven kernel families, shot noise, JPEG, sinc
+
+The second-order model is at the end of the file: ``DegradeStage`` / ``realesrgan_stages``,
+``degrade_noise``, ``expected_mix`` and ``HighOrderDegrader``.
 """
 import ctypes as C
 import math
@@ -136,12 +141,13 @@ def expected_params(seed, t, B, ksize, sigma=(0.2, 3.0), anisotropic=True, noise
     return k, s, p
 
 
-def expected_noise(seed, t, first, count, rank=0):
+def expected_noise(seed, t, first, count, rank=0, grey=False):
     """Host, no GPU (sisr_degrade_noise_host): z of output elements ``first`` .. ``first + count - 1`` (flat over [N, C, h, w]) at
-    step ``t`` -> float32 numpy array [count]."""
+    step ``t`` -> float32 numpy array [count].  ``grey=True``: the stream of ``degrade_noise``'s grey mode, one z per PIXEL (flat
+    over [N, h, w]; sisr_degrade_noise_grey_host)."""
     z = np.zeros(int(count), np.float32)
-    L.check(L.lib().sisr_degrade_noise_host(int(t), int(seed), int(rank), int(first), int(count), z.ctypes.data_as(C.c_void_p)),
-            'sisr_degrade_noise_host')
+    fn = 'sisr_degrade_noise_grey_host' if grey else 'sisr_degrade_noise_host'
+    L.check(getattr(L.lib(), fn)(int(t), int(seed), int(rank), int(first), int(count), z.ctypes.data_as(C.c_void_p)), fn)
     return z
 
 
@@ -237,3 +243,278 @@ class Degrader:
             raise ValueError('Degrader.load_state_dict: seed must be in [0, 2^64) and rank in [0, %d), got %d, %d' % (RANK_LIMIT, seed, rank))
         self.step.copy_(torch.as_tensor(state['step'], dtype=torch.int64).reshape(()))
         self.seed, self.rank = seed, rank
+
+
+# ---- second-order degradation ------------------------------------------------------------------------------
+FAMILIES = ('iso', 'aniso', 'generalized_iso', 'generalized_aniso', 'plateau_iso', 'plateau_aniso', 'sinc')
+NOISE_MODES = ('none', 'gaussian', 'shot')
+
+
+def _check_prob(p, who, name):
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError('%s: %s must be a probability in [0, 1], got %g' % (who, name, p))
+    return p
+
+
+def _check_range(r, who, name, positive):
+    lo, hi = float(r[0]), float(r[1])
+    if not ((0.0 < lo if positive else 0.0 <= lo) and lo <= hi < math.inf):
+        raise ValueError('%s: %s = (lo, hi) needs %s lo <= hi, got (%g, %g)' % (who, name, '0 <' if positive else '0 <=', lo, hi))
+    return lo, hi
+
+
+class DegradeStage:
+    """The settings of one stage of ``HighOrderDegrader``: the blur kernel is drawn from seven families, the noise is Gaussian or
+    shot noise, colour or grey, and the stage may end with a JPEG round trip.
+
+    ``ksize, ksize_min``   the kernel table is ksize x ksize (odd, <= 21); the drawn kernel occupies a centred square whose odd side
+                           is uniform in ksize_min .. ksize, the rest of the table is 0.
+    ``blur_prob``          the probability of blurring at all (otherwise the delta kernel).
+    ``sinc_prob``          the probability of the sinc family; otherwise ``kernel_probs`` picks among iso, aniso, generalized_iso,
+                           generalized_aniso, plateau_iso, plateau_aniso (six values >= 0 that sum to 1).
+    ``sigma``              both standard deviations are uniform in it; ``beta_gaussian`` / ``beta_plateau`` likewise for the shape.
+    ``noise, shot``        amplitude ranges of the two noise modes in [-1, 1] units (``shot``: Real-ESRGAN's poisson_scale);
+                           Gaussian with probability ``gaussian_prob``, grey with ``grey_prob``; both (0, 0): no noise.
+    ``jpeg``               None or (qlo, qhi)."""
+
+    def __init__(self, ksize=21, ksize_min=7, blur_prob=1.0, kernel_probs=(0.45, 0.25, 0.12, 0.03, 0.12, 0.03), sinc_prob=0.1,
+                 sigma=(0.2, 3.0), beta_gaussian=(0.5, 4.0), beta_plateau=(1.0, 2.0), noise=(0., 0.), shot=(0., 0.), gaussian_prob=0.5,
+                 grey_prob=0.4, jpeg=None):
+        who = 'DegradeStage'
+        self.ksize, self.ksize_min = _check_ksize(ksize, who), int(ksize_min)
+        if not 1 <= self.ksize_min <= self.ksize or self.ksize_min % 2 == 0:
+            raise ValueError('%s: ksize_min must be odd and in [1, ksize = %d], got %d' % (who, self.ksize, self.ksize_min))
+        self.blur_prob, self.sinc_prob = _check_prob(blur_prob, who, 'blur_prob'), _check_prob(sinc_prob, who, 'sinc_prob')
+        self.gaussian_prob, self.grey_prob = _check_prob(gaussian_prob, who, 'gaussian_prob'), _check_prob(grey_prob, who, 'grey_prob')
+        self.kernel_probs = tuple(float(p) for p in kernel_probs)
+        if len(self.kernel_probs) != 6 or min(self.kernel_probs) < 0 or abs(sum(self.kernel_probs) - 1.0) > 1e-6:
+            raise ValueError('%s: kernel_probs must be six values >= 0 that sum to 1, got %s' % (who, self.kernel_probs))
+        self.sigma = _check_range(sigma, who, 'sigma', True)
+        self.beta_gaussian = _check_range(beta_gaussian, who, 'beta_gaussian', True)
+        self.beta_plateau = _check_range(beta_plateau, who, 'beta_plateau', True)
+        self.noise, self.shot = _check_range(noise, who, 'noise', False), _check_range(shot, who, 'shot', False)
+        self.jpeg = None
+        if jpeg is not None:
+            qlo, qhi = int(jpeg[0]), int(jpeg[1])
+            if not 1 <= qlo <= qhi <= 100:
+                raise ValueError('%s: jpeg = (qlo, qhi) needs 1 <= qlo <= qhi <= 100, got (%d, %d)' % (who, qlo, qhi))
+            self.jpeg = (qlo, qhi)
+
+    def c_struct(self, final_sinc_prob=None):
+        """the settings as sisr_hip.h's SisrDegradeMix"""
+        fp = 0.0 if final_sinc_prob is None else _check_prob(final_sinc_prob, 'DegradeStage', 'final_sinc_prob')
+        return L.DegradeMix(self.ksize, self.ksize_min, self.blur_prob, self.sinc_prob, (C.c_float * 6)(*self.kernel_probs), *self.sigma,
+                            *self.beta_gaussian, *self.beta_plateau, *self.noise, *self.shot, self.gaussian_prob, self.grey_prob, fp)
+
+
+def realesrgan_stages():
+    """The two published stages of Real-ESRGAN's second-order model in this package's units: noise 1-30 / 1-25 of 255 (times 2 for
+    the [-1, 1] range), poisson_scale 0.05-3 / 0.05-2.5, JPEG quality 30-95, blur probability 1.0 / 0.8, sigma (0.2, 3) / (0.2, 1.5)."""
+    return (DegradeStage(blur_prob=1.0, sigma=(0.2, 3.0), noise=(2 / 255., 60 / 255.), shot=(0.05, 3.0), jpeg=(30, 95)),
+            DegradeStage(blur_prob=0.8, sigma=(0.2, 1.5), noise=(2 / 255., 50 / 255.), shot=(0.05, 2.5), jpeg=(30, 95)))
+
+
+def expected_mix(seed, t, B, stage, rank=0, final_sinc_prob=None):
+    """Host, no GPU (sisr_degrade_mix_host: the device code's own text compiled for the host): the mixed draw of step ``t`` ->
+    (kernels [B, K, K], final_kernels [B, K, K] or None, params [B, 8] = family, k_eff, sigma1, sigma2, theta, beta, omega, blur
+    flag, noise_table [B, 4] = mode, grey flag, amplitude, 0), float32 numpy arrays.  ``final_sinc_prob=None``: no final filter."""
+    B, K = int(B), stage.ksize
+    if B < 1 or int(t) < 0:
+        raise ValueError('expected_mix: B must be >= 1 and t >= 0, got %d, %d' % (B, int(t)))
+    mix = stage.c_struct(final_sinc_prob)
+    k, p, nt = np.zeros((B, K, K), np.float32), np.zeros((B, 8), np.float32), np.zeros((B, 4), np.float32)
+    fk = None if final_sinc_prob is None else np.zeros((B, K, K), np.float32)
+    L.check(L.lib().sisr_degrade_mix_host(int(t), int(seed), int(rank), B, C.byref(mix), k.ctypes.data_as(C.c_void_p),
+                                          None if fk is None else fk.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p),
+                                          nt.ctypes.data_as(C.c_void_p)), 'sisr_degrade_mix_host')
+    return k, fk, p, nt
+
+
+class _DegradeNoise(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, table, step, seed, rank, clamp):
+        n, c, h, w = x.shape
+        y = torch.empty_like(x)
+        L.check(L.lib().sisr_degrade_noise_fwd(x.data_ptr(), table.data_ptr(), step.data_ptr(), seed, rank, y.data_ptr(), n, c, h, w,
+                                               int(clamp), _stream()), 'sisr_degrade_noise_fwd')
+        ctx.shape, ctx.clamp = (n, c, h, w), clamp
+        ctx.save_for_backward(*((y,) if clamp else ()))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        yc = ctx.saved_tensors[0] if ctx.clamp else None
+        dx = torch.empty_like(dy)
+        L.check(L.lib().sisr_degrade_noise_bwd(dy.data_ptr(), None if yc is None else yc.data_ptr(), dx.data_ptr(), *ctx.shape,
+                                               _stream()), 'sisr_degrade_noise_bwd')
+        return (dx,) + (None,) * 5
+
+
+def degrade_noise(x, noise_table, step, seed=0, rank=0, clamp=True):
+    """``clamp(x + n)`` over x [N, C, h, w] fp32 on the device, C in 1..4, with the noise of each sample's row of ``noise_table``
+    [N, 4] = (mode, grey flag, amplitude a, 0):
+
+    mode 0 ``none`` n = 0;  1 ``gaussian`` n = a z;  2 ``shot`` n = (a / 8) sqrt(clip((v + 1) / 2, 0, 1)) z -- the Gaussian
+    approximation of Poisson noise at 256 levels with Real-ESRGAN's ``poisson_scale`` a.  Colour noise: v is the element and z the
+    stream ``expected_noise`` restates; grey noise: v is the pixel's luma (C = 3: BT.601, otherwise the channel mean), one z per
+    pixel (``expected_noise(grey=True)``) and the same n in every channel.  ``step`` as in ``degrade``.  n is a constant under
+    autograd, for shot noise too: the gradient is ``dy`` where the output lies strictly inside (-1, 1)."""
+    require_gpu_tensor(x, 'degrade_noise input')
+    if x.dim() != 4 or not 1 <= x.shape[1] <= 4 or x.dtype != torch.float32:
+        raise ValueError('degrade_noise: an fp32 [N, C, h, w] batch with 1 to 4 channels is expected, got %s %s' % (x.dtype, tuple(x.shape)))
+    x = x.contiguous()
+    n = x.shape[0]
+    seed, rank = int(seed), int(rank)
+    if not 0 <= seed < 1 << 64 or not 0 <= rank < RANK_LIMIT:
+        raise ValueError('degrade_noise: seed must be in [0, 2^64) and rank in [0, %d), got %d, %d' % (RANK_LIMIT, seed, rank))
+    table = torch.as_tensor(noise_table).to(device=x.device, dtype=torch.float32).contiguous()
+    if tuple(table.shape) != (n, 4):
+        raise ValueError('degrade_noise: noise_table must be [N = %d, 4], got %s' % (n, tuple(table.shape)))
+    if not (isinstance(step, torch.Tensor) and step.is_cuda and step.dtype == torch.int64 and step.numel() == 1):
+        step = torch.full((), 0 if step is None else int(step), dtype=torch.int64, device=x.device)
+    return _DegradeNoise.apply(x, table, step, seed, rank, bool(clamp))
+
+
+class HighOrderDegrader:
+    """The second-order degradation of Real-ESRGAN on the device: every stage draws a blur kernel from seven families, resamples,
+    adds Gaussian or shot noise and compresses; the last stage also runs a sinc filter (ringing and overshoot).
+
+    >>> d = HighOrderDegrader(seed=1)                         # the two published stages
+    >>> img_lr = d(img_hr, (48, 48))                          # differentiable in img_hr; nothing is read back
+    >>> sisr.install(degradation=d)
+
+    Per stage, in this order: ``draw_mix`` (sisr_degrade_draw_mix: ``step`` advances by ONE per stage, so the noise and JPEG-quality
+    streams, keyed by the step, are independent between stages), sisr_jpeg_tables on the drawn step if the stage compresses,
+    ``degrade(x, size, kernels, None, clamp=False)``, ``degrade_noise(..., clamp=True)``, ``jpeg_roundtrip``.
+
+    ``stages``           ``DegradeStage`` records.  Every stage but the last resamples to the middle size, the last to
+                         ``image_size_lr``.
+    ``mid_size``         a fixed middle size (h, w): nothing is read back and the call is capturable (graph.GraphedStep).
+    ``mid_scale``        (lo, hi): the middle size is the HR size times a factor drawn on the HOST per call from
+                         ``numpy.random.default_rng((seed, rank, calls))``; shapes change from call to call, a call under stream
+                         capture raises.  Neither given: the rounded geometric mean of the HR and LR sizes.
+    ``final_sinc_prob``  the probability that the sample's final filter is a sinc kernel (otherwise the delta kernel); None: no
+                         final filter.  The filter is ``degrade`` at equal sizes, where the cubic taps are exactly (0, 1, 0, 0): a pure
+                         blur, clamped.  ``final_order``: 'sinc_jpeg' filters before the last stage's JPEG round trip, 'jpeg_sinc' after.
+    ``last_*``           the latest call's tables, one entry per stage: ``last_kernels``, ``last_params``, ``last_noise_table``,
+                         ``last_drawn_step``, ``last_tables`` / ``last_quality`` (None without JPEG), ``last_sizes``; and
+                         ``last_final_kernels``.  ``step``: the 0-dim int64 device tensor of draws made so far."""
+
+    def __init__(self, stages=None, mid_size=None, mid_scale=None, final_sinc_prob=0.8, final_order='sinc_jpeg', seed=0, rank=0,
+                 device=None, jpeg_subsampling='420', jpeg_grad='ste'):
+        from . import jpeg as J
+        who = 'HighOrderDegrader'
+        self.stages = tuple(realesrgan_stages() if stages is None else stages)
+        if not self.stages or not all(isinstance(s, DegradeStage) for s in self.stages):
+            raise ValueError('%s: stages must be a non-empty sequence of DegradeStage' % who)
+        if mid_size is not None and mid_scale is not None:
+            raise ValueError('%s: give mid_size or mid_scale, not both' % who)
+        self.mid_size = None
+        if mid_size is not None:
+            self.mid_size = (int(mid_size[0]), int(mid_size[1]))
+            if min(self.mid_size) < 1:
+                raise ValueError('%s: mid_size must be >= 1, got %s' % (who, self.mid_size))
+        self.mid_scale = None if mid_scale is None else _check_range(mid_scale, who, 'mid_scale', True)
+        self.final_sinc_prob = None if final_sinc_prob is None else _check_prob(final_sinc_prob, who, 'final_sinc_prob')
+        if final_order not in ('sinc_jpeg', 'jpeg_sinc'):
+            raise ValueError("%s: final_order is 'sinc_jpeg' or 'jpeg_sinc', got %r" % (who, final_order))
+        if jpeg_subsampling not in J.SUBSAMPLING or jpeg_grad not in J.GRAD:
+            raise ValueError("%s: jpeg_subsampling is '444' or '420' and jpeg_grad 'ste' or 'cubic', got %r, %r"
+                             % (who, jpeg_subsampling, jpeg_grad))
+        self.final_order, self.jpeg_subsampling, self.jpeg_grad = final_order, jpeg_subsampling, jpeg_grad
+        self.seed, self.rank = int(seed), int(rank)
+        if not 0 <= self.seed < 1 << 64 or not 0 <= self.rank < RANK_LIMIT:
+            raise ValueError('%s: seed must be in [0, 2^64) and rank in [0, %d), got %d, %d' % (who, RANK_LIMIT, self.seed, self.rank))
+        dev = torch.device('cuda' if device is None else device)
+        if dev.type != 'cuda':
+            raise RuntimeError('%s: the draws live on the MI355X (got device %s); there is no CPU fallback' % (who, dev))
+        self.step = torch.zeros((), dtype=torch.int64, device=dev)
+        self.calls = 0
+        self._mix = [s.c_struct(self.final_sinc_prob if i == len(self.stages) - 1 else None) for i, s in enumerate(self.stages)]
+        none = [None] * len(self.stages)
+        self.last_kernels, self.last_params, self.last_noise_table, self.last_drawn_step = list(none), list(none), list(none), list(none)
+        self.last_tables, self.last_quality, self.last_sizes, self.last_final_kernels = list(none), list(none), list(none), None
+
+    def draw_mix(self, i, n):
+        """the tables of the next step for stage ``i`` and a batch of ``n``: -> (kernels, final_kernels or None, params, noise_table,
+        drawn_step) on the device; advances ``step``"""
+        dev, K = self.step.device, self.stages[i].ksize
+        final = i == len(self.stages) - 1 and self.final_sinc_prob is not None
+        k = torch.empty((n, K, K), dtype=torch.float32, device=dev)
+        fk = torch.empty((n, K, K), dtype=torch.float32, device=dev) if final else None
+        p = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        nt = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        t = torch.empty((), dtype=torch.int64, device=dev)
+        L.check(L.lib().sisr_degrade_draw_mix(self.step.data_ptr(), self.seed, self.rank, n, C.byref(self._mix[i]), k.data_ptr(),
+                                              None if fk is None else fk.data_ptr(), p.data_ptr(), nt.data_ptr(), t.data_ptr(),
+                                              _stream()), 'sisr_degrade_draw_mix')
+        self.last_kernels[i], self.last_params[i], self.last_noise_table[i], self.last_drawn_step[i] = k, p, nt, t
+        if final:
+            self.last_final_kernels = fk
+        return k, fk, p, nt, t
+
+    def stage_sizes(self, size_hr, size_lr):
+        """the output size of every stage for this call (``mid_scale``: drawn on the host from the call count)"""
+        mid = self.mid_size
+        if len(self.stages) > 1 and mid is None:
+            if self.mid_scale is not None:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError('HighOrderDegrader: mid_scale draws a new size on the host per call and cannot be captured; '
+                                       'give a fixed mid_size')
+                s = float(np.random.default_rng((self.seed, self.rank, self.calls)).uniform(*self.mid_scale))
+                mid = tuple(max(1, int(round(v * s))) for v in size_hr)
+            else:
+                mid = tuple(max(1, int(round(math.sqrt(a * b)))) for a, b in zip(size_hr, size_lr))
+        return [mid] * (len(self.stages) - 1) + [size_lr]
+
+    def __call__(self, img_hr, image_size_lr):
+        from .jpeg import jpeg_roundtrip
+        require_gpu_tensor(img_hr, 'HighOrderDegrader input')
+        if img_hr.device != self.step.device:
+            raise RuntimeError('HighOrderDegrader: the batch is on %s, the draws on %s' % (img_hr.device, self.step.device))
+        if img_hr.dim() != 4 or img_hr.dtype != torch.float32:
+            raise ValueError('HighOrderDegrader: an fp32 [N, C, H, W] batch is expected, got %s %s' % (img_hr.dtype, tuple(img_hr.shape)))
+        n = int(img_hr.shape[0])
+        size_lr = (int(image_size_lr[0]), int(image_size_lr[1]))
+        sizes = self.stage_sizes((int(img_hr.shape[2]), int(img_hr.shape[3])), size_lr)
+        self.calls += 1
+        x = img_hr
+        for i, st in enumerate(self.stages):
+            k, fk, _, nt, t = self.draw_mix(i, n)
+            tables = None
+            if st.jpeg is not None:                                       # before the forward: the draws of a step stay together
+                q = torch.empty(n, dtype=torch.int32, device=x.device)
+                tables = torch.empty((n, 2, 8, 8), dtype=torch.float32, device=x.device)
+                L.check(L.lib().sisr_jpeg_tables(t.data_ptr(), self.seed, self.rank, n, st.jpeg[0], st.jpeg[1], q.data_ptr(),
+                                                 tables.data_ptr(), _stream()), 'sisr_jpeg_tables')
+                self.last_quality[i] = q
+            else:
+                self.last_quality[i] = None
+            self.last_tables[i], self.last_sizes[i] = tables, sizes[i]
+            x = degrade(x, sizes[i], k, None, clamp=False)
+            x = degrade_noise(x, nt, t, self.seed, self.rank, clamp=True)
+            if fk is not None and self.final_order == 'sinc_jpeg':
+                x = degrade(x, sizes[i], fk, None, clamp=True)
+            if tables is not None:
+                x = jpeg_roundtrip(x, tables, self.jpeg_subsampling, self.jpeg_grad, True)
+            if fk is not None and self.final_order == 'jpeg_sinc':
+                x = degrade(x, sizes[i], fk, None, clamp=True)
+        return x
+
+    def lr_from_hr(self, img_hr, image_size_lr, device='cpu'):
+        """the reference's signature (utils.py:22-31; ``device`` is accepted and unused, as in utils.lr_from_hr)"""
+        return self(img_hr, image_size_lr)
+
+    def state_dict(self):
+        return dict(seed=self.seed, rank=self.rank, step=self.step.clone(), calls=self.calls)
+
+    def load_state_dict(self, state):
+        """copies the count INTO the existing tensor (a captured draw points at it)"""
+        seed, rank = int(state['seed']), int(state['rank'])
+        if not 0 <= seed < 1 << 64 or not 0 <= rank < RANK_LIMIT:
+            raise ValueError('HighOrderDegrader.load_state_dict: seed must be in [0, 2^64) and rank in [0, %d), got %d, %d'
+                             % (RANK_LIMIT, seed, rank))
+        self.step.copy_(torch.as_tensor(state['step'], dtype=torch.int64).reshape(()))
+        self.seed, self.rank, self.calls = seed, rank, int(state.get('calls', 0))
