@@ -981,6 +981,38 @@ int sisr_freq_loss_bwd(const float *spec, const float *pmax, const float *g, int
                        int32_t crop, int32_t luma, int32_t kind, float eps, float alpha, float *work, float *da, float *db,
                        void *stream);
 
+/* ---- separable Gaussian filter with a mirrored border, forward and backward, and the unsharp mask on it.
+ *      Tensors are fp32 [N][C][H][W], contiguous; `planes` = N C.  K odd, 1 .. SISR_GAUSS_MAX_K, R = K / 2:
+ *          y[i][j] = sum_{a, b} t[a] t[b] x[m(i + a - R)][m(j + b - R)],  m(p) = -p below 0, 2 (L - 1) - p from L on
+ *      (torch's 'reflect', OpenCV's BORDER_REFLECT_101: the edge pixel is not repeated).  The mirror needs H > R and W > R: smaller
+ *      planes return SISR_E_UNSUPPORTED.  SISR_E_BADARG before any HIP call for null pointers, K even or outside
+ *      1 .. SISR_GAUSS_MAX_K, sizes < 1, an output whose bytes overlap an input's or another output's (checked on the byte ranges:
+ *      the tiles read their neighbours' pixels), lo >= hi or settings that are not finite; SISR_E_TOOBIG for H W or the workgroup
+ *      count (planes times the 32 x 64 tiles of a plane) above INT32_MAX.  One launch per filter, LDS only between the two passes,
+ *      fixed summation order, no atomics, plain vector stores: the same bits on every call, and nothing is read back by the host.
+ *      A non-finite input value reaches the outputs inside the filter's support and no others (a term outside it is 0 x 0, never 0 times
+ *      the value). --------------------------------------------------------------------------------------------------------- */
+#define SISR_GAUSS_MAX_K 63
+/* HOST: t_i = exp(-(i - (K - 1) / 2)^2 / (2 sigma^2)) / sum, evaluated and normalised in double, rounded once.  sigma <= 0: OpenCV's
+ * rule sigma = 0.3 ((K - 1) / 2 - 1) + 0.8 (8.0 at K = 51) -- with the FORMULA for every K: OpenCV's tabulated kernels for K <= 7 are
+ * not reproduced.  taps_host: K floats of host memory */
+int sisr_gauss_taps_host(int32_t K, float sigma, float *taps_host);
+/* taps_dev: K floats in device memory (any K taps: nothing below assumes they are symmetric or sum to 1) */
+int sisr_gauss_blur_fwd(const float *x, const float *taps_dev, float *y, int64_t planes, int32_t H, int32_t W, int32_t K,
+                        void *stream);
+/* dx = G^T dy, the exact transpose of the forward, in gather form */
+int sisr_gauss_blur_bwd(const float *dy, const float *taps_dev, float *dx, int64_t planes, int32_t H, int32_t W, int32_t K,
+                        void *stream);
+/* HOST: bytes of the unsharp mask's workspace, one float and one byte per element; < 0: a status code */
+int64_t sisr_usm_ws_bytes(int64_t planes, int32_t H, int32_t W);
+/* Real-ESRGAN's USMSharp with s = 255 / (hi - lo):  blur = G x;  res = x - blur;  mask = |res| s > threshold (bytes 0 / 1);
+ * soft = G mask;  sharp = min(max(x + weight res, lo), hi);  y = x + soft (sharp - x) -- that recipe's soft sharp + (1 - soft) x,
+ * written so that weight = 0 or an all-zero mask returns x bit for bit.  Two launches: the first leaves blur and the mask in ws,
+ * the second filters the mask and combines.  mask_out: [N][C][H][W] bytes, or NULL.  y, ws and mask_out share no byte with x, the
+ * taps or each other (SISR_E_BADARG) */
+int sisr_usm_fwd(const float *x, const float *taps_dev, int32_t K, float weight, float threshold, float lo, float hi, void *ws,
+                 float *y, uint8_t *mask_out, int64_t planes, int32_t H, int32_t W, void *stream);
+
 /* ---- misc---------------------------------------------------------------------------------- */
 /* ---- optimizer: fused multi-tensor Adam --------------------------------------------------
  * One launch performs torch.optim.Adam's update (amsgrad=False, maximize=False; config.py:292-294, stepped at

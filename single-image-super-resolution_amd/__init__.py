@@ -8,6 +8,16 @@ reference's own module names; ``install()`` additionally patches ``utils.lr_from
 """
 from . import _lib  # noqa: F401
 
+_FILTERS = ('gaussian_taps', 'gaussian_blur', 'usm_sharpen', 'USMSharp')      # filters.py
+
+
+def __getattr__(name):
+    """the public names of ``filters`` under the package's own name, resolved on first use (importing the package stays light)"""
+    if name in _FILTERS:
+        import importlib
+        return getattr(importlib.import_module('.filters', __name__), name)
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))
+
 
 def install(fused_adam=False, fused_losses=False, degradation=None):
     """Register this package's model modules under the reference's top-level module names, so the

@@ -21,6 +21,7 @@ JPEG_GRAD_STE, JPEG_GRAD_CUBIC = range(2)
 PIX_L1, PIX_CHARBONNIER, PIX_MSE = range(3)  # pix_kind of sisr_image_loss_fwd / sisr_image_loss_bwd
 FREQ_L1, FREQ_CHARBONNIER, FREQ_FOCAL = range(3)   # kind of sisr_freq_loss_fwd / sisr_freq_loss_bwd
 FREQ_MAX_SIDE = 256                          # SISR_FREQ_MAX_SIDE: the longest view side the DFT kernels take
+GAUSS_MAX_K = 63                             # SISR_GAUSS_MAX_K: the longest filter of sisr_gauss_blur_* / sisr_usm_fwd
 ROUTE_GENERIC, ROUTE_DEEP, ROUTE_TOIMAGE, ROUTE_TRUNK, ROUTE_THIN = range(5)      # enum SisrRoute: what the sisr_*_route calls answer
 
 _f = C.c_void_p      # device pointers travel as void*
@@ -268,6 +269,11 @@ _SIGS = {
     'sisr_freq_loss_ws_floats': [_i32] * 7,
     'sisr_freq_loss_fwd': [_f, _f] + [_i32] * 7 + [_f32, _f32, _f, _f, _f, _f, _f],
     'sisr_freq_loss_bwd': [_f, _f, _f] + [_i32] * 7 + [_f32, _f32, _f, _f, _f, _f],
+    'sisr_gauss_taps_host': [_i32, _f32, _f],
+    'sisr_gauss_blur_fwd': [_f, _f, _f, _i64, _i32, _i32, _i32, _f],
+    'sisr_gauss_blur_bwd': [_f, _f, _f, _i64, _i32, _i32, _i32, _f],
+    'sisr_usm_ws_bytes': [_i64, _i32, _i32],
+    'sisr_usm_fwd': [_f, _f, _i32, _f32, _f32, _f32, _f32, _f, _f, _f, _i64, _i32, _i32, _f],
     'sisr_struct_sizes': [C.POINTER(_i32), _i32],
     'sisr_device_info': [C.POINTER(_i32), C.POINTER(_i32), C.c_char_p, _i32],
     'sisr_mfma_selftest': [_f, _f],
@@ -307,6 +313,7 @@ def lib():
     L.sisr_adam_norm_ws_doubles.restype = C.c_int64
     L.sisr_wgrad_bf16_slab_lead.restype = C.c_int64
     L.sisr_weight_image_bytes.restype = C.c_int64
+    L.sisr_usm_ws_bytes.restype = C.c_int64
     L.sisr_version.restype = C.c_char_p
     L.sisr_version.argtypes = []
     sizes = (_i32 * 9)()
