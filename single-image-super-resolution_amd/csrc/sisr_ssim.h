@@ -1,5 +1,6 @@
 // sisr_ssim.h -- the forward SSIM tile scheme, once, for its two callers: the metric (metrics.hip) and the image loss
-// (image_loss.hip).  Per image of two fp32 NCHW batches, on a view applied while staging and never materialised (`crop` pixels
+// (image_loss.hip); the geometry, the window, the constants and the workgroup decode also serve MS-SSIM (ms_ssim.hip) and the
+// backward scheme (sisr_ssim_bwd.h).  Per image of two fp32 NCHW batches, on a view applied while staging and never materialised (`crop` pixels
 // stripped from each side: H' = H - 2 crop, W' = W - 2 crop; for C == 3 with `luma` the BT.601 full-range plane
 // Y = 0.299 R + 0.587 G + 0.114 B in place of the three planes, C' = 1):
 //   SSIM[n] = mean over C' and the (H' - 10) x (W' - 10) "valid" window positions of
@@ -16,10 +17,10 @@
 // ssim_fold_image adds an image's partials in a fixed order in double.  No atomics: the results are the same bits every call.
 // LDS: 2 x 26 x 42 staged pixels + 5 x 26 x 32 row-filtered moments + 8 floats = 25.4 KB per workgroup.
 //
-// Rounding: this header is compiled under the compiler's default contraction, and both callers get the same instructions from it:
-// the SSIM of the loss is the metric's bit for bit.  image_loss.hip therefore includes it BEFORE its contract-off pragma; the
-// backward kernel there keeps a row pass of its own (il_row_moments) under that pragma, because its three instantiations must
-// round every product as written for da to be the same bits whether or not db is asked for.
+// Rounding: this header is compiled under the compiler's default contraction, and every caller gets the same instructions from it:
+// the SSIM of the loss is the metric's bit for bit.  The backward scheme (sisr_ssim_bwd.h) includes this header FIRST and only
+// then switches contraction off for itself and for the rest of the including file; it keeps a row pass of its own under that
+// pragma, because its instantiations must round every product as written for da to be the same bits whether or not db is asked for.
 #pragma once
 #include "sisr_dev.h"
 
@@ -82,6 +83,33 @@ static SsimWindow ssim_window() {
     }
     for (int k = 0; k < SSIM_WIN; ++k) win.w[k] = (float)(wd[k] / sum);
     return win;
+}
+
+// a workgroup of a flat grid over (image n, plane, tile row, tile column), in that order; base: the first element of the plane
+// (of plane 0 under luma)
+struct SsimTile {
+    int n, plane, ty, tx;
+    int64_t plane_elems, base;
+};
+
+__device__ __forceinline__ SsimTile ssim_tile(const SsimGeom& g, int tiles_y, int tiles_x) {
+    SsimTile t;
+    const int tiles = tiles_y * tiles_x, per_image = g.planes * tiles;
+    t.n = blockIdx.x / per_image;
+    const int r = blockIdx.x - t.n * per_image;
+    t.plane = r / tiles;
+    const int q = r - t.plane * tiles;
+    t.ty = q / tiles_x;
+    t.tx = q - t.ty * tiles_x;
+    t.plane_elems = (int64_t)g.H * g.W;
+    t.base = ((int64_t)t.n * g.C + (g.luma ? 0 : t.plane)) * t.plane_elems;
+    return t;
+}
+
+// C1 = (0.01 L)^2, C2 = (0.03 L)^2 as the kernels take them
+static void ssim_constants(double L, float& c1, float& c2) {
+    c1 = (float)(0.01 * L * 0.01 * L);
+    c2 = (float)(0.03 * L * 0.03 * L);
 }
 
 // workgroup = (image n, plane, tile row, tile column), flat in that order; part[workgroup][2] = (sum of SSIM values, sum of rho).
@@ -185,8 +213,10 @@ __device__ __forceinline__ void ssim_fold_image(const float* __restrict__ part, 
 template <int PIX, int APRON>
 static int ssim_launch_tiles(int ws_floats, hipStream_t st, const float* a, const float* b, const SsimGeom& g, double L, int do_ssim,
                              float eps2, float* work) {
+    float c1, c2;
+    ssim_constants(L, c1, c2);
     hipLaunchKernelGGL((ssim_tile_kernel<PIX, APRON>), dim3((unsigned)(ws_floats / 2)), dim3(SISR_BLOCK), 0, st, a, b, g,
-                       ssim_window(), (float)(0.01 * L * 0.01 * L), (float)(0.03 * L * 0.03 * L), do_ssim, eps2, work);
+                       ssim_window(), c1, c2, do_ssim, eps2, work);
     SISR_CHECK_LAUNCH();
     return 0;
 }

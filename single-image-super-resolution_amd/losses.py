@@ -59,6 +59,21 @@ def _scalar(dev):
     return torch.empty((), dtype=torch.float32, device=dev)
 
 
+def _check_reduction(reduction, what):
+    if reduction not in ('mean', 'none'):
+        raise ValueError("%s: reduction is 'mean' or 'none', got %r" % (what, reduction))
+
+
+def _ptr(t):
+    """the device address of an optional tensor, None (a null pointer) without one"""
+    return None if t is None else t.data_ptr()
+
+
+def _wanted_grads(ctx, shape, dev):
+    """(da, db): an uninitialised fp32 gradient for each of the first two inputs that needs one, else None"""
+    return tuple(torch.empty(shape, dtype=torch.float32, device=dev) if need else None for need in ctx.needs_input_grad[:2])
+
+
 class _FeatureMSE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, weight):
@@ -77,12 +92,10 @@ class _FeatureMSE(torch.autograd.Function):
     def backward(ctx, g):
         a, b = ctx.saved_tensors
         g = g.to(torch.float32).contiguous()
-        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
-        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        da, db = _wanted_grads(ctx, a.shape, a.device)
         if da is not None or db is not None:
             L.check(L.lib().sisr_mse_bwd(a.data_ptr(), b.data_ptr(), g.data_ptr(), a.numel(), ctx.weight,
-                                         None if da is None else da.data_ptr(), None if db is None else db.data_ptr(),
-                                         _stream()), 'sisr_mse_bwd')
+                                         _ptr(da), _ptr(db), _stream()), 'sisr_mse_bwd')
         return da, db, None
 
 
@@ -114,8 +127,7 @@ class _ImageLoss(torch.autograd.Function):
         ssim = torch.empty(n, dtype=torch.float32, device=dev) if want_parts else None
         pix = torch.empty(n, dtype=torch.float32, device=dev) if want_parts else None
         L.check(lib.sisr_image_loss_fwd(a.data_ptr(), b.data_ptr(), n, c, h, w, crop, luma, data_range, w_ssim, w_pix, kind, eps,
-                                        work.data_ptr(), loss.data_ptr(), None if ssim is None else ssim.data_ptr(),
-                                        None if pix is None else pix.data_ptr(), _stream()), 'sisr_image_loss_fwd')
+                                        work.data_ptr(), loss.data_ptr(), _ptr(ssim), _ptr(pix), _stream()), 'sisr_image_loss_fwd')
         ctx.save_for_backward(a, b)            # the inputs themselves: the backward recomputes the window moments
         ctx.cfg = cfg
         if want_parts:
@@ -127,13 +139,11 @@ class _ImageLoss(torch.autograd.Function):
     def backward(ctx, g, _g_ssim, _g_pix):
         a, b = ctx.saved_tensors
         n, c, h, w, crop, luma, data_range, w_ssim, w_pix, kind, eps = ctx.cfg
-        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
-        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        da, db = _wanted_grads(ctx, a.shape, a.device)
         if da is not None or db is not None:
             g = g.to(torch.float32).contiguous()
             L.check(L.lib().sisr_image_loss_bwd(a.data_ptr(), b.data_ptr(), g.data_ptr(), n, c, h, w, crop, luma, data_range,
-                                                w_ssim, w_pix, kind, eps, None if da is None else da.data_ptr(),
-                                                None if db is None else db.data_ptr(), _stream()), 'sisr_image_loss_bwd')
+                                                w_ssim, w_pix, kind, eps, _ptr(da), _ptr(db), _stream()), 'sisr_image_loss_bwd')
         return da, db, None, None
 
 
@@ -153,8 +163,7 @@ def image_loss(a, b, ssim_weight=0.0, pixel_weight=1.0, pixel='l1', eps=1e-3, da
     n, c, h, w = a.shape
     if pixel not in PIXEL_KINDS:
         raise ValueError('%s: pixel is one of %s, got %r' % (what, sorted(PIXEL_KINDS), pixel))
-    if reduction not in ('mean', 'none'):
-        raise ValueError("%s: reduction is 'mean' or 'none', got %r" % (what, reduction))
+    _check_reduction(reduction, what)
     if not float(eps) >= 0.0:
         raise ValueError('%s: eps must not be negative, got %r' % (what, eps))
     require_gpu_tensor(a, 'image_loss input a')
@@ -198,8 +207,7 @@ class _MsSsimLoss(torch.autograd.Function):
     def backward(ctx, g):
         a, b, pyr_a, pyr_b, terms = ctx.saved_tensors
         n, c, h, w, crop, luma, data_range, wts = ctx.cfg
-        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
-        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        da, db = _wanted_grads(ctx, a.shape, a.device)
         if da is not None or db is not None:
             lib = L.lib()
             g = g.to(torch.float32).contiguous()
@@ -207,8 +215,7 @@ class _MsSsimLoss(torch.autograd.Function):
             work = torch.empty(ws, dtype=torch.float32, device=a.device)
             L.check(lib.sisr_ms_ssim_bwd(a.data_ptr(), b.data_ptr(), pyr_a.data_ptr(), pyr_b.data_ptr(), terms.data_ptr(),
                                          g.data_ptr(), n, c, h, w, crop, luma, data_range, len(wts), weights5(wts), work.data_ptr(),
-                                         None if da is None else da.data_ptr(), None if db is None else db.data_ptr(), _stream()),
-                    'sisr_ms_ssim_bwd')
+                                         _ptr(da), _ptr(db), _stream()), 'sisr_ms_ssim_bwd')
         return da, db, None
 
 
@@ -223,8 +230,7 @@ def ms_ssim_loss(a, b, data_range=2.0, crop_border=0, luma=False, weights=MS_SSI
     what = 'ms_ssim_loss'
     _validate_pair(a, b, what)
     crop, wts = check_ms_ssim(a, b, data_range, crop_border, weights, what=what)
-    if reduction not in ('mean', 'none'):
-        raise ValueError("%s: reduction is 'mean' or 'none', got %r" % (what, reduction))
+    _check_reduction(reduction, what)
     require_gpu_tensor(a, 'ms_ssim_loss input a')
     require_gpu_tensor(b, 'ms_ssim_loss input b')
     n, c, h, w = a.shape
@@ -253,8 +259,7 @@ class _FreqLoss(torch.autograd.Function):
         spec = buf(1) if need else None                              # the spectrum D: written only when a gradient will be needed
         pmax = buf(2) if kind == L.FREQ_FOCAL else None
         L.check(lib.sisr_freq_loss_fwd(a.data_ptr(), b.data_ptr(), *shape, kind, eps, alpha, work.data_ptr(),
-                                       None if spec is None else spec.data_ptr(), None if pmax is None else pmax.data_ptr(),
-                                       loss.data_ptr(), _stream()), 'sisr_freq_loss_fwd')
+                                       _ptr(spec), _ptr(pmax), loss.data_ptr(), _stream()), 'sisr_freq_loss_fwd')
         if need:
             ctx.save_for_backward(spec, pmax)  # D and the plane maxima: the inputs are NOT kept
         ctx.cfg, ctx.dims = cfg, (a.shape, dev)
@@ -266,16 +271,15 @@ class _FreqLoss(torch.autograd.Function):
         spec, pmax = ctx.saved_tensors
         n, c, h, w, crop, luma, kind, eps, alpha = ctx.cfg
         shape, dev = ctx.dims
-        da = torch.empty(shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        db = torch.empty(shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        da, db = _wanted_grads(ctx, shape, dev)
         if da is not None or db is not None:
             lib = L.lib()
             g = g.to(torch.float32).contiguous()
             ws = L.check_count(lib.sisr_freq_loss_ws_floats(n, c, h, w, crop, luma, 3), 'sisr_freq_loss_ws_floats')
             work = torch.empty(ws, dtype=torch.float32, device=dev)
-            L.check(lib.sisr_freq_loss_bwd(spec.data_ptr(), None if pmax is None else pmax.data_ptr(), g.data_ptr(), n, c, h, w, crop,
-                                           luma, kind, eps, alpha, work.data_ptr(), None if da is None else da.data_ptr(),
-                                           None if db is None else db.data_ptr(), _stream()), 'sisr_freq_loss_bwd')
+            L.check(lib.sisr_freq_loss_bwd(spec.data_ptr(), _ptr(pmax), g.data_ptr(), n, c, h, w, crop,
+                                           luma, kind, eps, alpha, work.data_ptr(), _ptr(da), _ptr(db), _stream()),
+                    'sisr_freq_loss_bwd')
         return da, db, None
 
 
@@ -303,8 +307,7 @@ def frequency_loss(a, b, kind='l1', eps=1e-3, alpha=1.0, crop_border=0, luma=Fal
     n, c, h, w = a.shape
     if kind not in FREQ_KINDS:
         raise ValueError('%s: kind is one of %s, got %r' % (what, sorted(FREQ_KINDS), kind))
-    if reduction not in ('mean', 'none'):
-        raise ValueError("%s: reduction is 'mean' or 'none', got %r" % (what, reduction))
+    _check_reduction(reduction, what)
     if not float(eps) >= 0.0:
         raise ValueError('%s: eps must not be negative, got %r' % (what, eps))
     if not 0.0 < float(alpha) <= 4.0:
@@ -334,7 +337,7 @@ class _BCE(torch.autograd.Function):
         p = p.detach().contiguous()
         t_vec = None if t_vec is None else t_vec.detach().contiguous()
         loss, mean_p = _scalar(p.device), _scalar(p.device)
-        L.check(L.lib().sisr_bce_fwd(p.data_ptr(), None if t_vec is None else t_vec.data_ptr(), t_scalar, p.numel(), weight,
+        L.check(L.lib().sisr_bce_fwd(p.data_ptr(), _ptr(t_vec), t_scalar, p.numel(), weight,
                                      loss.data_ptr(), mean_p.data_ptr(), _stream()), 'sisr_bce_fwd')
         ctx.save_for_backward(p, t_vec)
         ctx.t_scalar, ctx.weight = t_scalar, weight
@@ -349,7 +352,7 @@ class _BCE(torch.autograd.Function):
         p, t_vec = ctx.saved_tensors
         g = g.to(torch.float32).contiguous()
         dp = torch.empty_like(p)
-        L.check(L.lib().sisr_bce_bwd(p.data_ptr(), None if t_vec is None else t_vec.data_ptr(), ctx.t_scalar, p.numel(),
+        L.check(L.lib().sisr_bce_bwd(p.data_ptr(), _ptr(t_vec), ctx.t_scalar, p.numel(),
                                      ctx.weight, g.data_ptr(), dp.data_ptr(), _stream()), 'sisr_bce_bwd')
         return dp, None, None, None
 

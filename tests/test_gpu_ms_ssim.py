@@ -80,6 +80,32 @@ def test_one_scale_of_weight_one_is_the_ssim_metric(shape, crop, luma):
     assert float((ms.double() - ssim.double()).abs().max()) <= 1e-6
 
 
+@pytest.mark.parametrize('shape,crop,luma', [((1, 1, 11, 11), 0, False), ((2, 3, 45, 70), 2, False), ((1, 3, 37, 50), 1, True)])
+def test_one_scale_of_weight_one_has_the_ssim_loss_gradient_bit_for_bit(shape, crop, luma):
+    """one window position; ragged tiles on both axes with three planes; the three-channel store under luma.  The two backward
+    kernels run the same text (csrc/sisr_ssim_bwd.h, contraction off) on the same map; with upstream ones the image loss adds a
+    pixel term of exactly 0 and MS-SSIM no pooled gradient, and the two factors in front of the window gradient,
+    (float)(-(1 / C') (1 / (Hv Wv))) times pow(t, 1) / t and (float)(-1 / (C' Hv Wv)), are the same float for these shapes
+    (every term of these cases is 0.29 or more: the t <= 0 rule is not in play)"""
+    Lo = pkg('losses')
+    kw = dict(crop_border=crop, luma=luma, reduction='none')
+    for want_b in (True, False):
+        grads = []
+        for loss_of in (lambda a, b: Lo.ms_ssim_loss(a, b, weights=(1.0,), **kw), lambda a, b: Lo.ssim_loss(a, b, **kw)):
+            a, b = (t.cuda() for t in _images(shape))
+            a.requires_grad_()
+            b.requires_grad_(want_b)
+            loss_of(a, b).sum().backward()
+            grads.append((a.grad, b.grad))
+        (ms_da, ms_db), (il_da, il_db) = grads
+        assert ms_da.shape == shape and bool((ms_da != 0).any())
+        assert torch.equal(ms_da, il_da)
+        if want_b:
+            assert torch.equal(ms_db, il_db)
+        else:
+            assert ms_db is None and il_db is None
+
+
 @pytest.mark.parametrize('shape,weights,crop,luma', [VALUE_CASES[2], VALUE_CASES[4], VALUE_CASES[6]])
 def test_loss_is_one_minus_the_metric(shape, weights, crop, luma):
     Lo, M = pkg('losses'), pkg('metrics')
