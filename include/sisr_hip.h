@@ -1013,6 +1013,56 @@ int64_t sisr_usm_ws_bytes(int64_t planes, int32_t H, int32_t W);
 int sisr_usm_fwd(const float *x, const float *taps_dev, int32_t K, float weight, float threshold, float lo, float hi, void *ws,
                  float *y, uint8_t *mask_out, int64_t planes, int32_t H, int32_t W, void *stream);
 
+/* ---- image resize with torch's half-pixel coordinates, the mode chosen per sample, forward and backward.
+ *      x [N][C][H][W] fp32, contiguous -> y [N][C][h][w], any h, w >= 1, up or down, any ratio.  modes [N] int32 in DEVICE memory, one
+ *      per sample: the host never reads it, so a captured launch follows whatever the table holds at replay.  A value outside 0 .. 2
+ *      is treated as SISR_RESIZE_BICUBIC (it indexes nothing).  y = R_h x R_w^T; row o of the 1-D operator R for `in` -> `out`, in integer
+ *      arithmetic (64-bit; nothing depends on an fp32 scale):
+ *        area      s = floor(o in / out), e = ceil((o + 1) in / out): weight 1 / (e - s) on s .. e - 1          (adaptive_avg_pool2d,
+ *                  which is what F.interpolate(mode='area') calls; the window is summed, then multiplied by the weight)
+ *        bilinear  num = max((2 o + 1) in - out, 0), den = 2 out, i0 = num div den, t = (num mod den) / den (one fp32 division):
+ *                  weights 1 - t, t on i0, i0 + 1
+ *        bicubic   num = (2 o + 1) in - out (may be negative), i0 = floor(num / den), t = (num - i0 den) / den, A = -0.75:
+ *                  ((A (t + 1) - 5 A) (t + 1) + 8 A) (t + 1) - 4 A,  ((A + 2) t - (A + 3)) t t + 1,  the second at 1 - t,  the first
+ *                  at 2 - t, on i0 - 1 .. i0 + 2; t and the four polynomials in double, each weight rounded to fp32 once
+ *      Indices are clamped to 0 .. in - 1; two taps that clamp onto the same pixel add.  The forward adds the products of a pass in
+ *      double and rounds once per pass (along x, then along y); the backward's sums are fp32 fused multiply-adds in index order.  This is F.interpolate(align_corners=False) of
+ *      modes 'bilinear' and 'bicubic' (no antialias) and mode 'area'.  A non-finite input value reaches the outputs whose taps read it
+ *      (a tap of weight 0 included, as in torch) and no others.
+ *      SISR_E_BADARG before any HIP call for null pointers, sizes < 1, x and y (or the mode table and y) sharing a byte, a mode outside
+ *      0 .. 2 given to the HOST table, weights of the draw that are negative, not finite or sum to 0, B < 1, rank outside [0, 65536);
+ *      SISR_E_TOOBIG for N C, H W, h w or the workgroup count above INT32_MAX.  Tiles shrink with the ratio until a workgroup's staged
+ *      block fits 64 KB of LDS.  SISR_E_UNSUPPORTED, from BOTH directions alike and before the launch, when not even a 1 x 1 tile fits:
+ *      a down-scaling with about (H / h + 2) (W / w + 3) > 16000 or an up-scaling with about (4 h / H + 2) (4 w / W + 3) > 16000.
+ *      Every ratio up to 16 per axis, up or down, is served. ------------------------------------------------------------------------ */
+enum { SISR_RESIZE_AREA = 0, SISR_RESIZE_BILINEAR = 1, SISR_RESIZE_BICUBIC = 2 };
+#define SISR_RESIZE_MAX_TAPS 64
+/* HOST, no HIP call: the rows of R as the kernels compute them (one __host__ __device__ text).  Row o has count[o] weights
+ * w[o][0 .. count[o] - 1] on the UNCLAMPED input indices first[o] .. first[o] + count[o] - 1 (bicubic: first may be -2, when
+ * up-scaling, and the last index may reach in + 1; bilinear: the last may reach in); a reader clamps them to 0 .. in - 1 and adds
+ * taps that meet.  first, count:
+ * [out] int32; w: [out][SISR_RESIZE_MAX_TAPS], zeros behind the row's weights.  SISR_RESIZE_MAX_TAPS bounds this table only: an
+ * area window longer than it is SISR_E_UNSUPPORTED here, while the kernels loop over a window of any length. */
+int sisr_resize_taps_host(int32_t mode, int32_t in_size, int32_t out_size, int32_t *first, int32_t *count, float *w);
+/* One launch: a workgroup per output tile (16 x 64, halved until it fits) and plane; the tile's taps, the input footprint and the
+ * row-filtered footprint live in LDS. */
+int sisr_resize_fwd(const float *x, const int32_t *modes_dev, float *y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t h, int32_t w,
+                    void *stream);
+/* dx [N][C][H][W] = R_h^T dy R_w, the exact transpose (clamped border taps fold onto the border pixel), in gather form: every input
+ * pixel sums the outputs that read it in index order.  One launch, no atomics, no zero-fill, every element of dx stored, the same
+ * bits on every call. */
+int sisr_resize_bwd(const float *dy, const int32_t *modes_dev, float *dx, int32_t N, int32_t C, int32_t H, int32_t W, int32_t h, int32_t w,
+                    void *stream);
+/* One workgroup: t = *drawn_step_dev is READ and not advanced (the pattern of sisr_jpeg_tables: the launch shares the step a stage's
+ * draw stored).  Sample b: counter {t low, t high, b, 0xFE090000 | rank}, u0 = ((r0 >> 8) + 0.5) 2^-24 in fp32; with
+ * p_i = weight_i / ((p_area + p_bilinear) + p_bicubic) in fp32, the mode is the first i with p_i > 0 and u0 <= p_0 + .. + p_i (fp32,
+ * added in index order; u0 above the rounded sum: the last mode with p_i > 0).  modes_dev [B] int32. */
+int sisr_resize_modes_draw(const int64_t *drawn_step_dev, uint64_t seed, int32_t rank, int32_t B, float p_area, float p_bilinear,
+                           float p_bicubic, int32_t *modes_dev, void *stream);
+/* HOST: the same text for step t >= 0 into host memory, no GPU involved. */
+int sisr_resize_modes_host(int64_t t, uint64_t seed, int32_t rank, int32_t B, float p_area, float p_bilinear, float p_bicubic,
+                           int32_t *modes_host);
+
 /* ---- misc---------------------------------------------------------------------------------- */
 /* ---- optimizer: fused multi-tensor Adam --------------------------------------------------
  * One launch performs torch.optim.Adam's update (amsgrad=False, maximize=False; config.py:292-294, stepped at

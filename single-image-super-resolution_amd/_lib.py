@@ -22,6 +22,8 @@ PIX_L1, PIX_CHARBONNIER, PIX_MSE = range(3)  # pix_kind of sisr_image_loss_fwd /
 FREQ_L1, FREQ_CHARBONNIER, FREQ_FOCAL = range(3)   # kind of sisr_freq_loss_fwd / sisr_freq_loss_bwd
 FREQ_MAX_SIDE = 256                          # SISR_FREQ_MAX_SIDE: the longest view side the DFT kernels take
 GAUSS_MAX_K = 63                             # SISR_GAUSS_MAX_K: the longest filter of sisr_gauss_blur_* / sisr_usm_fwd
+RESIZE_AREA, RESIZE_BILINEAR, RESIZE_BICUBIC = range(3)      # mode codes of sisr_resize_fwd / sisr_resize_bwd
+RESIZE_MAX_TAPS = 64                         # SISR_RESIZE_MAX_TAPS: the row length of sisr_resize_taps_host's table
 ROUTE_GENERIC, ROUTE_DEEP, ROUTE_TOIMAGE, ROUTE_TRUNK, ROUTE_THIN = range(5)      # enum SisrRoute: what the sisr_*_route calls answer
 
 _f = C.c_void_p      # device pointers travel as void*
@@ -274,6 +276,11 @@ _SIGS = {
     'sisr_gauss_blur_bwd': [_f, _f, _f, _i64, _i32, _i32, _i32, _f],
     'sisr_usm_ws_bytes': [_i64, _i32, _i32],
     'sisr_usm_fwd': [_f, _f, _i32, _f32, _f32, _f32, _f32, _f, _f, _f, _i64, _i32, _i32, _f],
+    'sisr_resize_taps_host': [_i32, _i32, _i32, _f, _f, _f],
+    'sisr_resize_fwd': [_f, _f, _f] + [_i32] * 6 + [_f],
+    'sisr_resize_bwd': [_f, _f, _f] + [_i32] * 6 + [_f],
+    'sisr_resize_modes_draw': [_f, C.c_uint64, _i32, _i32, _f32, _f32, _f32, _f, _f],
+    'sisr_resize_modes_host': [_i64, C.c_uint64, _i32, _i32, _f32, _f32, _f32, _f],
     'sisr_struct_sizes': [C.POINTER(_i32), _i32],
     'sisr_device_info': [C.POINTER(_i32), C.POINTER(_i32), C.c_char_p, _i32],
     'sisr_mfma_selftest': [_f, _f],

@@ -1,8 +1,8 @@
-// sisr_philox.h -- the counter-based random numbers of the device-side samplers (patchsrc.hip, degrade.hip, jpeg.hip): one text for host and
+// sisr_philox.h -- the counter-based random numbers of the device-side samplers (patchsrc.hip, degrade.hip, jpeg.hip, resize.hip): one text for host and
 // device, so every draw has a host restatement that needs no GPU.  Word 3 of a counter says whose it is: a patch-source sample
 // carries its rank (< 2^31), the epoch permutation tags >= 0xFFFFFFE7, the degradation 0xFE01xxxx / 0xFE02xxxx (degrade.hip), the
 // JPEG quality 0xFE03xxxx (jpeg.hip), the mixed kernel draw 0xFE04xxxx .. 0xFE07xxxx (family and size, shape, cutoff and noise row,
-// final filter) and the grey noise 0xFE08xxxx (degrade.hip).  The next free tag is 0xFE09xxxx.
+// final filter), the grey noise 0xFE08xxxx (degrade.hip) and the resize mode 0xFE09xxxx (resize.hip).  The next free tag is 0xFE0Axxxx.
 #pragma once
 #include <stdint.h>
 

@@ -398,14 +398,23 @@ class HighOrderDegrader:
     ``final_sinc_prob``  the probability that the sample's final filter is a sinc kernel (otherwise the delta kernel); None: no
                          final filter.  The filter is ``degrade`` at equal sizes, where the cubic taps are exactly (0, 1, 0, 0): a pure
                          blur, clamped.  ``final_order``: 'sinc_jpeg' filters before the last stage's JPEG round trip, 'jpeg_sinc' after.
+    ``resize_probs``     None: every stage resamples with the align-corners bicubic fused into ``degrade`` (section 18).  A triple of
+                         weights (area, bilinear, bicubic): every stage draws a resampler PER SAMPLE on its drawn step
+                         (sisr_resize_modes_draw: the count does not advance, ``state_dict`` is unchanged) and becomes
+                         ``degrade`` at equal sizes -- a pure blur -- followed by ``resize.resize`` with torch's half-pixel
+                         coordinates, Real-ESRGAN's ``random.choice(['area', 'bilinear', 'bicubic'])``; ``last_modes[i]`` [N] int32.
     ``last_*``           the latest call's tables, one entry per stage: ``last_kernels``, ``last_params``, ``last_noise_table``,
                          ``last_drawn_step``, ``last_tables`` / ``last_quality`` (None without JPEG), ``last_sizes``; and
                          ``last_final_kernels``.  ``step``: the 0-dim int64 device tensor of draws made so far."""
 
     def __init__(self, stages=None, mid_size=None, mid_scale=None, final_sinc_prob=0.8, final_order='sinc_jpeg', seed=0, rank=0,
-                 device=None, jpeg_subsampling='420', jpeg_grad='ste'):
+                 device=None, jpeg_subsampling='420', jpeg_grad='ste', resize_probs=None):
         from . import jpeg as J
         who = 'HighOrderDegrader'
+        self.resize_probs = None
+        if resize_probs is not None:
+            from .resize import _check_probs
+            self.resize_probs = _check_probs(resize_probs, who)
         self.stages = tuple(realesrgan_stages() if stages is None else stages)
         if not self.stages or not all(isinstance(s, DegradeStage) for s in self.stages):
             raise ValueError('%s: stages must be a non-empty sequence of DegradeStage' % who)
@@ -436,6 +445,7 @@ class HighOrderDegrader:
         none = [None] * len(self.stages)
         self.last_kernels, self.last_params, self.last_noise_table, self.last_drawn_step = list(none), list(none), list(none), list(none)
         self.last_tables, self.last_quality, self.last_sizes, self.last_final_kernels = list(none), list(none), list(none), None
+        self.last_modes = list(none)
 
     def draw_mix(self, i, n):
         """the tables of the next step for stage ``i`` and a batch of ``n``: -> (kernels, final_kernels or None, params, noise_table,
@@ -493,7 +503,13 @@ class HighOrderDegrader:
             else:
                 self.last_quality[i] = None
             self.last_tables[i], self.last_sizes[i] = tables, sizes[i]
-            x = degrade(x, sizes[i], k, None, clamp=False)
+            if self.resize_probs is None:
+                x = degrade(x, sizes[i], k, None, clamp=False)
+            else:                                                         # a pure blur at the stage's input size, then the drawn resampler
+                from .resize import draw_resize_modes, resize
+                modes = self.last_modes[i] = draw_resize_modes(t, self.seed, self.rank, n, self.resize_probs)
+                x = degrade(x, (int(x.shape[2]), int(x.shape[3])), k, None, clamp=False)
+                x = resize(x, sizes[i], modes)
             x = degrade_noise(x, nt, t, self.seed, self.rank, clamp=True)
             if fk is not None and self.final_order == 'sinc_jpeg':
                 x = degrade(x, sizes[i], fk, None, clamp=True)
