@@ -1013,6 +1013,36 @@ int64_t sisr_usm_ws_bytes(int64_t planes, int32_t H, int32_t W);
 int sisr_usm_fwd(const float *x, const float *taps_dev, int32_t K, float weight, float threshold, float lo, float hi, void *ws,
                  float *y, uint8_t *mask_out, int64_t planes, int32_t H, int32_t W, void *stream);
 
+/* ---- artifact-aware (locally discriminative, LDL) image loss: the refined artifact map of Liang et al. (CVPR 2022) and the L1 it
+ *      weighs, forward and backward.  sr, gt, ema: fp32 [N][C][H][W], contiguous, C 1 or 3; K = ksize odd,
+ *      3 .. SISR_ARTIFACT_MAX_K, P = K / 2, H > P and W > P:
+ *          r_sr[n,y,x] = sum_c |gt - sr|,   r_ema[n,y,x] = sum_c |gt - ema|
+ *          p[n]        = Var(r_sr[n,:,:])^(1/5)                       (unbiased: divisor H W - 1)
+ *          v[n,y,x]    = Var of r_sr[n] over the K x K window at (y, x) (unbiased: divisor K K - 1), coordinates outside the plane
+ *                        mirrored without repeating the edge pixel: -q below 0, 2 (L - 1) - q from L on (the rule of sisr_gauss_*)
+ *          map[n,y,x]  = p[n] v[n,y,x], exactly 0 where r_sr < r_ema  (strict: a tie keeps the weight)
+ *          loss[n]     = weight mean_{c,y,x} map |sr - gt|            = weight sum_{y,x} map r_sr / (C H W)
+ *      The map is a CONSTANT of the loss: dsr = g[n] weight map sign(sr - gt) / (C H W), dgt = -dsr, sign(0) = 0, nothing for ema.
+ *      Both variances are taken around a value of the data (shifted sums in double, count / mean / M2 partials merged in a fixed
+ *      order; the window's in two passes), never as a difference of raw moments.  Fixed-order sums, no atomics, plain vector stores:
+ *      the same bits on every call, and nothing is read back by the host.  SISR_E_BADARG before any HIP call for null pointers, a
+ *      workspace that is not 8-byte aligned, N < 1, H or W < 1, K even or outside 3 .. SISR_ARTIFACT_MAX_K, a weight that is not finite;
+ *      SISR_E_UNSUPPORTED for C not in {1, 3} and for H <= P or W <= P; SISR_E_TOOBIG for N C H W or the workspace above INT32_MAX
+ *      floats. ------------------------------------------------------------------------------------------------------------------ */
+#define SISR_ARTIFACT_MAX_K 11
+/* HOST: floats of the forward's workspace: the two residual planes [N][H][W], the (count, mean, M2) partials of every sample and
+ * one partial sum per 8 x 64 tile, the last two kept as doubles; < 0: a status code */
+int sisr_artifact_ws_floats(int32_t N, int32_t H, int32_t W);
+/* map: [N][H][W]; loss: [N], or NULL for the map alone.  ws: 8-byte aligned.  Three launches (two without loss): the residual
+ * planes and the samples' variance partials; an 8 x 64 tile of r_sr with its mirrored halo in LDS -> window variance, p[n] from the
+ * merged partials, mask, map and the tile's sum of map r_sr; per sample a fixed-order sum in double */
+int sisr_artifact_fwd(const float *sr, const float *gt, const float *ema, int32_t N, int32_t C, int32_t H, int32_t W, int32_t ksize,
+                      float weight, void *ws, float *map, float *loss, void *stream);
+/* map: as the forward left it; g: [N] upstream gradients in DEVICE memory; dsr / dgt: [N][C][H][W], either may be NULL (then not
+ * written; dgt is -dsr bit for bit).  One elementwise launch */
+int sisr_artifact_bwd(const float *sr, const float *gt, const float *map, const float *g, int32_t N, int32_t C, int32_t H, int32_t W,
+                      float weight, float *dsr, float *dgt, void *stream);
+
 /* ---- image resize with torch's half-pixel coordinates, the mode chosen per sample, forward and backward.
  *      x [N][C][H][W] fp32, contiguous -> y [N][C][h][w], any h, w >= 1, up or down, any ratio.  modes [N] int32 in DEVICE memory, one
  *      per sample: the host never reads it, so a captured launch follows whatever the table holds at replay.  A value outside 0 .. 2

@@ -21,6 +21,7 @@ JPEG_GRAD_STE, JPEG_GRAD_CUBIC = range(2)
 PIX_L1, PIX_CHARBONNIER, PIX_MSE = range(3)  # pix_kind of sisr_image_loss_fwd / sisr_image_loss_bwd
 FREQ_L1, FREQ_CHARBONNIER, FREQ_FOCAL = range(3)   # kind of sisr_freq_loss_fwd / sisr_freq_loss_bwd
 FREQ_MAX_SIDE = 256                          # SISR_FREQ_MAX_SIDE: the longest view side the DFT kernels take
+ARTIFACT_MAX_K = 11                          # SISR_ARTIFACT_MAX_K: the largest window of sisr_artifact_fwd
 GAUSS_MAX_K = 63                             # SISR_GAUSS_MAX_K: the longest filter of sisr_gauss_blur_* / sisr_usm_fwd
 RESIZE_AREA, RESIZE_BILINEAR, RESIZE_BICUBIC = range(3)      # mode codes of sisr_resize_fwd / sisr_resize_bwd
 RESIZE_MAX_TAPS = 64                         # SISR_RESIZE_MAX_TAPS: the row length of sisr_resize_taps_host's table
@@ -271,6 +272,9 @@ _SIGS = {
     'sisr_freq_loss_ws_floats': [_i32] * 7,
     'sisr_freq_loss_fwd': [_f, _f] + [_i32] * 7 + [_f32, _f32, _f, _f, _f, _f, _f],
     'sisr_freq_loss_bwd': [_f, _f, _f] + [_i32] * 7 + [_f32, _f32, _f, _f, _f, _f],
+    'sisr_artifact_ws_floats': [_i32, _i32, _i32],
+    'sisr_artifact_fwd': [_f, _f, _f] + [_i32] * 5 + [_f32, _f, _f, _f, _f],
+    'sisr_artifact_bwd': [_f, _f, _f, _f] + [_i32] * 4 + [_f32, _f, _f, _f],
     'sisr_gauss_taps_host': [_i32, _f32, _f],
     'sisr_gauss_blur_fwd': [_f, _f, _f, _i64, _i32, _i32, _i32, _f],
     'sisr_gauss_blur_bwd': [_f, _f, _f, _i64, _i32, _i32, _i32, _f],

@@ -23,6 +23,11 @@ focal frequency loss, from ONE direct separable DFT of ``a - b`` (view sides up 
 backward; saved are the spectrum and the plane maxima, not the inputs.  ``fft_l1_loss`` and ``focal_frequency_loss`` are its
 one-term forms.
 
+``artifact_loss`` (csrc/artifact.hip) is the artifact-aware (locally discriminative, LDL) term of Liang et al., "Details or
+Artifacts" (CVPR 2022): an L1 between ``sr`` and ``gt`` weighted by the refined artifact map, which compares the residual of the
+generator's output with that of its EMA twin's; ``artifact_map`` is the map alone.  Three launches forward, one backward; saved are
+``sr``, ``gt`` and the one-channel map.  The map is a constant of the loss (detached).
+
 Nothing here synchronises with the host: losses and statistics are 0-dim fp32 device tensors, bit-identical from call to call,
 and the launches can be captured by ``graph.GraphedStep``.  Opt-in: ``install(fused_losses=True)`` points ``torch.nn.BCELoss`` at
 ``BCELoss``; a trainer rebinds its ``content_loss_g`` / ``adversarial_loss_*`` to the functions below.
@@ -329,6 +334,104 @@ def fft_l1_loss(a, b, crop_border=0, luma=False, reduction='mean'):
 def focal_frequency_loss(a, b, alpha=1.0, crop_border=0, luma=False, reduction='mean'):
     """the focal frequency loss per image -> ``frequency_loss`` with ``kind='focal'``"""
     return frequency_loss(a, b, kind='focal', alpha=alpha, crop_border=crop_border, luma=luma, reduction=reduction)
+
+
+def _check_artifact(sr, gt, ema, ksize, what):
+    """the argument errors, whatever the tensors live on -> (N, C, H, W)"""
+    _validate_pair(sr, gt, what)
+    _validate_pair(sr, ema, what)
+    if sr.dim() != 4 or sr.shape[1] not in (1, 3):
+        raise ValueError('%s: [N, C, H, W] batches with C 1 or 3 are expected, got shape %s' % (what, tuple(sr.shape)))
+    if not isinstance(ksize, int) or isinstance(ksize, bool) or ksize < 3 or ksize > L.ARTIFACT_MAX_K or ksize % 2 == 0:
+        raise ValueError('%s: ksize is an odd integer in 3 .. %d, got %r' % (what, L.ARTIFACT_MAX_K, ksize))
+    h, w = sr.shape[-2:]
+    if min(h, w) <= ksize // 2:
+        raise ValueError('%s: the mirrored border of a %d x %d window needs sides longer than %d, got %d x %d'
+                         % (what, ksize, ksize, ksize // 2, h, w))
+    if sr.numel() > 2 ** 31 - 1:
+        raise ValueError('%s: at most 2^31 - 1 elements per batch, got %d' % (what, sr.numel()))
+    return tuple(sr.shape)
+
+
+def _require_gpu_artifact(sr, gt, ema, what):
+    for t, name in ((sr, 'sr'), (gt, 'gt'), (ema, 'ema')):
+        require_gpu_tensor(t, '%s input %s' % (what, name))
+
+
+def _artifact_forward(sr, gt, ema, shape, ksize, weight, with_loss):
+    """-> (map [N, 1, H, W], loss [N] or None) of contiguous detached inputs"""
+    n, c, h, w = shape
+    lib, dev = L.lib(), sr.device
+    work = torch.empty(L.check_count(lib.sisr_artifact_ws_floats(n, h, w), 'sisr_artifact_ws_floats'), dtype=torch.float32, device=dev)
+    amap = torch.empty((n, 1, h, w), dtype=torch.float32, device=dev)
+    loss = torch.empty(n, dtype=torch.float32, device=dev) if with_loss else None
+    L.check(lib.sisr_artifact_fwd(sr.data_ptr(), gt.data_ptr(), ema.data_ptr(), n, c, h, w, ksize, weight, work.data_ptr(),
+                                  amap.data_ptr(), _ptr(loss), _stream()), 'sisr_artifact_fwd')
+    return amap, loss
+
+
+class _ArtifactLoss(torch.autograd.Function):
+    """-> (loss[N], map[N, 1, H, W]); ``cfg`` = (N, C, H, W, ksize, weight)"""
+
+    @staticmethod
+    def forward(ctx, sr, gt, ema, cfg):
+        sr, gt, ema = sr.detach().contiguous(), gt.detach().contiguous(), ema.detach().contiguous()
+        amap, loss = _artifact_forward(sr, gt, ema, cfg[:4], cfg[4], cfg[5], True)
+        ctx.save_for_backward(sr, gt, amap)    # the two inputs and the one-channel map: ema is not kept
+        ctx.cfg = cfg
+        ctx.mark_non_differentiable(amap)
+        return loss, amap
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_map):
+        sr, gt, amap = ctx.saved_tensors
+        n, c, h, w, _, weight = ctx.cfg
+        dsr, dgt = _wanted_grads(ctx, sr.shape, sr.device)
+        if dsr is not None or dgt is not None:
+            g = g.to(torch.float32).contiguous()
+            L.check(L.lib().sisr_artifact_bwd(sr.data_ptr(), gt.data_ptr(), amap.data_ptr(), g.data_ptr(), n, c, h, w, weight,
+                                              _ptr(dsr), _ptr(dgt), _stream()), 'sisr_artifact_bwd')
+        return dsr, dgt, None, None
+
+
+def artifact_map(gt, sr, ema, ksize=7):
+    """The refined artifact map of the LDL loss (BasicSR's ``get_refined_artifact_map(img_gt, img_output, img_ema, ksize)``) of three
+    fp32 [N, C, H, W] device batches, C 1 or 3 -> a detached fp32 [N, 1, H, W] tensor; no graph is recorded.  With
+    ``r_sr = sum_c |gt - sr|`` and ``r_ema = sum_c |gt - ema|``: the unbiased variance of ``r_sr`` over the ``ksize`` x ``ksize``
+    window of each pixel (mirrored border, torch's ``reflect``) times ``Var(r_sr[n])^(1/5)`` over the whole sample, and exactly 0
+    where ``r_sr < r_ema`` (strict: a tie keeps the weight, so ``ema is sr`` masks nothing).  ``ksize`` odd, 3 .. 11; H and W
+    longer than ``ksize // 2``."""
+    shape = _check_artifact(sr, gt, ema, ksize, 'artifact_map')
+    _require_gpu_artifact(sr, gt, ema, 'artifact_map')
+    with torch.no_grad():
+        return _artifact_forward(sr.detach().contiguous(), gt.detach().contiguous(), ema.detach().contiguous(), shape, ksize, 1.0,
+                                 False)[0]
+
+
+def artifact_loss(sr, gt, ema, ksize=7, weight=1.0, reduction='mean', return_map=False):
+    """The artifact-aware (LDL) loss of Liang et al. (CVPR 2022) per image of fp32 [N, C, H, W] device batches, C 1 or 3:
+    ``weight * mean_{c,y,x}(m * |sr - gt|)`` with ``m = artifact_map(gt, sr, ema, ksize)`` -- BasicSR's
+    ``L1Loss(m * sr, m * gt)``, as ``m >= 0``.  ``ema`` is the output of the EMA generator on the same input.
+    -> 0-dim fp32 device tensor (the mean over the batch), or [N] with ``reduction='none'``; with ``return_map`` also the detached
+    map.
+
+    THE MAP IS A CONSTANT OF THE LOSS (detached): ``dL/dsr = g[n] * weight * m * sign(sr - gt) / (C H W)``, ``dL/dgt = -dL/dsr``
+    bit for bit, ``sign(0) = 0``, and ``ema`` gets no gradient.  A gradient through the map (through the two variances) is left
+    out on purpose: the map is a weighting, not a term to be minimised.  Differentiable with respect to ``sr``, ``gt`` or both
+    (only what requires a gradient is computed), once.  Three launches forward, one backward; saved: ``sr``, ``gt`` and the map.
+    Non-contiguous inputs are made contiguous first; a bf16 caller casts."""
+    what = 'artifact_loss'
+    shape = _check_artifact(sr, gt, ema, ksize, what)
+    _check_reduction(reduction, what)
+    weight = float(weight)
+    if not np.isfinite(weight):
+        raise ValueError('%s: weight must be finite, got %r' % (what, weight))
+    _require_gpu_artifact(sr, gt, ema, what)
+    loss, amap = _ArtifactLoss.apply(sr, gt, ema, shape + (ksize, weight))
+    if reduction == 'mean':
+        loss = loss.mean()
+    return (loss, amap) if return_map else loss
 
 
 class _BCE(torch.autograd.Function):
