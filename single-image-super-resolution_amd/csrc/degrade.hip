@@ -7,12 +7,10 @@
 //   degrade_bwd_kernel   one workgroup per HR tile and (n, c): R^T (dy * mask) over the tile plus halo -> LDS, B^T (the flipped
 //                        kernel) over the tile's PADDED coordinates -> LDS, then the fold of the replicate border onto its pixels.
 //                        Gather form, fixed order, no atomics: the same bits on every call.
-// Random numbers: Philox4x32-10 keyed by the seed (sisr_philox.h); word 3 of the counter is 0xFE010000 | rank for a sample's
-// parameters and 0xFE020000 | rank for a group of four noise values -- tags no patch-source counter uses.  One text for host and
-// device (sisr_degrade_params_host / sisr_degrade_noise_host are the same arithmetic without a GPU).  Plain vector stores only.
-// The second-order model at the end of the file: degrade_draw_mix_kernel (seven kernel families, the noise
-// row and the final sinc filter of a sample; tags 0xFE04 .. 0xFE07) and degrade_noise_fwd_kernel / degrade_noise_bwd_kernel
-// (Gaussian or shot noise, colour or grey -- the grey stream is tagged 0xFE08 -- and the clamp), elementwise with a grid-stride loop.
+// Random numbers: the draws and tags of sisr_philox.h, one text for host and device (sisr_degrade_params_host / _noise_host are the
+// same arithmetic without a GPU).  Plain vector stores only.  A drawn kernel's weights, sum and store are one code for both draws.
+// The second-order model at the end of the file: degrade_draw_mix_kernel (family, noise row and final sinc
+// filter of a sample) and degrade_noise_fwd_kernel / _bwd_kernel (Gaussian or shot noise, colour or grey, the clamp), elementwise.
 #include "sisr_dev.h"
 #include "sisr_cubic.h"
 #include "sisr_philox.h"
@@ -21,23 +19,9 @@
 #include <cmath>
 
 #define DG_KMAX 21
-#define DG_TAG_PARAMS 0xFE010000u
-#define DG_TAG_NOISE 0xFE020000u
 #define DG_PI 3.14159265358979323846f
 
 // ---- random numbers --------------------------------------------------------------------------------------------------------------
-// u = ((r >> 8) + 0.5) 2^-24, in (0, 1]: fp32 rounds the 25-bit numerator to even above 1/2, so the last value reads as 1
-__host__ __device__ __forceinline__ float dg_uniform(uint32_t r) { return ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f); }
-
-// ln u for the same word.  Below 1/2 the numerator is exact and logf takes it; above, 1 - u = (2^24 - (r >> 8) - 0.5) 2^-24 is the
-// exact quantity and log1pf takes that: near u = 1, where a Box-Muller radius is sqrt(2 (1 - u)), the rounded u would carry an
-// error as large as the radius itself
-__host__ __device__ __forceinline__ float dg_log_uniform(uint32_t r) {
-    const uint32_t m = r >> 8;
-    if (m < (1u << 23)) return logf(((float)m + 0.5f) * (1.0f / 16777216.0f));
-    return log1pf(-(((float)((1u << 24) - m) - 0.5f) * (1.0f / 16777216.0f)));
-}
-
 struct DegradeDrawArgs {
     uint64_t seed;
     int rank, B, K, aniso;
@@ -46,43 +30,90 @@ struct DegradeDrawArgs {
 
 // parameters of sample b at step t: p = { sigma1, sigma2, theta, sigma_n }
 __host__ __device__ __forceinline__ void degrade_draw_params(const DegradeDrawArgs& a, int64_t t, int b, float p[4]) {
-    const uint32_t ctr[4] = {(uint32_t)((uint64_t)t & 0xFFFFFFFFu), (uint32_t)((uint64_t)t >> 32), (uint32_t)b,
-                             DG_TAG_PARAMS | (uint32_t)a.rank};
     uint32_t r[4];
-    philox4x32_10(ctr, (uint32_t)(a.seed & 0xFFFFFFFFu), (uint32_t)(a.seed >> 32), r);
-    p[0] = a.lo + (a.hi - a.lo) * dg_uniform(r[0]);
-    p[1] = a.aniso ? a.lo + (a.hi - a.lo) * dg_uniform(r[1]) : p[0];
-    p[2] = DG_PI * dg_uniform(r[2]);
-    p[3] = a.nlo + (a.nhi - a.nlo) * dg_uniform(r[3]);
-}
-
-// unnormalised weight of tap i = (dy + R) K + (dx + R)
-__host__ __device__ __forceinline__ float degrade_weight(int i, int K, const float p[4], float cs, float sn) {
-    const int R = (K - 1) / 2;
-    const float dy = (float)(i / K - R), dx = (float)(i % K - R);
-    const float u = cs * dx + sn * dy, v = -sn * dx + cs * dy;
-    return expf(-0.5f * (u * u / (p[0] * p[0]) + v * v / (p[1] * p[1])));
+    draw_words(a.seed, t, (uint32_t)b, DRAW_TAG_PARAMS | (uint32_t)a.rank, r);
+    p[0] = a.lo + (a.hi - a.lo) * draw_uniform(r[0]);
+    p[1] = a.aniso ? a.lo + (a.hi - a.lo) * draw_uniform(r[1]) : p[0];
+    p[2] = DG_PI * draw_uniform(r[2]);
+    p[3] = a.nlo + (a.nhi - a.nlo) * draw_uniform(r[3]);
 }
 
 // z of output element e: group g = e / 4 draws four words, Box-Muller on (u0, u1) and (u2, u3), element e takes z[e mod 4]
 __host__ __device__ __forceinline__ float degrade_noise_z_tagged(uint64_t seed, int64_t t, uint32_t tag_rank, int64_t e) {
-    const uint32_t ctr[4] = {(uint32_t)((uint64_t)t & 0xFFFFFFFFu), (uint32_t)((uint64_t)t >> 32), (uint32_t)(e >> 2), tag_rank};
     uint32_t r[4];
-    philox4x32_10(ctr, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), r);
+    draw_words(seed, t, (uint32_t)(e >> 2), tag_rank, r);
     const int j = (int)(e & 3);
-    const float rad = sqrtf(-2.0f * dg_log_uniform(r[j & 2]));
-    const float ang = 2.0f * DG_PI * dg_uniform(r[(j & 2) + 1]);
+    const float rad = sqrtf(-2.0f * draw_log_uniform(r[j & 2]));
+    const float ang = 2.0f * DG_PI * draw_uniform(r[(j & 2) + 1]);
     return rad * ((j & 1) ? sinf(ang) : cosf(ang));
 }
 __host__ __device__ __forceinline__ float degrade_noise_z(uint64_t seed, int64_t t, int rank, int64_t e) {
-    return degrade_noise_z_tagged(seed, t, DG_TAG_NOISE | (uint32_t)rank, e);
+    return degrade_noise_z_tagged(seed, t, DRAW_TAG_NOISE | (uint32_t)rank, e);
 }
 
 static bool degrade_draw_args_ok(const DegradeDrawArgs& a) {
     if (a.B < 1 || a.K < 1 || a.K > DG_KMAX || !(a.K & 1)) return false;
-    if (a.rank < 0 || a.rank >= 65536) return false;
+    if (a.rank < 0 || a.rank >= DRAW_RANK_LIMIT) return false;
     if (!(a.lo > 0.f) || !(a.lo <= a.hi) || !(a.hi < INFINITY)) return false;
     return a.nlo >= 0.f && a.nlo <= a.nhi && a.nhi < INFINITY;
+}
+
+// ---- one drawn kernel: its weights, their sum, the normalised store (both draws; the seven families are section 25's) -----------------
+#define DG_FAMILY_SINC 6                          // 0 .. 5 index kernel_probs: iso, aniso, generalized_iso / _aniso, plateau_iso / _aniso
+struct MixKernel {                                 // params row = family, k_eff, sigma1, sigma2, theta, beta, omega, on
+    int family, k_eff, on;
+    float s1, s2, theta, beta, omega;
+};
+
+// the first-order draw p = { sigma1, sigma2, theta, .. }: the anisotropic Gaussian at full size, rotated even where the sigmas are equal
+__host__ __device__ __forceinline__ MixKernel degrade_gaussian(int K, const float p[4]) { return {1, K, 1, p[0], p[1], p[2], 0.f, 0.f}; }
+
+// Bessel J1 for x >= 0 in double (arguments reach pi sqrt(2) 10 = 44.4): below 12 the power series sum_k (-1)^k (x/2)^(2k+1) /
+// (k! (k+1)!) (largest term 4.2e3: 5e-13 of cancellation), from 12 on Hankel's expansion sqrt(2 / (pi x)) (P cos c - Q sin c),
+// c = x - 3 pi / 4, with a_k = a_(k-1) (4 - (2k - 1)^2) / (8 k): P = sum (-1)^j a_2j / x^2j, Q = sum (-1)^j a_(2j+1) / x^(2j+1),
+// twelve terms.  Within 1e-11 of the integral definition on [0, 47].
+__host__ __device__ __forceinline__ double dg_j1(double x) {
+    if (x < 12.0) {
+        const double h = 0.5 * x, h2 = h * h;
+        double term = h, sum = h;
+#pragma unroll
+        for (int k = 1; k <= 32; ++k) {
+            term *= h2 * (-1.0 / (double)(k * (k + 1)));          // (a constant per unrolled step: no division at run time)
+            sum += term;
+        }
+        return sum;
+    }
+    const double inv = 1.0 / x;
+    double t = 1.0, P = 1.0, Q = 0.0;
+#pragma unroll
+    for (int k = 1; k <= 12; ++k) {
+        t *= ((4.0 - (double)((2 * k - 1) * (2 * k - 1))) / (8.0 * (double)k)) * inv;
+        const double s = ((k >> 1) & 1) ? -t : t;
+        if (k & 1) Q += s;
+        else P += s;
+    }
+    const double c = x - 2.35619449019234492885;
+    return sqrt(0.63661977236758134308 / x) * (P * cos(c) - Q * sin(c));
+}
+
+// unnormalised weight of tap i = (dy + R) K + (dx + R); cs, sn = cosf, sinf of theta
+__host__ __device__ __forceinline__ float mix_weight(int i, int K, const MixKernel& k, float cs, float sn) {
+    const int R = (K - 1) / 2, Re = (k.k_eff - 1) / 2;
+    const int iy = i / K - R, ix = i % K - R;
+    if (!k.on) return iy == 0 && ix == 0 ? 1.f : 0.f;
+    if (iy < -Re || iy > Re || ix < -Re || ix > Re) return 0.f;
+    if (k.family == DG_FAMILY_SINC) {
+        const double w = (double)k.omega;
+        if (iy == 0 && ix == 0) return (float)(w * w / (4.0 * 3.14159265358979323846));
+        const double r = sqrt((double)(ix * ix + iy * iy));
+        return (float)(w * dg_j1(w * r) / (2.0 * 3.14159265358979323846 * r));
+    }
+    const float dy = (float)iy, dx = (float)ix;
+    const float u = cs * dx + sn * dy, v = -sn * dx + cs * dy;
+    const float q = u * u / (k.s1 * k.s1) + v * v / (k.s2 * k.s2);
+    if (k.family < 2) return expf(-0.5f * q);
+    const float qb = powf(q, k.beta);
+    return k.family < 4 ? expf(-0.5f * qb) : 1.f / (qb + 1.f);
 }
 
 // The K^2 <= 448 weights of a sample sit 7 to a lane, tap i = lane + 64 m.  Their sum in a FIXED order: each lane adds its own,
@@ -100,30 +131,43 @@ static float degrade_sum_host(const float* w, int KK) {
     return part[0];
 }
 
-// One workgroup.  Every thread reads the count before the barrier, one thread stores count + 1 behind it (as patch_draw_kernel):
-// a captured draw advances on every replay.  One wave per sample (b = wave, wave + 4, ..): no LDS, no further barrier.
+// one kernel of one sample by one wave: the weights 7 to a lane, their sum in degrade_sum_host's order, the normalised store
+__device__ __forceinline__ void mix_store_kernel(const MixKernel& k, int K, int lane, float* __restrict__ dst) {
+    const int KK = K * K;
+    const float cs = cosf(k.theta), sn = sinf(k.theta);
+    float w[DG_PER_LANE], part = 0.f;
+#pragma unroll
+    for (int m = 0; m < DG_PER_LANE; ++m) {
+        const int i = lane + 64 * m;
+        w[m] = i < KK ? mix_weight(i, K, k, cs, sn) : 0.f;
+        part += w[m];
+    }
+    const float sum = wave_sum(part);
+#pragma unroll
+    for (int m = 0; m < DG_PER_LANE; ++m)
+        if (lane + 64 * m < KK) dst[lane + 64 * m] = w[m] / sum;
+}
+
+static void mix_kernel_host(const MixKernel& k, int K, float* dst) {
+    const int KK = K * K;
+    const float cs = cosf(k.theta), sn = sinf(k.theta);
+    float wk[DG_KMAX * DG_KMAX];
+    for (int i = 0; i < KK; ++i) wk[i] = mix_weight(i, K, k, cs, sn);
+    const float sum = degrade_sum_host(wk, KK);
+    for (int i = 0; i < KK; ++i) dst[i] = wk[i] / sum;
+}
+
+// One workgroup, the step protocol of sisr_philox.h.  One wave per sample (b = wave, wave + 4, ..): no LDS, no further barrier.
 __global__ void __launch_bounds__(SISR_BLOCK) degrade_draw_kernel(int64_t* __restrict__ step, DegradeDrawArgs a,
                                                                    float* __restrict__ kernels, float* __restrict__ noise_sigma,
                                                                    int64_t* __restrict__ drawn_step) {
-    const int64_t t = *step;
-    __syncthreads();
-    if (threadIdx.x == 0) { *step = t + 1; drawn_step[0] = t; }
+    const int64_t t = draw_step_read(step);
+    draw_step_advance(step, t, drawn_step);
     const int KK = a.K * a.K, lane = threadIdx.x & 63;
     for (int b = threadIdx.x >> 6; b < a.B; b += SISR_BLOCK / 64) {
-        float p[4], w[DG_PER_LANE];
+        float p[4];
         degrade_draw_params(a, t, b, p);
-        const float cs = cosf(p[2]), sn = sinf(p[2]);
-        float part = 0.f;
-#pragma unroll
-        for (int m = 0; m < DG_PER_LANE; ++m) {
-            const int i = lane + 64 * m;
-            w[m] = i < KK ? degrade_weight(i, a.K, p, cs, sn) : 0.f;
-            part += w[m];
-        }
-        const float sum = wave_sum(part);
-#pragma unroll
-        for (int m = 0; m < DG_PER_LANE; ++m)
-            if (lane + 64 * m < KK) kernels[(int64_t)b * KK + lane + 64 * m] = w[m] / sum;
+        mix_store_kernel(degrade_gaussian(a.K, p), a.K, lane, kernels + (int64_t)b * KK);
         if (lane == 0) noise_sigma[b] = p[3];
     }
 }
@@ -467,14 +511,10 @@ extern "C" int sisr_degrade_params_host(int64_t t, uint64_t seed, int32_t rank, 
                                         float* noise_sigma_host, float* params_host) {
     const DegradeDrawArgs a = {seed, rank, B, K, anisotropic != 0, sigma_lo, sigma_hi, noise_lo, noise_hi};
     if (!kernels_host || !noise_sigma_host || t < 0 || !degrade_draw_args_ok(a)) return SISR_E_BADARG;
-    const int KK = K * K;
     for (int b = 0; b < B; ++b) {
-        float p[4], wk[DG_KMAX * DG_KMAX];
+        float p[4];
         degrade_draw_params(a, t, b, p);
-        const float cs = cosf(p[2]), sn = sinf(p[2]);
-        for (int i = 0; i < KK; ++i) wk[i] = degrade_weight(i, K, p, cs, sn);
-        const float sum = degrade_sum_host(wk, KK);
-        for (int i = 0; i < KK; ++i) kernels_host[(int64_t)b * KK + i] = wk[i] / sum;
+        mix_kernel_host(degrade_gaussian(K, p), K, kernels_host + (int64_t)b * K * K);
         noise_sigma_host[b] = p[3];
         if (params_host)
             for (int i = 0; i < 4; ++i) params_host[4 * (int64_t)b + i] = p[i];
@@ -483,7 +523,7 @@ extern "C" int sisr_degrade_params_host(int64_t t, uint64_t seed, int32_t rank, 
 }
 
 extern "C" int sisr_degrade_noise_host(int64_t t, uint64_t seed, int32_t rank, int64_t first, int64_t count, float* z_host) {
-    if (!z_host || t < 0 || rank < 0 || rank >= 65536 || first < 0 || count < 1) return SISR_E_BADARG;
+    if (!z_host || t < 0 || rank < 0 || rank >= DRAW_RANK_LIMIT || first < 0 || count < 1) return SISR_E_BADARG;
     if (first + count > ((int64_t)1 << 34)) return SISR_E_TOOBIG;
     for (int64_t i = 0; i < count; ++i) z_host[i] = degrade_noise_z(seed, t, rank, first + i);
     return 0;
@@ -492,7 +532,7 @@ extern "C" int sisr_degrade_noise_host(int64_t t, uint64_t seed, int32_t rank, i
 extern "C" int sisr_degrade_fwd(const float* x, const float* kernels, const float* noise_sigma, const int64_t* step_dev, uint64_t seed,
                                 int32_t rank, float* y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t K, int32_t h, int32_t w,
                                 int32_t clampv, void* stream) {
-    if (!x || !kernels || !y || (noise_sigma && !step_dev) || !degrade_shape_ok(N, C, H, W, K, h, w) || rank < 0 || rank >= 65536)
+    if (!x || !kernels || !y || (noise_sigma && !step_dev) || !degrade_shape_ok(N, C, H, W, K, h, w) || rank < 0 || rank >= DRAW_RANK_LIMIT)
         return SISR_E_BADARG;
     if ((int64_t)N * C * h * w >= ((int64_t)1 << 34)) return SISR_E_TOOBIG;
     if ((int64_t)N * C > 65535 || ((int64_t)h + DG_TILE_MAX - 1) / DG_TILE_MAX > 65535) return SISR_E_TOOBIG;      // grid.z, grid.y (before the plan walks the tiles)
@@ -517,21 +557,10 @@ extern "C" int sisr_degrade_bwd(const float* dy, const float* y_saved, const flo
 }
 
 // ==== second-order degradation: the mixed kernel draw and the noise operator =================================
-// Draws of sample b at step t: four counters {t low, t high, b, tag | rank}, u_i = dg_uniform(r_i); an event of probability p
-// happens when u <= p (u is in (0, 1]: p = 1 always, p = 0 never).
-//   0xFE04  u0 blur on (blur_prob)   u1 k_eff = ksize_min + 2 min((int)(m u1), m - 1), m = (K - ksize_min) / 2 + 1
-//           u2 family sinc (sinc_prob)   u3 otherwise the first family i with u3 <= kernel_probs[0] + .. + kernel_probs[i]
-//   0xFE05  u0 sigma1   u1 sigma2   u2 theta = pi u2   u3 beta (the generalised range or the plateau range, by family)
-//   0xFE06  u0 omega   u1 noise mode gaussian (gaussian_prob), else shot   u2 grey (grey_prob)   u3 amplitude (the mode's range)
-//   0xFE07  the final filter: u0 sinc (final_sinc_prob), else delta   u1 its k_eff   u2 its omega
-// and 0xFE08 tags the grey noise (one z per pixel).  Everything is drawn whatever the earlier draws decided; a parameter the
+// Draws of sample b at step t: the four counters {t low, t high, b, DRAW_TAG_MIX_A .. _FINAL | rank} (which word decides what: the
+// enum's comments, DESIGN.md section 25's table, mix_draw_sample), u_i = draw_uniform(r_i); an event of probability p happens when
+// u <= p (u is in (0, 1]: p = 1 always, p = 0 never).  Everything is drawn whatever the earlier draws decided; a parameter the
 // family does not use is stored as 0 (beta, omega), the iso forms and sinc store sigma2 = sigma1, theta = 0.
-#define DG_TAG_MIX_A 0xFE040000u
-#define DG_TAG_MIX_B 0xFE050000u
-#define DG_TAG_MIX_C 0xFE060000u
-#define DG_TAG_MIX_FINAL 0xFE070000u
-#define DG_TAG_NOISE_GREY 0xFE080000u
-#define DG_FAMILY_SINC 6                          // 0 .. 5 index kernel_probs: iso, aniso, generalized_iso / _aniso, plateau_iso / _aniso
 #define DG_MIX_BLOCK 512                          // the draw's one workgroup: 8 waves, 8 samples at a time (222 VGPRs: 1024 threads would spill)
 #define DG_NOISE_NONE 0
 #define DG_NOISE_GAUSSIAN 1
@@ -543,44 +572,10 @@ struct MixDrawArgs {
     SisrDegradeMix m;
 };
 
-struct MixKernel {                                 // one drawn kernel: params row = family, k_eff, sigma1, sigma2, theta, beta, omega, on
-    int family, k_eff, on;
-    float s1, s2, theta, beta, omega;
-};
-
-// Bessel J1 for x >= 0 in double (arguments reach pi sqrt(2) 10 = 44.4): below 12 the power series sum_k (-1)^k (x/2)^(2k+1) /
-// (k! (k+1)!) (largest term 4.2e3: 5e-13 of cancellation), from 12 on Hankel's expansion sqrt(2 / (pi x)) (P cos c - Q sin c),
-// c = x - 3 pi / 4, with a_k = a_(k-1) (4 - (2k - 1)^2) / (8 k): P = sum (-1)^j a_2j / x^2j, Q = sum (-1)^j a_(2j+1) / x^(2j+1),
-// twelve terms.  Within 1e-11 of the integral definition on [0, 47].
-__host__ __device__ __forceinline__ double dg_j1(double x) {
-    if (x < 12.0) {
-        const double h = 0.5 * x, h2 = h * h;
-        double term = h, sum = h;
-#pragma unroll
-        for (int k = 1; k <= 32; ++k) {
-            term *= h2 * (-1.0 / (double)(k * (k + 1)));          // (a constant per unrolled step: no division at run time)
-            sum += term;
-        }
-        return sum;
-    }
-    const double inv = 1.0 / x;
-    double t = 1.0, P = 1.0, Q = 0.0;
-#pragma unroll
-    for (int k = 1; k <= 12; ++k) {
-        t *= ((4.0 - (double)((2 * k - 1) * (2 * k - 1))) / (8.0 * (double)k)) * inv;
-        const double s = ((k >> 1) & 1) ? -t : t;
-        if (k & 1) Q += s;
-        else P += s;
-    }
-    const double c = x - 2.35619449019234492885;
-    return sqrt(0.63661977236758134308 / x) * (P * cos(c) - Q * sin(c));
-}
-
 __host__ __device__ __forceinline__ void mix_philox(const MixDrawArgs& a, int64_t t, int b, uint32_t tag, float u[4]) {
-    const uint32_t ctr[4] = {(uint32_t)((uint64_t)t & 0xFFFFFFFFu), (uint32_t)((uint64_t)t >> 32), (uint32_t)b, tag | (uint32_t)a.rank};
     uint32_t r[4];
-    philox4x32_10(ctr, (uint32_t)(a.seed & 0xFFFFFFFFu), (uint32_t)(a.seed >> 32), r);
-    for (int i = 0; i < 4; ++i) u[i] = dg_uniform(r[i]);
+    draw_words(a.seed, t, (uint32_t)b, tag | (uint32_t)a.rank, r);
+    for (int i = 0; i < 4; ++i) u[i] = draw_uniform(r[i]);
 }
 
 __host__ __device__ __forceinline__ int mix_k_eff(const SisrDegradeMix& m, float u) {
@@ -596,22 +591,13 @@ __host__ __device__ __forceinline__ float mix_omega(int k_eff, float u) {
 __host__ __device__ __forceinline__ void mix_draw_sample(const MixDrawArgs& a, int64_t t, int b, MixKernel& k, MixKernel& f, float noise[4]) {
     const SisrDegradeMix& m = a.m;
     float ua[4], ub[4], uc[4], uf[4];
-    mix_philox(a, t, b, DG_TAG_MIX_A, ua);
-    mix_philox(a, t, b, DG_TAG_MIX_B, ub);
-    mix_philox(a, t, b, DG_TAG_MIX_C, uc);
-    mix_philox(a, t, b, DG_TAG_MIX_FINAL, uf);
+    mix_philox(a, t, b, DRAW_TAG_MIX_A, ua);
+    mix_philox(a, t, b, DRAW_TAG_MIX_B, ub);
+    mix_philox(a, t, b, DRAW_TAG_MIX_C, uc);
+    mix_philox(a, t, b, DRAW_TAG_MIX_FINAL, uf);
     k.on = ua[0] <= m.blur_prob;
     k.k_eff = mix_k_eff(m, ua[1]);
-    k.family = DG_FAMILY_SINC;
-    if (!(ua[2] <= m.sinc_prob)) {
-        float c = 0.f;
-        k.family = 0;
-        for (int i = 0; i < 6; ++i) {
-            if (m.kernel_probs[i] > 0.f) k.family = i;          // (u3 above the rounded sum: the last family that can be drawn)
-            c += m.kernel_probs[i];
-            if (m.kernel_probs[i] > 0.f && ua[3] <= c) break;
-        }
-    }
+    k.family = ua[2] <= m.sinc_prob ? DG_FAMILY_SINC : draw_pick(m.kernel_probs, 6, ua[3]);
     const bool aniso = k.family == 1 || k.family == 3 || k.family == 5;
     k.s1 = m.sigma_lo + (m.sigma_hi - m.sigma_lo) * ub[0];
     k.s2 = aniso ? m.sigma_lo + (m.sigma_hi - m.sigma_lo) * ub[1] : k.s1;
@@ -634,26 +620,6 @@ __host__ __device__ __forceinline__ void mix_draw_sample(const MixDrawArgs& a, i
     f.theta = f.beta = 0.f;
 }
 
-// unnormalised weight of tap i = (dy + R) K + (dx + R); cs, sn = cosf, sinf of theta
-__host__ __device__ __forceinline__ float mix_weight(int i, int K, const MixKernel& k, float cs, float sn) {
-    const int R = (K - 1) / 2, Re = (k.k_eff - 1) / 2;
-    const int iy = i / K - R, ix = i % K - R;
-    if (!k.on) return iy == 0 && ix == 0 ? 1.f : 0.f;
-    if (iy < -Re || iy > Re || ix < -Re || ix > Re) return 0.f;
-    if (k.family == DG_FAMILY_SINC) {
-        const double w = (double)k.omega;
-        if (iy == 0 && ix == 0) return (float)(w * w / (4.0 * 3.14159265358979323846));
-        const double r = sqrt((double)(ix * ix + iy * iy));
-        return (float)(w * dg_j1(w * r) / (2.0 * 3.14159265358979323846 * r));
-    }
-    const float dy = (float)iy, dx = (float)ix;
-    const float u = cs * dx + sn * dy, v = -sn * dx + cs * dy;
-    const float q = u * u / (k.s1 * k.s1) + v * v / (k.s2 * k.s2);
-    if (k.family < 2) return expf(-0.5f * q);
-    const float qb = powf(q, k.beta);
-    return k.family < 4 ? expf(-0.5f * qb) : 1.f / (qb + 1.f);
-}
-
 __host__ __device__ __forceinline__ void mix_params_row(const MixKernel& k, float p[8]) {
     p[0] = (float)k.family; p[1] = (float)k.k_eff; p[2] = k.s1; p[3] = k.s2;
     p[4] = k.theta; p[5] = k.beta; p[6] = k.omega; p[7] = (float)k.on;
@@ -664,7 +630,7 @@ static bool mix_range_ok(float lo, float hi, bool positive) { return (positive ?
 static bool mix_args_ok(const MixDrawArgs& a) {
     const SisrDegradeMix& m = a.m;
     if (a.B < 1 || m.K < 1 || m.K > DG_KMAX || !(m.K & 1) || m.ksize_min < 1 || m.ksize_min > m.K || !(m.ksize_min & 1)) return false;
-    if (a.rank < 0 || a.rank >= 65536) return false;
+    if (a.rank < 0 || a.rank >= DRAW_RANK_LIMIT) return false;
     if (!mix_prob_ok(m.blur_prob) || !mix_prob_ok(m.sinc_prob) || !mix_prob_ok(m.gaussian_prob) || !mix_prob_ok(m.grey_prob) ||
         !mix_prob_ok(m.final_sinc_prob))
         return false;
@@ -679,30 +645,12 @@ static bool mix_args_ok(const MixDrawArgs& a) {
            mix_range_ok(m.shot_lo, m.shot_hi, false);
 }
 
-// one kernel of one sample by one wave: the weights 7 to a lane, their sum in degrade_sum_host's order, the normalised store
-__device__ __forceinline__ void mix_store_kernel(const MixKernel& k, int K, int lane, float* __restrict__ dst) {
-    const int KK = K * K;
-    const float cs = cosf(k.theta), sn = sinf(k.theta);
-    float w[DG_PER_LANE], part = 0.f;
-#pragma unroll
-    for (int m = 0; m < DG_PER_LANE; ++m) {
-        const int i = lane + 64 * m;
-        w[m] = i < KK ? mix_weight(i, K, k, cs, sn) : 0.f;
-        part += w[m];
-    }
-    const float sum = wave_sum(part);
-#pragma unroll
-    for (int m = 0; m < DG_PER_LANE; ++m)
-        if (lane + 64 * m < KK) dst[lane + 64 * m] = w[m] / sum;
-}
-
-// degrade_draw_kernel's pattern: one workgroup, the count read before the barrier and stored behind it, one wave per sample
+// degrade_draw_kernel's pattern: one workgroup, the step protocol, one wave per sample
 __global__ void __launch_bounds__(DG_MIX_BLOCK) degrade_draw_mix_kernel(int64_t* __restrict__ step, MixDrawArgs a, float* __restrict__ kernels,
                                                                        float* __restrict__ final_kernels, float* __restrict__ params,
                                                                        float* __restrict__ noise_table, int64_t* __restrict__ drawn_step) {
-    const int64_t t = *step;
-    __syncthreads();
-    if (threadIdx.x == 0) { *step = t + 1; drawn_step[0] = t; }
+    const int64_t t = draw_step_read(step);
+    draw_step_advance(step, t, drawn_step);
     const int KK = a.m.K * a.m.K, lane = threadIdx.x & 63;
     for (int b = threadIdx.x >> 6; b < a.B; b += DG_MIX_BLOCK / 64) {
         MixKernel k, f;
@@ -718,15 +666,6 @@ __global__ void __launch_bounds__(DG_MIX_BLOCK) degrade_draw_mix_kernel(int64_t*
             for (int i = 0; i < 4; ++i) noise_table[4 * (int64_t)b + i] = noise[i];
         }
     }
-}
-
-static void mix_kernel_host(const MixKernel& k, int K, float* dst) {
-    const int KK = K * K;
-    const float cs = cosf(k.theta), sn = sinf(k.theta);
-    float wk[DG_KMAX * DG_KMAX];
-    for (int i = 0; i < KK; ++i) wk[i] = mix_weight(i, K, k, cs, sn);
-    const float sum = degrade_sum_host(wk, KK);
-    for (int i = 0; i < KK; ++i) dst[i] = wk[i] / sum;
 }
 
 extern "C" int sisr_degrade_mix_bytes(void) { return (int)sizeof(SisrDegradeMix); }
@@ -760,9 +699,9 @@ extern "C" int sisr_degrade_mix_host(int64_t t, uint64_t seed, int32_t rank, int
 }
 
 extern "C" int sisr_degrade_noise_grey_host(int64_t t, uint64_t seed, int32_t rank, int64_t first, int64_t count, float* z_host) {
-    if (!z_host || t < 0 || rank < 0 || rank >= 65536 || first < 0 || count < 1) return SISR_E_BADARG;
+    if (!z_host || t < 0 || rank < 0 || rank >= DRAW_RANK_LIMIT || first < 0 || count < 1) return SISR_E_BADARG;
     if (first + count > ((int64_t)1 << 34)) return SISR_E_TOOBIG;
-    for (int64_t i = 0; i < count; ++i) z_host[i] = degrade_noise_z_tagged(seed, t, DG_TAG_NOISE_GREY | (uint32_t)rank, first + i);
+    for (int64_t i = 0; i < count; ++i) z_host[i] = degrade_noise_z_tagged(seed, t, DRAW_TAG_NOISE_GREY | (uint32_t)rank, first + i);
     return 0;
 }
 
@@ -777,7 +716,7 @@ struct DegradeNoiseArgs {
 };
 
 // One thread per pixel (n, p), grid-stride: its C values, the sample's row {mode, grey, amplitude}.  Colour: z of element
-// (n C + c) hw + p from the stream of sisr_degrade_fwd; grey: one z of pixel n hw + p under DG_TAG_NOISE_GREY, v = the luma.
+// (n C + c) hw + p from the stream of sisr_degrade_fwd; grey: one z of pixel n hw + p under DRAW_TAG_NOISE_GREY, v = the luma.
 __global__ void __launch_bounds__(SISR_BLOCK) degrade_noise_fwd_kernel(DegradeNoiseArgs a) {
     const int64_t t = *a.step;
     for (int64_t i = (int64_t)blockIdx.x * SISR_BLOCK + threadIdx.x; i < a.pixels; i += (int64_t)gridDim.x * SISR_BLOCK) {
@@ -790,7 +729,7 @@ __global__ void __launch_bounds__(SISR_BLOCK) degrade_noise_fwd_kernel(DegradeNo
         for (int c = 0; c < 4; ++c) v[c] = c < a.C ? a.x[base + c * a.hw] : 0.f;
         if (mode != DG_NOISE_NONE && grey) {
             const float l = a.C == 3 ? 0.299f * v[0] + 0.587f * v[1] + 0.114f * v[2] : (v[0] + v[1] + v[2] + v[3]) / (float)a.C;
-            const float z = degrade_noise_z_tagged(a.seed, t, DG_TAG_NOISE_GREY | (uint32_t)a.rank, i);
+            const float z = degrade_noise_z_tagged(a.seed, t, DRAW_TAG_NOISE_GREY | (uint32_t)a.rank, i);
             const float g = mode == DG_NOISE_GAUSSIAN ? amp * z : amp * 0.125f * sqrtf(fminf(fmaxf((l + 1.f) * 0.5f, 0.f), 1.f)) * z;
 #pragma unroll
             for (int c = 0; c < 4; ++c) nz[c] = g;
@@ -830,7 +769,7 @@ static bool degrade_noise_shape_ok(int N, int C, int h, int w) { return N >= 1 &
 
 extern "C" int sisr_degrade_noise_fwd(const float* x, const float* noise_table, const int64_t* step_dev, uint64_t seed, int32_t rank,
                                       float* y, int32_t N, int32_t C, int32_t h, int32_t w, int32_t clampv, void* stream) {
-    if (!x || !noise_table || !step_dev || !y || !degrade_noise_shape_ok(N, C, h, w) || rank < 0 || rank >= 65536) return SISR_E_BADARG;
+    if (!x || !noise_table || !step_dev || !y || !degrade_noise_shape_ok(N, C, h, w) || rank < 0 || rank >= DRAW_RANK_LIMIT) return SISR_E_BADARG;
     if ((int64_t)N * C * h * w >= ((int64_t)1 << 34)) return SISR_E_TOOBIG;
     const int64_t hw = (int64_t)h * w;
     const DegradeNoiseArgs a = {x, noise_table, step_dev, y, seed, rank, C, clampv, hw, (int64_t)N * hw};

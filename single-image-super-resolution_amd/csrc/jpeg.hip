@@ -8,14 +8,12 @@
 //                       coefficient ('cubic' recomputes u from the saved input in a second set of planes, in double), the replicate pad folded
 //                       onto the last row / column.  Gather form, fixed order, no atomics: the same bits on every call.
 // The +128 of Cb / Cr and the -128 in front of the DCT cancel and are not executed; luma is carried as Y - 128 between the colour
-// transforms.  Quality draw: Philox4x32-10 keyed by the seed (sisr_philox.h), word 3 of the counter 0xFE030000 | rank -- a tag no
-// other counter in the tree uses (degrade.hip: 0xFE01xxxx, 0xFE02xxxx; patchsrc.hip: ranks < 2^31, tags >= 0xFFFFFFE7).  One text
-// for host and device (sisr_jpeg_tables_host).  Plain vector stores only.
+// transforms.  Quality draw: Philox4x32-10 keyed by the seed, word 3 of the counter DRAW_TAG_QUALITY | rank (sisr_philox.h).  One
+// text for host and device (sisr_jpeg_tables_host).  Plain vector stores only.
 #include "sisr_dev.h"
 #include "sisr_philox.h"
 
-#define JP_TAG_QUALITY 0xFE030000u
-#define JP_TH 16                       // tile: 16 rows x 64 columns = 2 x 8 blocks, 1 x 4 MCUs of 4:2:0
+#define JP_TH 16                      // tile: 16 rows x 64 columns = 2 x 8 blocks, 1 x 4 MCUs of 4:2:0
 #define JP_TW 64
 #define JP_P 65                        // row pitch (floats): 65 mod 32 = 1, see jp_row_pass
 #define JP_PLANE (JP_TH * JP_P)
@@ -28,14 +26,11 @@ struct JpegDrawArgs {
     int rank, B, qlo, qhi;
 };
 
-// q = min(qlo + (int)((qhi - qlo + 1) u0), qhi), u0 = ((r0 >> 8) + 0.5) 2^-24 in fp32 (the uniform of degrade.hip)
+// q = min(qlo + (int)((qhi - qlo + 1) u0), qhi) in fp32, u0 = draw_uniform(r0)
 __host__ __device__ __forceinline__ int jpeg_draw_quality(const JpegDrawArgs& a, int64_t t, int b) {
-    const uint32_t ctr[4] = {(uint32_t)((uint64_t)t & 0xFFFFFFFFu), (uint32_t)((uint64_t)t >> 32), (uint32_t)b,
-                             JP_TAG_QUALITY | (uint32_t)a.rank};
     uint32_t r[4];
-    philox4x32_10(ctr, (uint32_t)(a.seed & 0xFFFFFFFFu), (uint32_t)(a.seed >> 32), r);
-    const float u0 = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const int q = a.qlo + (int)((float)(a.qhi - a.qlo + 1) * u0);
+    draw_words(a.seed, t, (uint32_t)b, DRAW_TAG_QUALITY | (uint32_t)a.rank, r);
+    const int q = a.qlo + (int)((float)(a.qhi - a.qlo + 1) * draw_uniform(r[0]));
     return q < a.qhi ? q : a.qhi;
 }
 
@@ -52,7 +47,7 @@ __host__ __device__ __forceinline__ int jpeg_table_entry(int q, int tab, int i) 
 }
 
 static bool jpeg_draw_args_ok(const JpegDrawArgs& a) {
-    return a.B >= 1 && a.rank >= 0 && a.rank < 65536 && a.qlo >= 1 && a.qhi <= 100 && a.qlo <= a.qhi;
+    return a.B >= 1 && a.rank >= 0 && a.rank < DRAW_RANK_LIMIT && a.qlo >= 1 && a.qhi <= 100 && a.qlo <= a.qhi;
 }
 
 // One workgroup; the step count is only read (the launch shares the step that sisr_degrade_draw stored in drawn_step)

@@ -15,7 +15,6 @@
 #define PATCH_ORDER_RANDOM 0
 #define PATCH_ORDER_SEQUENTIAL 1
 #define PATCH_ORDER_PERMUTED 2
-#define PATCH_PERM_ROUNDS 24
 
 struct PatchDrawArgs {
     uint64_t seed;
@@ -24,24 +23,21 @@ struct PatchDrawArgs {
 
 // sigma_e(x): the swap-or-not shuffle (Hoang, Morris, Rogaway, CRYPTO 2012) of [0, M), keyed by the seed and the epoch e alone.
 // Round r pairs x with its partner x' = K_r - x (mod M) and one bit, drawn for the pair's larger member, decides whether the two
-// trade places: an involution per round, so a bijection for every M, with a fixed trip count.  The counter tags 0xFFFFFFFF and
-// 0xFFFFFFFE - r sit above every rank (word 3 of a sample's counter, < 2^31): no word is shared with a sample's draw.
+// trade places: an involution per round, so a bijection for every M, with a fixed trip count.  Both draws are counted by the epoch
+// in place of the step and tagged DRAW_TAG_PERM_KEY / DRAW_TAG_PERM_BIT - r (sisr_philox.h): no word is shared with a sample's draw.
 // K_r belongs to the epoch, not to x: patch_perm_key is computed once per round (ks[r]) and every position walks the same 24.
 __host__ __device__ __forceinline__ uint32_t patch_perm_key(uint64_t seed, int64_t e, uint32_t r, uint32_t M) {
-    const uint32_t ck[4] = {(uint32_t)((uint64_t)e & 0xFFFFFFFFu), (uint32_t)((uint64_t)e >> 32), r, 0xFFFFFFFFu};
     uint32_t o[4];
-    philox4x32_10(ck, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), o);
+    draw_words(seed, e, r, DRAW_TAG_PERM_KEY, o);
     return patch_mulhi32(o[0], M);
 }
 
 __host__ __device__ __forceinline__ uint32_t patch_permute(uint64_t seed, int64_t e, const uint32_t* ks, uint32_t x, uint32_t M) {
-    const uint32_t e0 = (uint32_t)((uint64_t)e & 0xFFFFFFFFu), e1 = (uint32_t)((uint64_t)e >> 32);
     for (uint32_t r = 0; r < PATCH_PERM_ROUNDS; ++r) {
         uint32_t xp = ks[r] + M - x;                 // in [1, 2 M): M < 2^31, no wrap
         if (xp >= M) xp -= M;
-        const uint32_t cb[4] = {e0, e1, xp > x ? xp : x, 0xFFFFFFFEu - r};
         uint32_t o[4];
-        philox4x32_10(cb, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), o);
+        draw_words(seed, e, xp > x ? xp : x, DRAW_TAG_PERM_BIT - r, o);
         if (o[0] & 1u) x = xp;
     }
     return x;
@@ -55,9 +51,8 @@ __host__ __device__ __forceinline__ int64_t patch_epoch_batches(const PatchDrawA
 // the host refuses where it can see the table, has range 1.  ks: the round keys of step t's epoch, read in permuted order only
 __host__ __device__ __forceinline__ void patch_draw_row(const PatchDrawArgs& a, const SisrImageRec* table, const uint32_t* ks,
                                                         int64_t t, int b, int32_t* row) {
-    const uint32_t ctr[4] = {(uint32_t)((uint64_t)t & 0xFFFFFFFFu), (uint32_t)((uint64_t)t >> 32), (uint32_t)b, (uint32_t)a.rank};
     uint32_t r[4];
-    philox4x32_10(ctr, (uint32_t)(a.seed & 0xFFFFFFFFu), (uint32_t)(a.seed >> 32), r);
+    draw_words(a.seed, t, (uint32_t)b, (uint32_t)a.rank, r);
     int32_t index;
     if (a.order == PATCH_ORDER_RANDOM) {
         index = (int32_t)patch_mulhi32(r[0], (uint32_t)a.M);
@@ -85,17 +80,14 @@ static bool patch_draw_args_ok(const PatchDrawArgs& a, bool has_table, bool perm
     return a.order == PATCH_ORDER_RANDOM;
 }
 
-// One workgroup.  Every thread reads the count before the barrier, one thread stores count + 1 behind it: the only code that
-// touches the count, so a captured draw advances on every replay (as ema_prepare_kernel, optim.hip).  Permuted order: 24 threads
-// leave the epoch's round keys in LDS in front of the same barrier.
+// One workgroup, the step protocol of sisr_philox.h.  Permuted order: 24 threads leave the epoch's round keys in LDS before its barrier.
 __global__ void __launch_bounds__(SISR_BLOCK) patch_draw_kernel(int64_t* __restrict__ step, PatchDrawArgs a,
                                                                  const SisrImageRec* __restrict__ table, int32_t* __restrict__ draws) {
     __shared__ uint32_t ks[PATCH_PERM_ROUNDS];
-    const int64_t t = *step;
+    const int64_t t = draw_step_read(step);
     if (a.order == PATCH_ORDER_PERMUTED && threadIdx.x < PATCH_PERM_ROUNDS)
         ks[threadIdx.x] = patch_perm_key(a.seed, t / patch_epoch_batches(a), threadIdx.x, (uint32_t)a.M);
-    __syncthreads();
-    if (threadIdx.x == 0) *step = t + 1;
+    draw_step_advance(step, t, nullptr);
     for (int b = threadIdx.x; b < a.B; b += SISR_BLOCK) {
         int32_t row[4];
         patch_draw_row(a, table, ks, t, b, row);

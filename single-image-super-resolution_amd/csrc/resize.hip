@@ -12,7 +12,7 @@
 //                      element of dx stored: the same bits on every call.
 // The mode is uniform within a workgroup (one plane) and is branched on once (the passes are templates).  The host does not know it,
 // so the tile and the LDS plan are sized for the worst of the three modes at that ratio and halved until they fit RZ_LDS_BUDGET.
-// Mode draw: Philox4x32-10 keyed by the seed (sisr_philox.h), word 3 of the counter 0xFE090000 | rank.  Plain vector stores only.
+// Mode draw: Philox4x32-10 keyed by the seed (sisr_philox.h), word 3 of the counter DRAW_TAG_MODE | rank.  Plain vector stores only.
 #include "sisr_dev.h"
 #include "sisr_philox.h"
 #include "sisr_cubic.h"
@@ -20,7 +20,6 @@
 #include <algorithm>
 #include <cmath>
 
-#define RZ_TAG_MODE 0xFE090000u
 #define RZ_TH 16
 #define RZ_TW 64
 #define RZ_LDS_BUDGET (64 * 1024)
@@ -333,27 +332,17 @@ struct RzDrawArgs {
     float p[3];              // normalised: see rz_draw_args
 };
 
-// the first mode i with p_i > 0 and u0 <= p_0 + .. + p_i (fp32, added in index order); u0 above the rounded sum: the last mode that
-// can be drawn.  u0 = ((r0 >> 8) + 0.5) 2^-24 in fp32 (the uniform of degrade.hip)
+// draw_pick over the three weights on u0 = draw_uniform(r0)
 __host__ __device__ __forceinline__ int rz_draw_mode(const RzDrawArgs& a, int64_t t, int b) {
-    const uint32_t ctr[4] = {(uint32_t)((uint64_t)t & 0xFFFFFFFFu), (uint32_t)((uint64_t)t >> 32), (uint32_t)b, RZ_TAG_MODE | (uint32_t)a.rank};
     uint32_t r[4];
-    philox4x32_10(ctr, (uint32_t)(a.seed & 0xFFFFFFFFu), (uint32_t)(a.seed >> 32), r);
-    const float u0 = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    float c = 0.f;
-    int m = 0;
-    for (int i = 0; i < 3; ++i) {
-        if (a.p[i] > 0.f) m = i;
-        c += a.p[i];
-        if (a.p[i] > 0.f && u0 <= c) break;
-    }
-    return m;
+    draw_words(a.seed, t, (uint32_t)b, DRAW_TAG_MODE | (uint32_t)a.rank, r);
+    return draw_pick(a.p, 3, draw_uniform(r[0]));
 }
 
 // checks, and divides the three weights by their fp32 sum (p0 + p1) + p2
 static bool rz_draw_args(uint64_t seed, int rank, int B, float p0, float p1, float p2, RzDrawArgs& a) {
     const float p[3] = {p0, p1, p2};
-    if (B < 1 || rank < 0 || rank >= 65536) return false;
+    if (B < 1 || rank < 0 || rank >= DRAW_RANK_LIMIT) return false;
     for (int i = 0; i < 3; ++i)
         if (!std::isfinite(p[i]) || p[i] < 0.f) return false;
     const float s = (p0 + p1) + p2;

@@ -24,10 +24,11 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import jpeg as J
+from .draws import DrawStream, check_seed_rank, step_tensor
 from .engine import _stream, require_gpu_tensor
 
 KSIZE_MAX = 21
-RANK_LIMIT = 1 << 16
 
 
 def _check_ksize(ksize, who):
@@ -87,15 +88,12 @@ def degrade(img_hr, image_size_lr, kernels, noise_sigma=None, step=None, seed=0,
     if k.dim() != 3 or k.shape[0] != n or k.shape[1] != k.shape[2]:
         raise ValueError('degrade: kernels must be [N = %d, K, K] or [K, K], got %s' % (n, tuple(k.shape)))
     _check_ksize(k.shape[-1], 'degrade')
-    seed, rank = int(seed), int(rank)
-    if not 0 <= seed < 1 << 64 or not 0 <= rank < RANK_LIMIT:
-        raise ValueError('degrade: seed must be in [0, 2^64) and rank in [0, %d), got %d, %d' % (RANK_LIMIT, seed, rank))
+    seed, rank = check_seed_rank(seed, rank, 'degrade')
     if noise_sigma is not None:
         noise_sigma = torch.as_tensor(noise_sigma).to(device=x.device, dtype=torch.float32).contiguous()
         if noise_sigma.dim() != 1 or noise_sigma.shape[0] != n:
             raise ValueError('degrade: noise_sigma must be [N = %d], got %s' % (n, tuple(noise_sigma.shape)))
-        if not (isinstance(step, torch.Tensor) and step.is_cuda and step.dtype == torch.int64 and step.numel() == 1):
-            step = torch.full((), 0 if step is None else int(step), dtype=torch.int64, device=x.device)
+        step = step_tensor(step, x.device)
     else:
         step = None
     return _Degrade.apply(x, size, k.contiguous(), noise_sigma, step, seed, rank, bool(clamp))
@@ -118,13 +116,15 @@ def gaussian_kernels(sigma1, sigma2, theta, ksize):
     return torch.from_numpy(wgt / wgt.sum(axis=(1, 2), keepdims=True))
 
 
+def _check_range(r, who, name, positive):
+    lo, hi = float(r[0]), float(r[1])
+    if not ((0.0 < lo if positive else 0.0 <= lo) and lo <= hi < math.inf):
+        raise ValueError('%s: %s = (lo, hi) needs %s lo <= hi, got (%g, %g)' % (who, name, '0 <' if positive else '0 <=', lo, hi))
+    return lo, hi
+
+
 def _check_ranges(sigma, noise, who):
-    lo, hi, nlo, nhi = float(sigma[0]), float(sigma[1]), float(noise[0]), float(noise[1])
-    if not (0.0 < lo <= hi < math.inf):
-        raise ValueError('%s: sigma = (lo, hi) needs 0 < lo <= hi, got (%g, %g)' % (who, lo, hi))
-    if not (0.0 <= nlo <= nhi < math.inf):
-        raise ValueError('%s: noise = (lo, hi) needs 0 <= lo <= hi, got (%g, %g)' % (who, nlo, nhi))
-    return lo, hi, nlo, nhi
+    return _check_range(sigma, who, 'sigma', True) + _check_range(noise, who, 'noise', False)
 
 
 def expected_params(seed, t, B, ksize, sigma=(0.2, 3.0), anisotropic=True, noise=(0., 0.), rank=0):
@@ -151,7 +151,7 @@ def expected_noise(seed, t, first, count, rank=0, grey=False):
     return z
 
 
-class Degrader:
+class Degrader(DrawStream):
     """A new blur kernel and noise level per sample and per call, drawn on the device.
 
     ``sigma``        (lo, hi): the two standard deviations of the Gaussian kernel are uniform in it (``anisotropic=False``: one
@@ -174,23 +174,15 @@ class Degrader:
                  jpeg_subsampling='420', jpeg_grad='ste'):
         self.ksize = _check_ksize(ksize, 'Degrader')
         self.sigma_lo, self.sigma_hi, self.noise_lo, self.noise_hi = _check_ranges(sigma, noise, 'Degrader')
-        self.anisotropic, self.seed, self.rank = bool(anisotropic), int(seed), int(rank)
-        if not 0 <= self.seed < 1 << 64 or not 0 <= self.rank < RANK_LIMIT:
-            raise ValueError('Degrader: seed must be in [0, 2^64) and rank in [0, %d), got %d, %d' % (RANK_LIMIT, self.seed, self.rank))
+        self.anisotropic = bool(anisotropic)
         self.jpeg = None
         if jpeg is not None:
-            from . import jpeg as J
-            qlo, qhi = int(jpeg[0]), int(jpeg[1])
-            if not 1 <= qlo <= qhi <= 100:
-                raise ValueError('Degrader: jpeg = (qlo, qhi) needs 1 <= qlo <= qhi <= 100, got (%d, %d)' % (qlo, qhi))
+            self.jpeg = J.check_quality_range(jpeg, 'Degrader')
             if jpeg_subsampling not in J.SUBSAMPLING or jpeg_grad not in J.GRAD:
                 raise ValueError("Degrader: jpeg_subsampling is '444' or '420' and jpeg_grad 'ste' or 'cubic', got %r, %r"
                                  % (jpeg_subsampling, jpeg_grad))
-            self.jpeg, self.jpeg_subsampling, self.jpeg_grad = (qlo, qhi), jpeg_subsampling, jpeg_grad
-        dev = torch.device('cuda' if device is None else device)
-        if dev.type != 'cuda':
-            raise RuntimeError('Degrader: the draws live on the MI355X (got device %s); there is no CPU fallback' % dev)
-        self.step = torch.zeros((), dtype=torch.int64, device=dev)
+            self.jpeg_subsampling, self.jpeg_grad = jpeg_subsampling, jpeg_grad
+        self._init_stream(seed, rank, device)
         self.last_kernels = self.last_noise_sigma = self.last_drawn_step = self.last_quality = self.last_tables = None
 
     def draw(self, n):
@@ -211,38 +203,20 @@ class Degrader:
             raise RuntimeError('Degrader: the batch is on %s, the draws on %s' % (img_hr.device, self.step.device))
         k, s, t = self.draw(int(img_hr.shape[0]))
         noisy = self.noise_hi > 0.0
-        if self.jpeg is None:
-            return degrade(img_hr, image_size_lr, k, s if noisy else None, t if noisy else None, self.seed, self.rank, True)
-        tables = self.draw_jpeg_tables(int(img_hr.shape[0]), t)          # before the forward: the draws of a step stay together
+        # before the forward: the draws of a step stay together
+        tables = None if self.jpeg is None else self.draw_jpeg_tables(int(img_hr.shape[0]), t)
         lr = degrade(img_hr, image_size_lr, k, s if noisy else None, t if noisy else None, self.seed, self.rank, True)
-        from .jpeg import jpeg_roundtrip
-        return jpeg_roundtrip(lr, tables, self.jpeg_subsampling, self.jpeg_grad, True)
+        return lr if tables is None else J.jpeg_roundtrip(lr, tables, self.jpeg_subsampling, self.jpeg_grad, True)
 
     def draw_jpeg_tables(self, n, drawn_step):
         """the quantisation tables of step ``drawn_step`` (a 0-dim int64 device tensor, read and NOT advanced) for a batch of ``n``
         -> tables [n, 2, 8, 8] on the device; ``last_quality`` holds the qualities"""
-        dev = self.step.device
-        q = torch.empty(n, dtype=torch.int32, device=dev)
-        tables = torch.empty((n, 2, 8, 8), dtype=torch.float32, device=dev)
-        L.check(L.lib().sisr_jpeg_tables(drawn_step.data_ptr(), self.seed, self.rank, n, self.jpeg[0], self.jpeg[1], q.data_ptr(),
-                                         tables.data_ptr(), _stream()), 'sisr_jpeg_tables')
-        self.last_quality, self.last_tables = q, tables
-        return tables
+        self.last_quality, self.last_tables = J.draw_tables(drawn_step, self.seed, self.rank, n, *self.jpeg)
+        return self.last_tables
 
     def lr_from_hr(self, img_hr, image_size_lr, device='cpu'):
         """the reference's signature (utils.py:22-31; ``device`` is accepted and unused, as in utils.lr_from_hr)"""
         return self(img_hr, image_size_lr)
-
-    def state_dict(self):
-        return dict(seed=self.seed, rank=self.rank, step=self.step.clone())
-
-    def load_state_dict(self, state):
-        """copies the count INTO the existing tensor (a captured draw points at it)"""
-        seed, rank = int(state['seed']), int(state['rank'])
-        if not 0 <= seed < 1 << 64 or not 0 <= rank < RANK_LIMIT:
-            raise ValueError('Degrader.load_state_dict: seed must be in [0, 2^64) and rank in [0, %d), got %d, %d' % (RANK_LIMIT, seed, rank))
-        self.step.copy_(torch.as_tensor(state['step'], dtype=torch.int64).reshape(()))
-        self.seed, self.rank = seed, rank
 
 
 # ---- second-order degradation (DESIGN.md section 25) ------------------------------------------------------------------------------
@@ -255,13 +229,6 @@ def _check_prob(p, who, name):
     if not 0.0 <= p <= 1.0:
         raise ValueError('%s: %s must be a probability in [0, 1], got %g' % (who, name, p))
     return p
-
-
-def _check_range(r, who, name, positive):
-    lo, hi = float(r[0]), float(r[1])
-    if not ((0.0 < lo if positive else 0.0 <= lo) and lo <= hi < math.inf):
-        raise ValueError('%s: %s = (lo, hi) needs %s lo <= hi, got (%g, %g)' % (who, name, '0 <' if positive else '0 <=', lo, hi))
-    return lo, hi
 
 
 class DegradeStage:
@@ -294,12 +261,7 @@ class DegradeStage:
         self.beta_gaussian = _check_range(beta_gaussian, who, 'beta_gaussian', True)
         self.beta_plateau = _check_range(beta_plateau, who, 'beta_plateau', True)
         self.noise, self.shot = _check_range(noise, who, 'noise', False), _check_range(shot, who, 'shot', False)
-        self.jpeg = None
-        if jpeg is not None:
-            qlo, qhi = int(jpeg[0]), int(jpeg[1])
-            if not 1 <= qlo <= qhi <= 100:
-                raise ValueError('%s: jpeg = (qlo, qhi) needs 1 <= qlo <= qhi <= 100, got (%d, %d)' % (who, qlo, qhi))
-            self.jpeg = (qlo, qhi)
+        self.jpeg = None if jpeg is None else J.check_quality_range(jpeg, who)
 
     def c_struct(self, final_sinc_prob=None):
         """the settings as sisr_hip.h's SisrDegradeMix"""
@@ -366,18 +328,14 @@ def degrade_noise(x, noise_table, step, seed=0, rank=0, clamp=True):
         raise ValueError('degrade_noise: an fp32 [N, C, h, w] batch with 1 to 4 channels is expected, got %s %s' % (x.dtype, tuple(x.shape)))
     x = x.contiguous()
     n = x.shape[0]
-    seed, rank = int(seed), int(rank)
-    if not 0 <= seed < 1 << 64 or not 0 <= rank < RANK_LIMIT:
-        raise ValueError('degrade_noise: seed must be in [0, 2^64) and rank in [0, %d), got %d, %d' % (RANK_LIMIT, seed, rank))
+    seed, rank = check_seed_rank(seed, rank, 'degrade_noise')
     table = torch.as_tensor(noise_table).to(device=x.device, dtype=torch.float32).contiguous()
     if tuple(table.shape) != (n, 4):
         raise ValueError('degrade_noise: noise_table must be [N = %d, 4], got %s' % (n, tuple(table.shape)))
-    if not (isinstance(step, torch.Tensor) and step.is_cuda and step.dtype == torch.int64 and step.numel() == 1):
-        step = torch.full((), 0 if step is None else int(step), dtype=torch.int64, device=x.device)
-    return _DegradeNoise.apply(x, table, step, seed, rank, bool(clamp))
+    return _DegradeNoise.apply(x, table, step_tensor(step, x.device), seed, rank, bool(clamp))
 
 
-class HighOrderDegrader:
+class HighOrderDegrader(DrawStream):
     """The second-order degradation of Real-ESRGAN on the device: every stage draws a blur kernel from seven families, resamples,
     adds Gaussian or shot noise and compresses; the last stage also runs a sinc filter (ringing and overshoot).
 
@@ -409,7 +367,6 @@ class HighOrderDegrader:
 
     def __init__(self, stages=None, mid_size=None, mid_scale=None, final_sinc_prob=0.8, final_order='sinc_jpeg', seed=0, rank=0,
                  device=None, jpeg_subsampling='420', jpeg_grad='ste', resize_probs=None):
-        from . import jpeg as J
         who = 'HighOrderDegrader'
         self.resize_probs = None
         if resize_probs is not None:
@@ -433,13 +390,7 @@ class HighOrderDegrader:
             raise ValueError("%s: jpeg_subsampling is '444' or '420' and jpeg_grad 'ste' or 'cubic', got %r, %r"
                              % (who, jpeg_subsampling, jpeg_grad))
         self.final_order, self.jpeg_subsampling, self.jpeg_grad = final_order, jpeg_subsampling, jpeg_grad
-        self.seed, self.rank = int(seed), int(rank)
-        if not 0 <= self.seed < 1 << 64 or not 0 <= self.rank < RANK_LIMIT:
-            raise ValueError('%s: seed must be in [0, 2^64) and rank in [0, %d), got %d, %d' % (who, RANK_LIMIT, self.seed, self.rank))
-        dev = torch.device('cuda' if device is None else device)
-        if dev.type != 'cuda':
-            raise RuntimeError('%s: the draws live on the MI355X (got device %s); there is no CPU fallback' % (who, dev))
-        self.step = torch.zeros((), dtype=torch.int64, device=dev)
+        self._init_stream(seed, rank, device)
         self.calls = 0
         self._mix = [s.c_struct(self.final_sinc_prob if i == len(self.stages) - 1 else None) for i, s in enumerate(self.stages)]
         none = [None] * len(self.stages)
@@ -480,7 +431,6 @@ class HighOrderDegrader:
         return [mid] * (len(self.stages) - 1) + [size_lr]
 
     def __call__(self, img_hr, image_size_lr):
-        from .jpeg import jpeg_roundtrip
         require_gpu_tensor(img_hr, 'HighOrderDegrader input')
         if img_hr.device != self.step.device:
             raise RuntimeError('HighOrderDegrader: the batch is on %s, the draws on %s' % (img_hr.device, self.step.device))
@@ -493,16 +443,9 @@ class HighOrderDegrader:
         x = img_hr
         for i, st in enumerate(self.stages):
             k, fk, _, nt, t = self.draw_mix(i, n)
-            tables = None
-            if st.jpeg is not None:                                       # before the forward: the draws of a step stay together
-                q = torch.empty(n, dtype=torch.int32, device=x.device)
-                tables = torch.empty((n, 2, 8, 8), dtype=torch.float32, device=x.device)
-                L.check(L.lib().sisr_jpeg_tables(t.data_ptr(), self.seed, self.rank, n, st.jpeg[0], st.jpeg[1], q.data_ptr(),
-                                                 tables.data_ptr(), _stream()), 'sisr_jpeg_tables')
-                self.last_quality[i] = q
-            else:
-                self.last_quality[i] = None
-            self.last_tables[i], self.last_sizes[i] = tables, sizes[i]
+            # before the forward: the draws of a step stay together
+            q, tables = (None, None) if st.jpeg is None else J.draw_tables(t, self.seed, self.rank, n, *st.jpeg)
+            self.last_quality[i], self.last_tables[i], self.last_sizes[i] = q, tables, sizes[i]
             if self.resize_probs is None:
                 x = degrade(x, sizes[i], k, None, clamp=False)
             else:                                                         # a pure blur at the stage's input size, then the drawn resampler
@@ -514,23 +457,16 @@ class HighOrderDegrader:
             if fk is not None and self.final_order == 'sinc_jpeg':
                 x = degrade(x, sizes[i], fk, None, clamp=True)
             if tables is not None:
-                x = jpeg_roundtrip(x, tables, self.jpeg_subsampling, self.jpeg_grad, True)
+                x = J.jpeg_roundtrip(x, tables, self.jpeg_subsampling, self.jpeg_grad, True)
             if fk is not None and self.final_order == 'jpeg_sinc':
                 x = degrade(x, sizes[i], fk, None, clamp=True)
         return x
 
-    def lr_from_hr(self, img_hr, image_size_lr, device='cpu'):
-        """the reference's signature (utils.py:22-31; ``device`` is accepted and unused, as in utils.lr_from_hr)"""
-        return self(img_hr, image_size_lr)
+    lr_from_hr = Degrader.lr_from_hr                                       # the same adapter to the reference's signature
 
     def state_dict(self):
-        return dict(seed=self.seed, rank=self.rank, step=self.step.clone(), calls=self.calls)
+        return dict(super().state_dict(), calls=self.calls)
 
     def load_state_dict(self, state):
-        """copies the count INTO the existing tensor (a captured draw points at it)"""
-        seed, rank = int(state['seed']), int(state['rank'])
-        if not 0 <= seed < 1 << 64 or not 0 <= rank < RANK_LIMIT:
-            raise ValueError('HighOrderDegrader.load_state_dict: seed must be in [0, 2^64) and rank in [0, %d), got %d, %d'
-                             % (RANK_LIMIT, seed, rank))
-        self.step.copy_(torch.as_tensor(state['step'], dtype=torch.int64).reshape(()))
-        self.seed, self.rank, self.calls = seed, rank, int(state.get('calls', 0))
+        super().load_state_dict(state)
+        self.calls = int(state.get('calls', 0))

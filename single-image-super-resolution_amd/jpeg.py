@@ -15,12 +15,11 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .draws import TAG_QUALITY, check_seed_rank, draw_words, uniform24          # TAG_QUALITY: also this module's name for it
 from .engine import _stream, require_gpu_tensor
 
 SUBSAMPLING = {'444': L.JPEG_444, '420': L.JPEG_420}
 GRAD = {'ste': L.JPEG_GRAD_STE, 'cubic': L.JPEG_GRAD_CUBIC}
-TAG_QUALITY = 0xFE030000
-RANK_LIMIT = 1 << 16
 
 # ISO/IEC 10918-1 Annex K, tables K.1 (luminance) and K.2 (chrominance), row-major
 BASE_TABLES = np.array([
@@ -47,18 +46,31 @@ def quant_tables(q):
 
 
 def expected_quality(seed, t, B, qlo, qhi, rank=0):
-    """Host restatement of the quality draw of step ``t`` (sisr_jpeg_tables): Philox4x32-10 keyed by the seed, counter
-    {t low, t high, b, 0xFE030000 | rank}; u0 = ((r0 >> 8) + 0.5) 2^-24 and the product in fp32 -> int32 numpy array [B]."""
-    from .patches import philox4x32_10
-    B, qlo, qhi = int(B), _check_quality(qlo, 'expected_quality'), _check_quality(qhi, 'expected_quality')
-    seed, t, rank = int(seed), int(t), int(rank)
-    if B < 1 or t < 0 or qlo > qhi or not 0 <= rank < RANK_LIMIT or not 0 <= seed < 1 << 64:
-        raise ValueError('expected_quality: B >= 1, t >= 0, qlo <= qhi, rank in [0, %d) and seed in [0, 2^64) are expected' % RANK_LIMIT)
-    ctr = np.stack([np.full(B, t & 0xFFFFFFFF, np.uint64), np.full(B, (t >> 32) & 0xFFFFFFFF, np.uint64), np.arange(B, dtype=np.uint64),
-                    np.full(B, TAG_QUALITY | rank, np.uint64)], axis=-1)
-    r = philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
-    u0 = ((r[:, 0] >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24)
+    """Host restatement of the quality draw of step ``t`` (sisr_jpeg_tables): the first word of the counter tagged
+    TAG_QUALITY | rank (draws.py), u0 its 24-bit uniform and the product in fp32 -> int32 numpy array [B]."""
+    B, t, (qlo, qhi) = int(B), int(t), check_quality_range((qlo, qhi), 'expected_quality')
+    seed, rank = check_seed_rank(seed, rank, 'expected_quality')
+    if B < 1 or t < 0:
+        raise ValueError('expected_quality: B >= 1 and t >= 0 are expected, got %d, %d' % (B, t))
+    u0 = uniform24(draw_words(seed, t, np.arange(B), TAG_QUALITY | rank)[:, 0])
     return np.minimum(qlo + (np.float32(qhi - qlo + 1) * u0).astype(np.int32), qhi).astype(np.int32)
+
+
+def check_quality_range(jpeg, who):
+    qlo, qhi = int(jpeg[0]), int(jpeg[1])
+    if not 1 <= qlo <= qhi <= 100:
+        raise ValueError('%s: jpeg = (qlo, qhi) needs 1 <= qlo <= qhi <= 100, got (%d, %d)' % (who, qlo, qhi))
+    return qlo, qhi
+
+
+def draw_tables(drawn_step, seed, rank, n, qlo, qhi):
+    """One launch (sisr_jpeg_tables): the qualities and quantisation tables of a batch of ``n`` on the step held by ``drawn_step``
+    (a 0-dim int64 device tensor, read and NOT advanced) -> (quality [n] int32, tables [n, 2, 8, 8] fp32) on the device"""
+    q = torch.empty(n, dtype=torch.int32, device=drawn_step.device)
+    tables = torch.empty((n, 2, 8, 8), dtype=torch.float32, device=drawn_step.device)
+    L.check(L.lib().sisr_jpeg_tables(drawn_step.data_ptr(), seed, rank, n, qlo, qhi, q.data_ptr(), tables.data_ptr(), _stream()),
+            'sisr_jpeg_tables')
+    return q, tables
 
 
 class _JpegRoundTrip(torch.autograd.Function):

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .draws import TAG_PERM_BIT, TAG_PERM_KEY, check_seed, draw_words, philox4x32_10  # noqa: F401  (philox4x32_10: its old home)
 from .engine import _stream
 from .utils import lr_from_hr
 
@@ -82,21 +83,6 @@ ORDERS = {'random': 0, 'sequential': 1, 'permuted': 2}
 OP_HFLIP, OP_VFLIP, OP_TRANSPOSE = 1, 2, 4
 PERM_ROUNDS = 24
 IMAGE_REC = np.dtype([('offset', '<i8'), ('H', '<i4'), ('W', '<i4')])          # SisrImageRec (sisr_hip.h), 16 bytes
-_M32 = 0xFFFFFFFF
-
-
-def philox4x32_10(counter, key):
-    """Philox4x32-10 (Salmon et al., SC'11) in numpy.  counter: [..., 4], key: [..., 2] words (broadcast against each other) ->
-    [..., 4] uint32.  The host restatement of the generator in csrc/patchsrc.hip."""
-    c = np.asarray(counter, dtype=np.uint64) & _M32
-    k = np.asarray(key, dtype=np.uint64) & _M32
-    c0, c1, c2, c3 = (c[..., i] for i in range(4))
-    k0, k1 = k[..., 0], k[..., 1]
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2           # 32 x 32 -> 64 bits: exact in uint64
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _M32
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _M32, (k1 + np.uint64(0xBB67AE85)) & _M32
-    return np.stack(np.broadcast_arrays(c0, c1, c2, c3), axis=-1).astype(np.uint32)
 
 
 def _mulhi(a, n):
@@ -107,18 +93,14 @@ def permuted_index(seed, epoch, position, M):
     """Pure numpy: sigma_e(p), the swap-or-not shuffle of [0, M) (Hoang, Morris, Rogaway, CRYPTO 2012; sisr_hip.h spells out the
     rounds) keyed by ``seed`` and the epoch alone.  ``epoch`` and ``position`` are integer arrays that broadcast against each
     other -> int64 array of images.  The host restatement of patch_permute in csrc/patchsrc.hip."""
-    seed, M = int(seed), int(M)
+    seed, M = check_seed(seed, 'permuted_index'), int(M)
     e, x = np.broadcast_arrays(np.asarray(epoch, dtype=np.uint64), np.asarray(position, dtype=np.uint64))
-    if M < 1 or not 0 <= seed < 1 << 64 or (x >= np.uint64(M)).any():
-        raise ValueError('permuted_index: positions must lie in [0, M = %d) and seed in [0, 2^64)' % M)
-    key = np.array([seed & _M32, seed >> 32], dtype=np.uint64)
-    e0, e1 = e & _M32, e >> np.uint64(32)
-    rounds = np.arange(PERM_ROUNDS, dtype=np.uint64)
-    ctr = np.stack(np.broadcast_arrays(e0[..., None], e1[..., None], rounds, np.uint64(_M32)), axis=-1)
-    ks = _mulhi(philox4x32_10(ctr, key)[..., 0].astype(np.uint64), M)                     # [..., rounds]
+    if M < 1 or (x >= np.uint64(M)).any():
+        raise ValueError('permuted_index: positions must lie in [0, M = %d)' % M)
+    ks = _mulhi(draw_words(seed, e[..., None], np.arange(PERM_ROUNDS), TAG_PERM_KEY)[..., 0].astype(np.uint64), M)      # [..., rounds]
     for r in range(PERM_ROUNDS):
         xp = (ks[..., r] + np.uint64(M) - x) % np.uint64(M)
-        bit = philox4x32_10(np.stack([e0, e1, np.maximum(x, xp), np.full_like(e, _M32 - 1 - r)], axis=-1), key)[..., 0] & 1
+        bit = draw_words(seed, e, np.maximum(x, xp), TAG_PERM_BIT - r)[..., 0] & 1
         x = np.where(bit == 1, xp, x)
     return x.astype(np.int64)
 
@@ -160,16 +142,16 @@ def expected_draws(seed, t, B, M, H0, W0, h, w, ops_mask, order='random', rank=0
     """Pure numpy: the [B, 4] int32 draw table (index, y0, x0, ops) of step ``t`` -- what sisr_patch_draw / sisr_patch_draw_table
     write and sisr_patch_draws_host / sisr_patch_draws_table_host compute.  ``sizes``: [M, 2] (H, W) of a ragged dataset (H0 and
     W0 are then not read).  For audits and tests."""
-    seed, t = int(seed), int(t)
+    t = int(t)
     B, M, H0, W0, h, w, ops_mask, rank, world = (int(v) for v in (B, M, H0, W0, h, w, ops_mask, rank, world))
     if sizes is not None:
         sizes = _sizes_array(sizes, 'expected_draws')
     _check_draw_args(B, M, H0, W0, h, w, ops_mask, order, rank, world, 'expected_draws', sizes)
-    if t < 0 or not 0 <= seed < 1 << 64:
-        raise ValueError('expected_draws: t must be >= 0 and seed in [0, 2^64), got t %d, seed %d' % (t, seed))
+    seed = check_seed(seed, 'expected_draws')
+    if t < 0:
+        raise ValueError('expected_draws: t must be >= 0, got %d' % t)
     b = np.arange(B, dtype=np.uint64)
-    ctr = np.stack([np.full(B, t & _M32, np.uint64), np.full(B, (t >> 32) & _M32, np.uint64), b, np.full(B, rank, np.uint64)], axis=-1)
-    r = philox4x32_10(ctr, np.array([seed & _M32, seed >> 32], dtype=np.uint64)).astype(np.uint64)
+    r = draw_words(seed, t, b, rank).astype(np.uint64)
     if order == 'random':
         index = _mulhi(r[:, 0], M)
     else:
@@ -297,10 +279,9 @@ class _PatchSource:
         who = type(self).__name__
         self.C, self.B, self.window = C, int(batch_size), window
         self.ops_mask = (OP_HFLIP if hflip else 0) | (OP_VFLIP if vflip else 0) | (OP_TRANSPOSE if transpose else 0)
-        self.order, self.seed, self.rank, self.world = order, int(seed), int(rank), int(world)
+        self.order, self.rank, self.world = order, int(rank), int(world)
         self._check(order, self.rank, self.world, who)
-        if not 0 <= self.seed < 1 << 64:
-            raise ValueError('%s: seed must be in [0, 2^64), got %d' % (who, self.seed))
+        self.seed = check_seed(seed, who)
         if float(std) == 0.0:
             raise ValueError('%s: std must not be 0' % who)
         check_device()                                                     # after the checks that need the shape alone
@@ -376,10 +357,9 @@ class _PatchSource:
     def load_state_dict(self, state):
         """copies the count INTO the existing tensor (a captured draw points at it)"""
         who = type(self).__name__ + '.load_state_dict'
-        order, rank, world, seed = state['order'], int(state['rank']), int(state['world']), int(state['seed'])
+        order, rank, world = state['order'], int(state['rank']), int(state['world'])
         self._check(order, rank, world, who)
-        if not 0 <= seed < 1 << 64:
-            raise ValueError('%s: seed must be in [0, 2^64), got %d' % (who, seed))
+        seed = check_seed(state['seed'], who)
         self._step.copy_(torch.as_tensor(state['step_count'], dtype=torch.int64).reshape(()))
         self.order, self.rank, self.world, self.seed = order, rank, world, seed
 

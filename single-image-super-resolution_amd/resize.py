@@ -24,10 +24,10 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib as L
+from .draws import step_tensor
 from .engine import _stream, require_gpu_tensor
 
 MODES = ('area', 'bilinear', 'bicubic')          # the index is the code of the device table
-RANK_LIMIT = 1 << 16
 _TABLES = {}                                     # (code, N, device) -> the constant table of a mode given by name
 
 
@@ -78,8 +78,7 @@ def draw_resize_modes(drawn_step, seed, rank, B, probs):
     """One launch (sisr_resize_modes_draw): the modes of a batch of ``B`` on the step held by ``drawn_step`` (a 0-dim int64 device
     tensor, read and NOT advanced) -> int32 device tensor [B]"""
     p = _check_probs(probs, 'draw_resize_modes')
-    if not (isinstance(drawn_step, torch.Tensor) and drawn_step.is_cuda and drawn_step.dtype == torch.int64 and drawn_step.numel() == 1):
-        raise ValueError('draw_resize_modes: the step is a 0-dim int64 device tensor')
+    step_tensor(drawn_step, strict='draw_resize_modes')
     modes = torch.empty(int(B), dtype=torch.int32, device=drawn_step.device)
     L.check(L.lib().sisr_resize_modes_draw(drawn_step.data_ptr(), int(seed), int(rank), int(B), p[0], p[1], p[2], modes.data_ptr(),
                                            _stream()), 'sisr_resize_modes_draw')

@@ -18,12 +18,7 @@ def pkg(sub):
 
 def _uniforms(seed, t, index, tag, rank):
     """float64 u_i = ((r_i >> 8) + 0.5) 2^-24 of counters {t low, t high, index, tag | rank}: [len(index), 4]"""
-    P = pkg('patches')
-    index = np.asarray(index, dtype=np.uint64)
-    n = index.shape[0]
-    ctr = np.stack([np.full(n, t & 0xFFFFFFFF, np.uint64), np.full(n, (t >> 32) & 0xFFFFFFFF, np.uint64), index,
-                    np.full(n, tag | rank, np.uint64)], axis=-1)
-    r = P.philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+    r = pkg('draws').draw_words(seed, t, np.asarray(index, dtype=np.uint64), tag | rank)
     return ((r >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24
 
 

@@ -113,10 +113,7 @@ def _host_tables(t, seed, rank, B, qlo, qhi):
 
 def _quality_from_philox(seed, t, B, qlo, qhi, rank):
     """rebuilt here from the documented counter, the uniform in float64 (exact: 25 bits), the product rounded to fp32 as the kernel's"""
-    P = pkg('patches')
-    ctr = np.stack([np.full(B, t & 0xFFFFFFFF, np.uint64), np.full(B, (t >> 32) & 0xFFFFFFFF, np.uint64), np.arange(B, dtype=np.uint64),
-                    np.full(B, TAG_QUALITY | rank, np.uint64)], axis=-1)
-    r = P.philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+    r = pkg('draws').draw_words(seed, t, np.arange(B), TAG_QUALITY | rank)
     u0 = (((r[:, 0] >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24).astype(np.float32)
     return np.minimum(qlo + np.floor(np.float32(qhi - qlo + 1) * u0).astype(np.int64), qhi)
 

@@ -146,11 +146,8 @@ def test_weights_at_ratio_two_are_exact():
 def _draw_by_hand(seed, t, B, probs, rank):
     """the draw rebuilt from the numpy Philox on its counters: {t low, t high, b, 0xFE090000 | rank}, u0 = ((r0 >> 8) + 0.5) 2^-24,
     the weights divided by their fp32 sum, the first mode with p_i > 0 and u0 <= p_0 + .. + p_i"""
-    PH = pkg('patches')
     f32 = np.float32
-    b = np.arange(B, dtype=np.uint64)
-    ctr = np.stack([np.full(B, t & 0xFFFFFFFF, np.uint64), np.full(B, t >> 32, np.uint64), b, np.full(B, 0xFE090000 | rank, np.uint64)], -1)
-    r = PH.philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint64))
+    r = pkg('draws').draw_words(seed, t, np.arange(B), 0xFE090000 | rank)
     u0 = ((r[:, 0] >> 8).astype(f32) + f32(0.5)) * f32(1.0 / 16777216.0)
     w = [f32(v) for v in probs]
     s = f32(f32(w[0] + w[1]) + w[2])
