@@ -1043,6 +1043,47 @@ int sisr_artifact_fwd(const float *sr, const float *gt, const float *ema, int32_
 int sisr_artifact_bwd(const float *sr, const float *gt, const float *map, const float *g, int32_t N, int32_t C, int32_t H, int32_t W,
                       float weight, float *dsr, float *dgt, void *stream);
 
+/* ---- multi-tap perceptual loss with a Gram-matrix style term (BasicSR's PerceptualLoss), forward and backward.
+ *      fa, fb: fp32 [B][total], contiguous: the output layout of MaskedVGG.forward.  shapes: HOST array [n_taps][3] of (C, H, W) with
+ *      sum_l C_l H_l W_l == total; tap l is columns [off_l, off_l + C_l P_l) of every row in NCHW order, P_l = H_l W_l, F_x,l[n] that
+ *      slice as C_l x P_l.  layer_w: HOST array [n_taps].  Per tap, with crit one of SISR_PERCEP_L1 (mean |d|), SISR_PERCEP_L2
+ *      (mean d^2), SISR_PERCEP_FRO (sqrt(sum d^2) over the whole batch tensor of the tap):
+ *          T_l = crit(fa_l, fb_l)      G_x,l[n] = F_x,l[n] F_x,l[n]^T / (C_l P_l)      S_l = crit(G_a,l, G_b,l) over its B C_l^2 elements
+ *          perceptual = perceptual_weight sum_l w_l T_l          style = style_weight sum_l w_l S_l
+ *      A term whose weight is 0 is not computed: none of its launches happen and its outputs are not written.  The Gram products run
+ *      on v_mfma_f32_32x32x2_f32 (exact fp32 products), 32 x 32 tiles on or above the diagonal with the mirror stored from the same
+ *      sums (G is bit-symmetric), P split across workgroups with the partials added in split order; every reduction over a tensor is
+ *      a fixed-order sum in double.  No atomics, nothing read back by the host: the same bits on every call.  sign(0) = 0; a zero
+ *      Frobenius norm gives an all-zero gradient; a NaN in gives NaN terms.  SISR_E_BADARG before any HIP call for null pointers, a
+ *      workspace that is not 16-byte aligned, B < 1, n_taps outside 1 .. SISR_PERCEP_MAX_TAPS, a non-positive dim, a shape sum that is
+ *      not total, an unknown criterion, both weights 0; SISR_E_TOOBIG for a tap of more than INT32_MAX elements per sample. ------- */
+#define SISR_PERCEP_MAX_TAPS 8
+#define SISR_PERCEP_L1 0
+#define SISR_PERCEP_L2 1
+#define SISR_PERCEP_FRO 2
+/* HOST: bytes of the workspace, in this order: one double per workgroup of the feature pass (with_feature), one per workgroup of the
+ * Gram finish and the [C][C] Gram partials of both inputs, samples and splits of P (with_style); < 0: a status code.  The Gram-only
+ * entry takes the with_style size. */
+int64_t sisr_percep_ws_bytes(int32_t B, int32_t n_taps, const int32_t *shapes, int32_t with_feature, int32_t with_style);
+/* gram: the taps' G [B][C_l][C_l] one after the other (sum_l B C_l^2 floats), the bits the loss forms internally.  Two launches */
+int sisr_percep_gram(const float *f, int32_t B, int64_t total, int32_t n_taps, const int32_t *shapes, void *ws, float *gram,
+                     void *stream);
+/* terms_p / terms_s: [n_taps] tables of T_l / S_l (either may be NULL); perceptual / style: the scalars, required when their weight
+ * is not 0; dmat: NULL, or sum_l B C_l^2 floats that receive D_l[n] = dS_l / dG_a,l[n] for the backward (l1: sign(d) / (B C^2), l2:
+ * 2 d / (B C^2), fro: d, the norm S_l dividing in the backward).  Launches: Gram partials, Gram finish (style), feature pass
+ * (perceptual), tables and scalars: four with both terms, whatever B is */
+int sisr_percep_fwd(const float *fa, const float *fb, int32_t B, int64_t total, int32_t n_taps, const int32_t *shapes,
+                    const float *layer_w, float perceptual_weight, float style_weight, int32_t crit, void *ws, float *terms_p,
+                    float *terms_s, float *perceptual, float *style, float *dmat, void *stream);
+/* dmat, terms_p, terms_s: as the forward left them (the tables are read for SISR_PERCEP_FRO only); g_perceptual / g_style: the
+ * upstream gradients of the two scalars in DEVICE memory, required when their weight is not 0; dfa / dfb: [B][total], either may be
+ * NULL (then not computed).  dstyle / dF_a = (2 / (C P)) D F_a and dstyle / dF_b = -(2 / (C P)) D F_b on the same instruction with the
+ * feature term's derivative added in the epilogue: one launch, every element stored exactly once */
+int sisr_percep_bwd(const float *fa, const float *fb, const float *dmat, const float *terms_p, const float *terms_s,
+                    const float *g_perceptual, const float *g_style, int32_t B, int64_t total, int32_t n_taps, const int32_t *shapes,
+                    const float *layer_w, float perceptual_weight, float style_weight, int32_t crit, float *dfa, float *dfb,
+                    void *stream);
+
 /* ---- image resize with torch's half-pixel coordinates, the mode chosen per sample, forward and backward.
  *      x [N][C][H][W] fp32, contiguous -> y [N][C][h][w], any h, w >= 1, up or down, any ratio.  modes [N] int32 in DEVICE memory, one
  *      per sample: the host never reads it, so a captured launch follows whatever the table holds at replay.  A value outside 0 .. 2

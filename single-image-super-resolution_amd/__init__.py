@@ -11,15 +11,16 @@ from . import _lib  # noqa: F401
 _FILTERS = ('gaussian_taps', 'gaussian_blur', 'usm_sharpen', 'USMSharp')      # filters.py
 _RESIZE = ('resize', 'resize_taps', 'expected_resize_modes')                   # resize.py
 _ARTIFACT = ('artifact_map', 'artifact_loss')                                  # losses.py
+_PERCEP = ('gram_matrix', 'perceptual_loss', 'PerceptualLoss')                 # losses.py
 
 
 def __getattr__(name):
-    """the public names of ``filters`` and ``resize`` and the artifact-aware loss of ``losses`` under the package's own name,
+    """the public names of ``filters`` and ``resize`` and the artifact-aware and perceptual losses of ``losses`` under the package's own name,
     resolved on first use (importing the package stays light)"""
     if name in _FILTERS:
         import importlib
         return getattr(importlib.import_module('.filters', __name__), name)
-    if name in _ARTIFACT:
+    if name in _ARTIFACT or name in _PERCEP:
         import importlib
         return getattr(importlib.import_module('.losses', __name__), name)
     if name in _RESIZE:                         # ``resize`` itself is the (callable) module: that is what the name is bound to from then on

@@ -22,6 +22,8 @@ PIX_L1, PIX_CHARBONNIER, PIX_MSE = range(3)  # pix_kind of sisr_image_loss_fwd /
 FREQ_L1, FREQ_CHARBONNIER, FREQ_FOCAL = range(3)   # kind of sisr_freq_loss_fwd / sisr_freq_loss_bwd
 FREQ_MAX_SIDE = 256                          # SISR_FREQ_MAX_SIDE: the longest view side the DFT kernels take
 ARTIFACT_MAX_K = 11                          # SISR_ARTIFACT_MAX_K: the largest window of sisr_artifact_fwd
+PERCEP_MAX_TAPS = 8                          # SISR_PERCEP_MAX_TAPS: the most taps sisr_percep_* take
+PERCEP_L1, PERCEP_L2, PERCEP_FRO = range(3)  # crit codes of sisr_percep_fwd / sisr_percep_bwd
 GAUSS_MAX_K = 63                             # SISR_GAUSS_MAX_K: the longest filter of sisr_gauss_blur_* / sisr_usm_fwd
 RESIZE_AREA, RESIZE_BILINEAR, RESIZE_BICUBIC = range(3)      # mode codes of sisr_resize_fwd / sisr_resize_bwd
 RESIZE_MAX_TAPS = 64                         # SISR_RESIZE_MAX_TAPS: the row length of sisr_resize_taps_host's table
@@ -275,6 +277,10 @@ _SIGS = {
     'sisr_artifact_ws_floats': [_i32, _i32, _i32],
     'sisr_artifact_fwd': [_f, _f, _f] + [_i32] * 5 + [_f32, _f, _f, _f, _f],
     'sisr_artifact_bwd': [_f, _f, _f, _f] + [_i32] * 4 + [_f32, _f, _f, _f],
+    'sisr_percep_ws_bytes': [_i32, _i32, C.POINTER(_i32), _i32, _i32],
+    'sisr_percep_gram': [_f, _i32, _i64, _i32, C.POINTER(_i32), _f, _f, _f],
+    'sisr_percep_fwd': [_f, _f, _i32, _i64, _i32, C.POINTER(_i32), C.POINTER(_f32), _f32, _f32, _i32, _f, _f, _f, _f, _f, _f, _f],
+    'sisr_percep_bwd': [_f] * 7 + [_i32, _i64, _i32, C.POINTER(_i32), C.POINTER(_f32), _f32, _f32, _i32, _f, _f, _f],
     'sisr_gauss_taps_host': [_i32, _f32, _f],
     'sisr_gauss_blur_fwd': [_f, _f, _f, _i64, _i32, _i32, _i32, _f],
     'sisr_gauss_blur_bwd': [_f, _f, _f, _i64, _i32, _i32, _i32, _f],
@@ -325,6 +331,7 @@ def lib():
     L.sisr_wgrad_bf16_slab_lead.restype = C.c_int64
     L.sisr_weight_image_bytes.restype = C.c_int64
     L.sisr_usm_ws_bytes.restype = C.c_int64
+    L.sisr_percep_ws_bytes.restype = C.c_int64
     L.sisr_version.restype = C.c_char_p
     L.sisr_version.argtypes = []
     sizes = (_i32 * 9)()

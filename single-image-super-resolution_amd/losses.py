@@ -28,6 +28,12 @@ Artifacts" (CVPR 2022): an L1 between ``sr`` and ``gt`` weighted by the refined 
 generator's output with that of its EMA twin's; ``artifact_map`` is the map alone.  Three launches forward, one backward; saved are
 ``sr``, ``gt`` and the one-channel map.  The map is a constant of the loss (detached).
 
+``perceptual_loss`` (csrc/percep.hip) is the multi-tap perceptual loss of the ESRGAN / Real-ESRGAN recipes (BasicSR's
+``PerceptualLoss``): a per-tap L1 / L2 / Frobenius criterion over the taps of a ``MaskedVGG`` feature vector with one weight per tap,
+and the optional style term on the Gram matrices of the same taps, which run on the exact-fp32 matrix instruction.  Four launches
+forward with both terms, one backward; saved are the inputs, the derivative ``D`` of the style term with respect to the Gram
+matrices and the per-tap terms.  ``gram_matrix`` is the Gram matrices alone; ``PerceptualLoss`` the module around an extractor.
+
 Nothing here synchronises with the host: losses and statistics are 0-dim fp32 device tensors, bit-identical from call to call,
 and the launches can be captured by ``graph.GraphedStep``.  Opt-in: ``install(fused_losses=True)`` points ``torch.nn.BCELoss`` at
 ``BCELoss``; a trainer rebinds its ``content_loss_g`` / ``adversarial_loss_*`` to the functions below.
@@ -432,6 +438,178 @@ def artifact_loss(sr, gt, ema, ksize=7, weight=1.0, reduction='mean', return_map
     if reduction == 'mean':
         loss = loss.mean()
     return (loss, amap) if return_map else loss
+
+
+PERCEP_CRITERIA = {'l1': L.PERCEP_L1, 'l2': L.PERCEP_L2, 'fro': L.PERCEP_FRO}
+
+
+def _check_taps(feat, shapes, what):
+    """the argument errors of a (B, total) feature tensor and its tap shapes -> ((C, H, W), ...) of ints"""
+    if feat.dim() != 2:
+        raise ValueError('%s: a (B, total) feature tensor is expected, got shape %s' % (what, tuple(feat.shape)))
+    try:
+        taps = tuple(tuple(int(v) for v in s) for s in shapes)
+    except (TypeError, ValueError):
+        raise ValueError('%s: shapes is a sequence of (C, H, W), got %r' % (what, shapes)) from None
+    if not 1 <= len(taps) <= L.PERCEP_MAX_TAPS:
+        raise ValueError('%s: 1 .. %d taps are expected, got %d' % (what, L.PERCEP_MAX_TAPS, len(taps)))
+    if any(len(s) != 3 or min(s) < 1 for s in taps):
+        raise ValueError('%s: every shape is (C, H, W) with positive sizes, got %r' % (what, taps))
+    if any(s[0] * s[1] * s[2] > 2 ** 31 - 1 for s in taps):
+        raise ValueError('%s: at most 2^31 - 1 elements per tap and sample, got %r' % (what, taps))
+    total = sum(c * h * w for c, h, w in taps)
+    if total != feat.shape[1]:
+        raise ValueError('%s: the shapes %r hold %d elements per sample, the tensor has %d' % (what, taps, total, feat.shape[1]))
+    return taps
+
+
+def _tap_array(taps):
+    return (L._i32 * (3 * len(taps)))(*[v for s in taps for v in s])
+
+
+def _percep_work(lib, b, taps, with_feature, with_style, dev):
+    size = L.check_count(lib.sisr_percep_ws_bytes(b, len(taps), _tap_array(taps), int(with_feature), int(with_style)),
+                         'sisr_percep_ws_bytes')
+    return torch.empty(max(size, 16) // 4, dtype=torch.float32, device=dev)
+
+
+def _gram_forward(feat, taps):
+    """-> the taps' (B, C, C) Gram matrices of a contiguous detached (B, total) tensor: views of one buffer"""
+    lib, dev, b = L.lib(), feat.device, feat.shape[0]
+    work = _percep_work(lib, b, taps, False, True, dev)
+    out = torch.empty(sum(b * c * c for c, _, _ in taps), dtype=torch.float32, device=dev)
+    L.check(lib.sisr_percep_gram(feat.data_ptr(), b, feat.shape[1], len(taps), _tap_array(taps), work.data_ptr(), out.data_ptr(),
+                                 _stream()), 'sisr_percep_gram')
+    grams, off = [], 0
+    for c, _, _ in taps:
+        grams.append(out[off:off + b * c * c].view(b, c, c))
+        off += b * c * c
+    return tuple(grams)
+
+
+def gram_matrix(feat, shapes):
+    """The Gram matrices ``F F^T / (C H W)`` (BasicSR's ``_gram_mat``) of every tap of a fp32 (B, total) device feature tensor in the
+    layout of ``MaskedVGG.forward``; ``shapes``: the taps' ``(C, H, W)``, as ``model_content_extractor.tap_shapes`` returns them.
+    -> a tuple of detached (B, C, C) tensors, bit-symmetric and the same bits ``perceptual_loss`` forms internally; no graph is
+    recorded.  Two launches for all taps and samples."""
+    what = 'gram_matrix'
+    _check_tensor(feat, what)
+    taps = _check_taps(feat, shapes, what)
+    require_gpu_tensor(feat, 'gram_matrix input')
+    with torch.no_grad():
+        return _gram_forward(feat.detach().contiguous(), taps)
+
+
+class _Perceptual(torch.autograd.Function):
+    """-> (perceptual or None, style or None, terms_p or None, terms_s or None); ``cfg`` = (taps, layer_weights, pw, sw, crit)"""
+
+    @staticmethod
+    def forward(ctx, fa, fb, cfg):
+        fa, fb = fa.detach().contiguous(), fb.detach().contiguous()
+        taps, lw, pw, sw, crit = cfg
+        lib, dev, b = L.lib(), fa.device, fa.shape[0]
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        work = _percep_work(lib, b, taps, pw != 0.0, sw != 0.0, dev)
+        percep, terms_p = (_scalar(dev), torch.empty(len(taps), dtype=torch.float32, device=dev)) if pw != 0.0 else (None, None)
+        style, terms_s = (_scalar(dev), torch.empty(len(taps), dtype=torch.float32, device=dev)) if sw != 0.0 else (None, None)
+        # D = dS / dG_a, written only when a gradient will be needed
+        dmat = torch.empty(sum(b * c * c for c, _, _ in taps), dtype=torch.float32, device=dev) if need and sw != 0.0 else None
+        L.check(lib.sisr_percep_fwd(fa.data_ptr(), fb.data_ptr(), b, fa.shape[1], len(taps), _tap_array(taps),
+                                    (L._f32 * len(taps))(*lw), pw, sw, crit, work.data_ptr(), _ptr(terms_p), _ptr(terms_s),
+                                    _ptr(percep), _ptr(style), _ptr(dmat), _stream()), 'sisr_percep_fwd')
+        if need:
+            ctx.save_for_backward(fa, fb, dmat, terms_p, terms_s)      # the inputs, D and the per-tap terms (the 'fro' norms)
+        ctx.cfg = cfg
+        ctx.mark_non_differentiable(*[t for t in (terms_p, terms_s) if t is not None])
+        return percep, style, terms_p, terms_s
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_p, g_s, _g_tp, _g_ts):
+        fa, fb, dmat, terms_p, terms_s = ctx.saved_tensors
+        taps, lw, pw, sw, crit = ctx.cfg
+        dfa, dfb = _wanted_grads(ctx, fa.shape, fa.device)
+        if dfa is not None or dfb is not None:
+            g_p = None if pw == 0.0 else g_p.to(torch.float32).contiguous()
+            g_s = None if sw == 0.0 else g_s.to(torch.float32).contiguous()
+            L.check(L.lib().sisr_percep_bwd(fa.data_ptr(), fb.data_ptr(), _ptr(dmat), _ptr(terms_p), _ptr(terms_s), _ptr(g_p),
+                                            _ptr(g_s), fa.shape[0], fa.shape[1], len(taps), _tap_array(taps),
+                                            (L._f32 * len(taps))(*lw), pw, sw, crit, _ptr(dfa), _ptr(dfb), _stream()),
+                    'sisr_percep_bwd')
+        return dfa, dfb, None
+
+
+def perceptual_loss(fa, fb, shapes, layer_weights=None, perceptual_weight=1.0, style_weight=0.0, criterion='l1', return_terms=False):
+    """BasicSR's ``PerceptualLoss`` on two fp32 (B, total) device feature tensors in the layout of ``MaskedVGG.forward`` (tap ``l`` is
+    columns ``[off_l, off_l + C_l H_l W_l)`` of every row in NCHW order); ``shapes``: the taps' ``(C, H, W)``, as
+    ``model_content_extractor.tap_shapes`` returns them, at most 8.  Per tap, with ``crit`` the mean of ``|d|`` ('l1'), the mean of
+    ``d^2`` ('l2') or ``sqrt(sum d^2)`` over the whole batch tensor of the tap ('fro'):
+
+    ``perceptual = perceptual_weight * sum_l w_l * crit(fa_l, fb_l)`` and ``style = style_weight * sum_l w_l * crit(G(fa_l), G(fb_l))``
+    with ``G = F F^T / (C H W)`` per sample (``gram_matrix``) and ``w = layer_weights`` (ones by default).
+
+    -> ``(perceptual, style)``, 0-dim fp32 device tensors; a term whose weight is 0 is ``None`` and none of its launches happen.  With
+    ``return_terms`` also the two detached ``[n_taps]`` tables of the unweighted per-tap terms.  Differentiable with respect to
+    ``fa``, ``fb`` or both (only what requires a gradient is computed), once; ``sign(0) = 0``, a zero Frobenius norm gives an
+    all-zero gradient, a NaN in gives NaN terms.  Four launches forward with both terms, one backward; saved: the inputs, ``D`` (the
+    style term's derivative with respect to the Gram matrices, ``B C^2`` floats per tap) and the per-tap terms -- neither ``a - b``
+    nor the Gram matrices.  Non-contiguous inputs are made contiguous first; a bf16 caller casts."""
+    what = 'perceptual_loss'
+    _validate_pair(fa, fb, what)
+    taps = _check_taps(fa, shapes, what)
+    if layer_weights is None:
+        layer_weights = (1.0,) * len(taps)
+    lw = tuple(float(v) for v in layer_weights)
+    if len(lw) != len(taps):
+        raise ValueError('%s: one layer weight per tap is expected, got %d for %d taps' % (what, len(lw), len(taps)))
+    pw, sw = float(perceptual_weight), float(style_weight)
+    if not all(np.isfinite(v) for v in lw + (pw, sw)):
+        raise ValueError('%s: the weights must be finite, got %r, %r, %r' % (what, lw, pw, sw))
+    if criterion not in PERCEP_CRITERIA:
+        raise ValueError('%s: criterion is one of %s, got %r' % (what, sorted(PERCEP_CRITERIA), criterion))
+    require_gpu_tensor(fa, 'perceptual_loss input fa')
+    require_gpu_tensor(fb, 'perceptual_loss input fb')
+    if pw == 0.0 and sw == 0.0:
+        out = (None, None, None, None)
+    else:
+        out = _Perceptual.apply(fa, fb, (taps, lw, pw, sw, PERCEP_CRITERIA[criterion]))
+    return out if return_terms else out[:2]
+
+
+class PerceptualLoss(torch.nn.Module):
+    """BasicSR's ``PerceptualLoss`` around a content extractor of ``model_content_extractor`` (``MaskedVGG``, ``vgg_4conv_1maxPool``
+    or ``identity()``): ``forward(x, gt)`` -> ``(percep, style)`` of ``perceptual_loss`` on the extractor's features, the tap shapes
+    taken from ``tap_shapes``.  ``gt``'s features are computed under ``no_grad``.  ``range_norm`` maps [-1, 1] images to [0, 1] and
+    ``input_norm`` applies the ImageNet mean / std, as BasicSR's ``VGGFeatureExtractor`` does (a per-channel affine on the
+    3-channel image: torch ops, not the hot path).  The Real-ESRGAN setting: ``MaskedVGG(0b11111)``, ``layer_weights=(0.1, 0.1, 1,
+    1, 1)``, ``criterion='l1'``."""
+
+    def __init__(self, extractor, layer_weights=None, perceptual_weight=1.0, style_weight=0.0, criterion='l1', input_norm=False,
+                 range_norm=False):
+        super().__init__()
+        if criterion not in PERCEP_CRITERIA:
+            raise ValueError('PerceptualLoss: criterion is one of %s, got %r' % (sorted(PERCEP_CRITERIA), criterion))
+        self.extractor = extractor
+        self.layer_weights = None if layer_weights is None else tuple(float(v) for v in layer_weights)
+        self.perceptual_weight, self.style_weight, self.criterion = float(perceptual_weight), float(style_weight), criterion
+        self.input_norm, self.range_norm = bool(input_norm), bool(range_norm)
+        self.register_buffer('mean', torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1), persistent=False)
+        self.register_buffer('std', torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1), persistent=False)
+
+    def _features(self, x):
+        if self.range_norm:
+            x = (x + 1) / 2
+        if self.input_norm:
+            x = (x - self.mean.to(x.device)) / self.std.to(x.device)
+        return self.extractor(x).reshape(x.shape[0], -1)
+
+    def forward(self, x, gt):
+        from .model_content_extractor import tap_shapes
+        shapes = tap_shapes(self.extractor, x.shape[2], x.shape[3])
+        fx = self._features(x)
+        with torch.no_grad():
+            fg = self._features(gt.detach())
+        return perceptual_loss(fx, fg, shapes, self.layer_weights, self.perceptual_weight, self.style_weight, self.criterion)
 
 
 class _BCE(torch.autograd.Function):

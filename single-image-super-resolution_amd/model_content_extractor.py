@@ -166,3 +166,28 @@ def get_size(im, mask):
         if mask & (1 << i):
             size += (w // 2 ** i) * (h // 2 ** i) * layersSize[i]
     return size
+
+
+def tap_shapes(extractor, h, w):
+    """The ``(C, H, W)`` of every tap of a content extractor's output for an ``h`` x ``w`` image, in the order of its ``(B, -1)``
+    feature vector, read from the module's own layers (so ``width_div`` is honoured): ``MaskedVGG`` -> one per kept layer,
+    ``vgg_4conv_1maxPool`` -> one, ``identity()`` -> ``((3, h, w),)``.  The sizes sum to ``get_size`` for a ``MaskedVGG`` of full
+    width."""
+    if isinstance(extractor, nn.Identity):
+        return ((3, int(h), int(w)),)
+    if isinstance(extractor, MaskedVGG):
+        layers, kept = extractor.layers, extractor.intermediate_layers_kept
+    elif isinstance(extractor, _VGGPrefix):
+        layers = extractor
+        kept = [max(i for i, m in enumerate(layers, 1) if isinstance(m, Conv2d))]
+    else:
+        raise ValueError('tap_shapes: a MaskedVGG, a vgg_4conv_1maxPool or an identity() extractor is expected, got %s'
+                         % type(extractor))
+    shapes, pools = [], 0
+    for i, m in enumerate(layers, 1):
+        if isinstance(m, Conv2d):
+            if i in kept:
+                shapes.append((int(m.weight.shape[0]), int(h) >> pools, int(w) >> pools))
+        elif m.what.startswith('MaxPool'):
+            pools += 1
+    return tuple(shapes)
