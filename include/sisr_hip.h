@@ -1134,6 +1134,54 @@ int sisr_resize_modes_draw(const int64_t *drawn_step_dev, uint64_t seed, int32_t
 int sisr_resize_modes_host(int64_t t, uint64_t seed, int32_t rank, int32_t B, float p_area, float p_bilinear, float p_bicubic,
                            int32_t *modes_host);
 
+/* ---- NIQE, the no-reference image quality score of Mittal, Soundararajan and Bovik (IEEE SPL 2013), as BasicSR's calculate_niqe
+ *      defines it: the 36 features of every block of an image, and the score against a pristine model.
+ *      img: fp32 [N][C][H][W], contiguous, C 1 or 3; block even, 16 .. SISR_NIQE_MAX_BLOCK; everything after the image is read is double.
+ *      1. View and plane: strip `crop` pixels from every side; v = (x - lo) k with k = 255 / (hi - lo) (lo, hi taken as double);
+ *         C == 3: Y = 16 + ((65.481 R + 128.553 G) + 24.966 B) / 255 (BT.601 studio range, MATLAB's rgb2ycbcr), C == 1: Y = v; the
+ *         products and sums rounded as written (nothing fused); Y = rint(Y), half to even; the top-left
+ *         floor(h / block) block x floor(w / block) block pixels are kept (nb = their blocks, row-major) and nothing else is seen.
+ *      2. Two scales: scale 1 is that plane with blocks of `block`; scale 2 the plane down-scaled by 2 with blocks of block / 2:
+ *         along each axis out[i] = sum_{k=0..7} w_k in[2 i - 3 + k], w = (-3, -9, 29, 111, 111, 29, -9, -3) / 256 (MATLAB's
+ *         antialiased bicubic at exactly 1/2), an index outside the axis mirrored with the edge pixel repeated (-1 -> 0, L -> L - 1),
+ *         no clamp of the result (the sums are exact in double, so the order of the axes does not matter).
+ *      3. MSCN: g_k ~ exp(-k^2 / (2 (7/6)^2)), k = -3 .. 3, normalised to sum 1; the 2-D window is g_i g_j; the border is replicated.
+ *         mu = g * I, sigma = sqrt(|g * I^2 - mu^2|), mscn = (I - mu) / (sigma + 1), computed from the moments ABOUT THE PIXEL:
+ *         m1 = sum g_i g_j (I_ij - I), m2 = sum g_i g_j (I_ij - I)^2, sigma = sqrt(|m2 - m1^2|), mscn = -m1 / (sigma + 1): the
+ *         differences are exact, the variance loses no digits, and a constant 7 x 7 neighbourhood gives exactly 0.
+ *      4. AGGD fit of a field f over one block: L = sqrt(mean f^2 over f < 0), R = sqrt(mean f^2 over f > 0), gamma = L / R,
+ *         r = (mean |f|)^2 / mean f^2, Rhat = r (gamma^3 + 1) (gamma + 1) / (gamma^2 + 1)^2; alpha = alpha_j = 0.2 + 0.001 j with
+ *         j = argmin_j (rho_j - Rhat)^2 over j = 0 .. SISR_NIQE_TABLE - 1 (first minimum; a NaN or infinite Rhat: j = 0, and every other
+ *         number of that fit is a NaN), rho_j = Gamma(2 / alpha_j)^2 / (Gamma(1 / alpha_j) Gamma(3 / alpha_j)), strictly increasing;
+ *         beta_l = L sqrt(Gamma(1 / alpha) / Gamma(3 / alpha)), beta_r likewise, m = (beta_r - beta_l) Gamma(2 / alpha) / Gamma(1 / alpha).
+ *         tables: DEVICE double [4][SISR_NIQE_TABLE], built by the caller on the host: Gamma(1 / alpha_j), Gamma(2 / alpha_j),
+ *         Gamma(3 / alpha_j) and rho_j formed from them.
+ *      5. Features of a block, 18 per scale, scale 1 first: (alpha, (beta_l + beta_r) / 2) of the block's MSCN, then for the shifts
+ *         (0, 1), (1, 0), (1, 1), (1, -1) the fit (alpha, m, beta_l, beta_r) of mscn roll(mscn, shift), the roll circular INSIDE the
+ *         block; block (by, bx) of scale 2 is the block / 2 square at the same block coordinates of the down-scaled plane.
+ *         sharp: the block's mean of sigma at scale 1.
+ *      6. Score against (mu_p [36], cov_p [36][36], DEVICE doubles): mu_d = the column means over the blocks ignoring NaNs, cov_d = the
+ *         unbiased covariance of the rows without a NaN, S = (cov_p + cov_d) / 2, d = mu_p - mu_d, score = sqrt(d^T S^-1 d) by a Cholesky
+ *         factorisation in double (square-root-free, S = L D L^T: the same pivots); fewer than two complete rows, or a pivot that is
+ *         not > 0, gives a NaN score (the pseudo-inverse of a singular S is not formed).
+ *      Launches: sisr_niqe_features FOUR (plane, down-scale, one block launch per scale), sisr_niqe_score ONE, whatever N and nb are.
+ *      No atomics, fixed-order sums, nothing read back by the host: the same bits on every call.
+ *      SISR_E_BADARG before any HIP call for null pointers (sharp may be NULL), a workspace, feature, model or table pointer that is not
+ *      8-byte aligned, N < 1, nb < 1, an odd block or one outside 16 .. SISR_NIQE_MAX_BLOCK, a non-finite or empty value range, a negative
+ *      crop; SISR_E_UNSUPPORTED for C not 1 or 3 or a view smaller than one block; SISR_E_TOOBIG past INT32_MAX elements or N > 65535. */
+#define SISR_NIQE_MAX_BLOCK 96
+#define SISR_NIQE_FEATURES 36
+#define SISR_NIQE_TABLE 9801
+/* HOST: bytes of the workspace (the two planes and the score's row flags: one workspace serves both calls; the score alone needs
+ * 4 N nb bytes); < 0: a status code */
+int64_t sisr_niqe_ws_bytes(int32_t N, int32_t H, int32_t W, int32_t crop, int32_t block);
+/* feat: double [N][nb][36]; sharp: float [N][nb] or NULL */
+int sisr_niqe_features(const float *img, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop, float lo, float hi, int32_t block,
+                       const double *tables, void *ws, double *feat, float *sharp, void *stream);
+/* feat: double [N][nb][36] as sisr_niqe_features left it; score: float [N] */
+int sisr_niqe_score(const double *feat, int32_t N, int32_t nb, const double *mu_p, const double *cov_p, void *ws, float *score,
+                    void *stream);
+
 /* ---- misc---------------------------------------------------------------------------------- */
 /* ---- optimizer: fused multi-tensor Adam --------------------------------------------------
  * One launch performs torch.optim.Adam's update (amsgrad=False, maximize=False; config.py:292-294, stepped at

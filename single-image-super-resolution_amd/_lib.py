@@ -27,6 +27,7 @@ PERCEP_L1, PERCEP_L2, PERCEP_FRO = range(3)  # crit codes of sisr_percep_fwd / s
 GAUSS_MAX_K = 63                             # SISR_GAUSS_MAX_K: the longest filter of sisr_gauss_blur_* / sisr_usm_fwd
 RESIZE_AREA, RESIZE_BILINEAR, RESIZE_BICUBIC = range(3)      # mode codes of sisr_resize_fwd / sisr_resize_bwd
 RESIZE_MAX_TAPS = 64                         # SISR_RESIZE_MAX_TAPS: the row length of sisr_resize_taps_host's table
+NIQE_MAX_BLOCK, NIQE_FEATURES, NIQE_TABLE = 96, 36, 9801   # SISR_NIQE_*: the largest block, the features of a block, the entries of the alpha table
 ROUTE_GENERIC, ROUTE_DEEP, ROUTE_TOIMAGE, ROUTE_TRUNK, ROUTE_THIN = range(5)      # enum SisrRoute: what the sisr_*_route calls answer
 
 _f = C.c_void_p      # device pointers travel as void*
@@ -281,6 +282,9 @@ _SIGS = {
     'sisr_percep_gram': [_f, _i32, _i64, _i32, C.POINTER(_i32), _f, _f, _f],
     'sisr_percep_fwd': [_f, _f, _i32, _i64, _i32, C.POINTER(_i32), C.POINTER(_f32), _f32, _f32, _i32, _f, _f, _f, _f, _f, _f, _f],
     'sisr_percep_bwd': [_f] * 7 + [_i32, _i64, _i32, C.POINTER(_i32), C.POINTER(_f32), _f32, _f32, _i32, _f, _f, _f],
+    'sisr_niqe_ws_bytes': [_i32] * 5,
+    'sisr_niqe_features': [_f] + [_i32] * 5 + [_f32, _f32, _i32, _f, _f, _f, _f, _f],
+    'sisr_niqe_score': [_f, _i32, _i32, _f, _f, _f, _f, _f],
     'sisr_gauss_taps_host': [_i32, _f32, _f],
     'sisr_gauss_blur_fwd': [_f, _f, _f, _i64, _i32, _i32, _i32, _f],
     'sisr_gauss_blur_bwd': [_f, _f, _f, _i64, _i32, _i32, _i32, _f],
@@ -332,6 +336,7 @@ def lib():
     L.sisr_weight_image_bytes.restype = C.c_int64
     L.sisr_usm_ws_bytes.restype = C.c_int64
     L.sisr_percep_ws_bytes.restype = C.c_int64
+    L.sisr_niqe_ws_bytes.restype = C.c_int64
     L.sisr_version.restype = C.c_char_p
     L.sisr_version.argtypes = []
     sizes = (_i32 * 9)()

@@ -25,7 +25,7 @@ import torch
 
 from . import _lib as L
 from .engine import _stream
-from .metrics import psnr_ssim
+from .metrics import niqe, psnr_ssim
 from .utils import lr_from_hr
 
 
@@ -235,10 +235,11 @@ class Upscaler:
         return dst
 
 
-def evaluate_image(up, img_hr_u8, image_size_lr=None):
+def evaluate_image(up, img_hr_u8, image_size_lr=None, niqe_model=None):
     """One whole-image validation: the [H, W, C] uint8 HR image is normalised, degraded with ``lr_from_hr`` to ``image_size_lr``
     (None: (H // s, W // s)), upscaled tiled by ``up`` and scored against the HR image with ``psnr_ssim`` (borders cropped by the
-    scale factor, the SR convention) -> ``dict(psnr=Tensor[1], ssim=Tensor[1])``.  H and W must be s times the LR size."""
+    scale factor, the SR convention) -> ``dict(psnr=Tensor[1], ssim=Tensor[1])``.  H and W must be s times the LR size.
+    ``niqe_model`` (a ``metrics.NiqeModel``): the dict gains ``niqe``, the no-reference score of the SR image, cropped alike."""
     if Upscaler._kind(img_hr_u8) != 'u8':
         raise RuntimeError('evaluate_image: a [H, W, C] uint8 image is expected, got %s' % img_hr_u8.dtype)
     if not img_hr_u8.is_cuda:
@@ -257,4 +258,6 @@ def evaluate_image(up, img_hr_u8, image_size_lr=None):
                                       _stream()), 'sisr_patch_gather')
     sr = up(lr_from_hr(hr, lr_size)[0])
     p, q = psnr_ssim(sr[None], hr, crop_border=s)
-    return dict(psnr=p, ssim=q)
+    if niqe_model is None:
+        return dict(psnr=p, ssim=q)
+    return dict(psnr=p, ssim=q, niqe=niqe(sr[None], niqe_model, crop_border=s))

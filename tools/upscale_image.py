@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Upscale one image file with a trained generator: ``upscale_image.py checkpoint in.png out.png [--tile --halo --feather
---ensemble --ema]``.
+--ensemble --ema --niqe MODEL.npz]``.
 
 The checkpoint is the reference's (utils._save: a dict whose ``net_g`` entry is the generator's state_dict; ``--ema`` takes the
 averaged weights stored beside it as ``net_g_ema``, ema.WeightEMA.shadow_state_dict).  The architecture is read off the
 state_dict's keys and shapes (``arch_from_state``) and the weights are loaded tolerantly (strict=False with the reference's
 coverage report).  The image is decoded and encoded with Pillow on the host; everything between runs on the MI355X
-(upscale.Upscaler).  Argument handling and ``arch_from_state`` need no GPU.
+(upscale.Upscaler).  ``--niqe MODEL.npz`` (a metrics.NiqeModel file: tools/fit_niqe.py, or a BasicSR-style parameter file) also prints
+the no-reference NIQE score of the output image; no HR image is needed.  Argument handling and ``arch_from_state`` need no GPU.
 """
 import argparse
 import importlib
@@ -36,6 +37,8 @@ def parse_args(argv=None):
     ap.add_argument('--ensemble', type=int, default=1, choices=(1, 8), help='8: mean over the eight flips / transpositions')
     ap.add_argument('--batch', type=int, default=8, help='tiles per generator call (default 8)')
     ap.add_argument('--ema', action='store_true', help="use the averaged weights ('net_g_ema') of the checkpoint")
+    ap.add_argument('--niqe', metavar='MODEL.npz', default=None,
+                    help='also print the NIQE score of the output image under this model (tools/fit_niqe.py writes one)')
     a = ap.parse_args(argv)
     if a.tile < 1 or a.batch < 1:
         ap.error('--tile and --batch must be >= 1')
@@ -98,6 +101,11 @@ def main(argv=None):
     print('%s: %d x %d -> %s: %d x %d (x%d, %d tiles of %d, halo %d)'
           % (a.input, img.shape[1], img.shape[0], a.output, sr.shape[1], sr.shape[0], up.scale,
              up.ensemble * up.plan(img.shape[0], img.shape[1]).n, up.tile, up.halo))
+    if a.niqe is not None:
+        M = _pkg('metrics')
+        model = M.NiqeModel.load(a.niqe).to('cuda')
+        out = ((sr.permute(2, 0, 1)[None].float() - 127.5) / 127.5).contiguous()
+        print('NIQE (model %s, block %d): %.4f' % (a.niqe, model.block, float(M.niqe(out, model))))
 
 
 if __name__ == '__main__':
