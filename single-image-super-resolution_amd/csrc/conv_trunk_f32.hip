@@ -18,9 +18,10 @@
 //     lane half kk multiplies channels 16 kk + s at step s, so its 16 A values (and its 16 B values) are four
 //     ds_read_b128 instead of sixteen ds_read_b32 -- a quarter of the LDS instructions per MFMA;
 //   * 1152 pixel tiles x 2 cout halves = exactly 9 units per CU at the benchmark size (no partial round);
-//   * role-specific loops with matching barrier counts (see conv_trunk.hip): the producers' per stage, the consumers' per tile
-//     with its two stages as straight-line code, tile coordinates advanced incrementally, and the epilogue's addresses as one
-//     lane register + the instruction's scalar offset and immediate.
+//   * role-specific loops with matching barrier counts (see conv_trunk.hip), both per tile with its two stages as
+//     straight-line code and tile coordinates advanced incrementally: the producers keep what depends on the tile alone (item
+//     addresses, edge test, the lane masks of the items outside the image) from one stage to the next, the consumers address
+//     the epilogue with one lane register + the instruction's scalar offset and immediate.
 // The two workgroups of a cout pair walk the same pixel tiles and share one statistics row: each writes its 32 channels.
 #include "sisr_dev.h"
 #include "sisr_bf16_stage.h"
@@ -161,36 +162,40 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
             }
             return;
         }
-        constexpr int W_IT = 2 * 9 * 32 * 32 / CF_THREADS;                     // 36 elements per thread
-        float wv[W_IT];
+        // 36 elements per thread; the two-tensor prologues, whose producers hold twice the staged values across this copy, take
+        // them in two passes of 18
+        constexpr int W_PASS = TWO ? 2 : 1, W_IT = 2 * 9 * 32 * 32 / CF_THREADS / W_PASS;
 #pragma unroll
-        for (int it = 0; it < W_IT; ++it) {                                     // all loads in flight, then the LDS writes
-            const int e = tid + it * CF_THREADS;
-            const int ci = e & 31, s = (e >> 5) % 3, t2 = (e >> 5) / 3;        // t2 = (q * 3 + r) * 32 + co
-            const int co = t2 & 31, qr = t2 >> 5;                               // qr = q * 3 + r
-            wv[it] = a.wpk[((int64_t)qr * a.cout_pad + 32 * hc + co) * CF_KROWP + s * CF_PS + ci];
-        }
+        for (int ps = 0; ps < W_PASS; ++ps) {
+            float wv[W_IT];
 #pragma unroll
-        for (int it = 0; it < W_IT; ++it) {
-            const int e = tid + it * CF_THREADS;
-            const int ci = e & 31, s = (e >> 5) % 3, t2 = (e >> 5) / 3;
-            const int co = t2 & 31, qr = t2 >> 5;
-            const int q = qr / 3, r = qr - 3 * q;
-            if constexpr (SPLIT) {
-                // lanes 2m / 2m + 1 hold input channels 2m / 2m + 1 of one row: the even lane writes the hi pair, the odd one the lo pair
-                const float vo = __shfl_xor(wv[it], 1);
-                const bool odd = ci & 1;
-                unsigned hw, lw;
-                cf_split2(odd ? vo : wv[it], odd ? wv[it] : vo, hw, lw);
-                reinterpret_cast<unsigned*>(wl)[((q * 9 + r * 3 + s) * 32 + co) * CF_WROW + (odd ? 16 : 0) + (ci >> 1)] = odd ? lw : hw;
-            } else {
-                wl[((q * 9 + r * 3 + s) * 32 + co) * CF_WROW + ci] = wv[it];
+            for (int it = 0; it < W_IT; ++it) {                                     // all loads in flight, then the LDS writes
+                const int e = tid + (ps * W_IT + it) * CF_THREADS;
+                const int ci = e & 31, s = (e >> 5) % 3, t2 = (e >> 5) / 3;        // t2 = (q * 3 + r) * 32 + co
+                const int co = t2 & 31, qr = t2 >> 5;                               // qr = q * 3 + r
+                wv[it] = a.wpk[((int64_t)qr * a.cout_pad + 32 * hc + co) * CF_KROWP + s * CF_PS + ci];
+            }
+#pragma unroll
+            for (int it = 0; it < W_IT; ++it) {
+                const int e = tid + (ps * W_IT + it) * CF_THREADS;
+                const int ci = e & 31, s = (e >> 5) % 3, t2 = (e >> 5) / 3;
+                const int co = t2 & 31, qr = t2 >> 5;
+                const int q = qr / 3, r = qr - 3 * q;
+                if constexpr (SPLIT) {
+                    // lanes 2m / 2m + 1 hold input channels 2m / 2m + 1 of one row: the even lane writes the hi pair, the odd one the lo pair
+                    const float vo = __shfl_xor(wv[it], 1);
+                    const bool odd = ci & 1;
+                    unsigned hw, lw;
+                    cf_split2(odd ? vo : wv[it], odd ? wv[it] : vo, hw, lw);
+                    reinterpret_cast<unsigned*>(wl)[((q * 9 + r * 3 + s) * 32 + co) * CF_WROW + (odd ? 16 : 0) + (ci >> 1)] = odd ? lw : hw;
+                } else {
+                    wl[((q * 9 + r * 3 + s) * 32 + co) * CF_WROW + ci] = wv[it];
+                }
             }
         }
     };
 
     const int n_mine = stream < a.total ? (a.total - stream + a.streams - 1) / a.streams : 0;   // pixel tiles of this workgroup
-    const int n_stages = 2 * n_mine;                                                               // (tile, channel half)
 
     if (!consumer) {
         // ---- producers: stage j + 1 = (tile (j + 1) / 2, channel half (j + 1) % 2) while the consumers multiply stage j -----
@@ -214,52 +219,75 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
             const unsigned f = (py == 0 ? 1u : 0u) | (py == CF_IH - 1 ? 2u : 0u) | (pxx == 0 ? 4u : 0u) | (pxx == CF_IW - 1 ? 8u : 0u) |
                                (px >= CF_NPIX ? 16u : 0u);
             flags |= f << (5 * k);
-            asm volatile("" : "+v"(rel[k]));                  // (opaque: kept in a register, not re-derived from m0 by every issue())
+            asm volatile("" : "+v"(rel[k]));                  // (opaque: one register per item, the start of its running offset voff[k])
         }
         const bool last_beyond = m0 + 32 * (CF_ITEMS - 1) >= CF_NPIX;
         const int ldso = SPLIT ? m0 * CF_PSF * 4 + quad * 8 : (m0 * CF_PSF + quad * 4) * 4;
         const bool easy_slope = slope >= 0.f && slope <= 1.f;
+        // skip-sum prologue: the lanes whose item k is one of the tile's own 8 x 16 pixels (no halo flag) -- the same for every
+        // tile, one lane mask per item for the whole launch
+        uint64_t own[CF_ITEMS];
+#pragma unroll
+        for (int k = 0; k < CF_ITEMS; ++k) own[k] = SUM ? __builtin_amdgcn_ballot_w64(((flags >> (5 * k)) & 31u) == 0u) : 0ull;
+        const unsigned xbytes = (unsigned)(a.xsc * a.xsc) * tbytes;
+        const __amdgpu_buffer_rsrc_t r1 = cf_rsrc(a.x1, xbytes), r2 = cf_rsrc(TWO ? a.x2 : a.x1, xbytes);
+        const __amdgpu_buffer_rsrc_t ro = cf_rsrc(SUM ? a.x_out : a.x1, tbytes);
 
-        // two staging register sets: the loads of stage j + 2 fly while stage j + 1 is transformed and written to LDS (a
-        // stage lasts ~4 us of MFMAs; a cold load round trip under a chip-wide load burst is not much shorter).  issue() is
-        // always executed, so that the loop has no control flow around loads and the compiler's wait counts stay exact.  Every
-        // item is loaded from where it would sit in the tensor, inside the image or not (a buffer load past either end of the
-        // tensor returns zeros; one that lands on a neighbouring row's pixels returns values commit() replaces by zeros): no
-        // per-item address select.
-        struct Stage { f32x4 s1[CF_ITEMS], s2[CF_ITEMS]; unsigned bad, origin; bool edge; };
-        Stage stA, stB;
-        auto issue = [&](int j, Stage& st) {
-            const int T = stream + (j >> 1) * a.streams, q = j & 1;
-            const unsigned xbytes = (unsigned)(a.xsc * a.xsc) * tbytes;
-            const __amdgpu_buffer_rsrc_t r1 = cf_rsrc(a.x1, xbytes), r2 = cf_rsrc(TWO ? a.x2 : a.x1, xbytes);
-            int n, ty, tx;
-            tile_coords(T, n, ty, tx);
-            const unsigned origin = (unsigned)(((n * a.xsc * a.H + a.xsc * ty * CF_TH + (a.xph >> 1)) * a.xsc * a.W + a.xsc * tx * CF_TW + (a.xph & 1)) * 256 + q * 128);
-            const unsigned e = (ty == 0 ? 1u : 0u) | (ty == tiles_y - 1 ? 2u : 0u) | (tx == 0 ? 4u : 0u) | (tx == a.tiles_x - 1 ? 8u : 0u);
-            st.edge = e != 0u;                                               // wave-uniform: this tile has items outside the image
-            st.bad = flags & ((e | 16u) * 0x02108421u);                      // (stages past the end are never committed)
-            st.origin = origin;
+        // what depends on the TILE and not on the channel half is computed once per tile: where item k of this lane sits in the
+        // tensor (voff: channel half 0; half 1 is 128 bytes on, the instructions' immediate), whether the tile touches the
+        // image's border (edge, wave-uniform), and for a border tile the lanes whose item k lies outside the image (bad: one lane
+        // mask per item).  voff belongs to the tile whose loads go out next (at byte `origin`) and moves on by the difference of
+        // two origins; edge / bad belong to the tile whose commit comes next.
+        auto tile_origin = [&](int n, int ty, int tx) {
+            return (unsigned)(((n * a.xsc * a.H + a.xsc * ty * CF_TH + (a.xph >> 1)) * a.xsc * a.W + a.xsc * tx * CF_TW + (a.xph & 1)) * 256);
+        };
+        auto tile_edges = [&](int ty, int tx) {                             // image missing above / below / left / right
+            return (ty == 0 ? 1u : 0u) | (ty == tiles_y - 1 ? 2u : 0u) | (tx == 0 ? 4u : 0u) | (tx == a.tiles_x - 1 ? 8u : 0u);
+        };
+        unsigned voff[CF_ITEMS], origin;
+        uint64_t bad[CF_ITEMS];
+        bool edge;
+        auto tile_masks = [&](unsigned e) {
+            edge = e != 0u;
+            const unsigned pat = e * 0x02108421u;                            // the edge pattern replicated over the items
 #pragma unroll
             for (int k = 0; k < CF_ITEMS; ++k) {
-                const unsigned voff = origin + (unsigned)rel[k];
-                st.s1[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r1, voff, 0, 0));
-                if (TWO) st.s2[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r2, voff, 0, 0));
+                unsigned pk = pat & (31u << (5 * k));
+                asm volatile("" : "+s"(pk));                  // (the item's part of the pattern in a scalar register, not its field mask in a lane register)
+                bad[k] = __builtin_amdgcn_ballot_w64((flags & pk) != 0u);
+            }
+        };
+        // two staging register sets, one per channel half: the loads of stage j + 2 fly while stage j + 1 is transformed and
+        // written to LDS (a stage lasts ~4 us of MFMAs; a cold load round trip under a chip-wide load burst is not much shorter).
+        // issue() is always executed, so that the loop has no control flow around loads and the compiler's wait counts stay exact.
+        // Every item is loaded from where it would sit in the tensor, inside the image or not (a buffer load past either end of
+        // the tensor returns zeros; one that lands on a neighbouring row's pixels returns values commit() replaces by zeros): no
+        // per-item address select.  The channel half's 128 bytes stay inside the item's own pixel (16 quad + 128 q < 256), so
+        // adding them behind the lane offset -- the immediate takes part in the range check -- changes no item's side of either end.
+        struct Stage { f32x4 s1[CF_ITEMS], s2[CF_ITEMS]; };
+        Stage st0, st1;
+        auto issue = [&](auto q_c, Stage& st) {
+            constexpr unsigned Q = decltype(q_c)::value;
+#pragma unroll
+            for (int k = 0; k < CF_ITEMS; ++k) {
+                st.s1[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r1, voff[k] + Q * 128u, 0, 0));
+                if (TWO) st.s2[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r2, voff[k] + Q * 128u, 0, 0));
             }
         };
         // EASY: 0 <= slope <= 1 (every slope this model family uses): leaky ReLU = max(v, slope v), no compare + select.
-        // EDGE: the tile has items outside the image (their LDS slots are zero AFTER the transform); an interior tile skips the selects.
-        auto commit_t = [&](auto easy_, auto edge_, int j, const Stage& st) {
+        // EDGE: the tile has items outside the image: their LDS slots are zero AFTER the transform -- the transformed values are
+        // written for every lane, then zeros over them by the lanes of the item's mask (LDS keeps a wave's writes in order); an
+        // interior tile has no second write.
+        // `back`: from voff's tile to the committed one (the skip-sum store's address).
+        auto commit_t = [&](auto easy_, auto edge_, auto q_c, unsigned back, const Stage& st) {
             constexpr int EASY = decltype(easy_)::value;
             constexpr bool EDGE = decltype(edge_)::value;
-            const int q = j & 1;
-            float* img = reinterpret_cast<float*>(halo0 + (j & 1) * CF_HALO_BYTES + ldso);
-            // (selects, not dynamically indexed arrays: those would live in scratch)
-            const f32x4 qa = q ? ka[1] : ka[0], qb = q ? kb[1] : kb[0], qd = q ? kd[1] : kd[0], qs = q ? ks[1] : ks[0], qt = q ? kt[1] : kt[0];
-            const __amdgpu_buffer_rsrc_t ro = cf_rsrc(SUM ? a.x_out : a.x1, tbytes);
+            constexpr int q = decltype(q_c)::value;
+            float* img = reinterpret_cast<float*>(halo0 + q * CF_HALO_BYTES + ldso);
+            const f32x4 qa = ka[q], qb = kb[q], qd = kd[q], qs = ks[q], qt = kt[q];
 #pragma unroll
             for (int k = 0; k < CF_ITEMS; ++k) {
                 if (k == CF_ITEMS - 1 && last_beyond) break;
-                const bool ok = !EDGE || ((st.bad >> (5 * k)) & 31u) == 0u;
                 auto value = [&](int c) {
                     const float v = st.s1[k][c];
                     if (PRO == SISR_PRO_NONE) return v;
@@ -269,41 +297,108 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
                     if (PRO == SISR_PRO_ACT_BWD) return st.s2[k][c] > 0.f ? v : slope * v;    // act'(pre-activation) * gradient
                     const float bx = st.s2[k][c];
                     float g = v;
-                    if (PRO == SISR_PRO_BNACT_BWD) g = qs[c] * bx + qt[c] > 0.f ? v : slope * v;
-                    return qa[c] * g + qb[c] * bx + qd[c];
+                    if (PRO == SISR_PRO_BNACT_BWD) g = __builtin_fmaf(qs[c], bx, qt[c]) > 0.f ? v : slope * v;
+                    if constexpr (SPLIT) {
+                        return qa[c] * g + qb[c] * bx + qd[c];
+                    } else {
+                        // exact build: which of the two products is rounded before the sum is spelled out, as this kernel has
+                        // computed it since it was written (left to the compiler it changes with the shape of the code around it,
+                        // and a last-bit change here moves every gradient behind it): one product feeds a fused multiply-add --
+                        // except for channels 2, 3 of the last item of an interior tile, where both are rounded
+#pragma clang fp contract(off)
+                        if (!EDGE && k == CF_ITEMS - 1 && c >= 2) return (qa[c] * g + qb[c] * bx) + qd[c];
+                        if (PRO == SISR_PRO_BNBWD) return __builtin_fmaf(qa[c], g, qb[c] * bx) + qd[c];
+                        return __builtin_fmaf(qb[c], bx, qa[c] * g) + qd[c];
+                    }
                 };
                 const f32x4 osum = {value(0), value(1), value(2), value(3)};
-                const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
                 if constexpr (SPLIT) {
                     typedef unsigned cf_u32x2 __attribute__((ext_vector_type(2)));
                     unsigned h0, l0, h1, l1;
                     cf_split2(osum[0], osum[1], h0, l0);
                     cf_split2(osum[2], osum[3], h1, l1);
                     const cf_u32x2 hw = {h0, h1}, lw = {l0, l1};
-                    const cf_u32x2 z2 = {0u, 0u};
-                    *reinterpret_cast<cf_u32x2*>(img + k * 32 * CF_PSF) = ok ? hw : z2;
-                    *reinterpret_cast<cf_u32x2*>(img + k * 32 * CF_PSF + 16) = ok ? lw : z2;
-                } else
-                *reinterpret_cast<f32x4*>(img + k * 32 * CF_PSF) = ok ? osum : zero4;        // the halo is zero AFTER the transform
-                // skip-sum prologue: the tile's own 8 x 16 pixels (no halo flag) store the materialised sum, once per pixel
-                // and channel half -- by the workgroup of cout half 0 (its partner stages the same tiles)
-                if (SUM && hc == 0 && ((flags >> (5 * k)) & 31u) == 0u)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(cf_u32x4, osum), ro, st.origin + (unsigned)rel[k], 0, 0);
+                    *reinterpret_cast<cf_u32x2*>(img + k * 32 * CF_PSF) = hw;
+                    *reinterpret_cast<cf_u32x2*>(img + k * 32 * CF_PSF + 16) = lw;
+                    if constexpr (EDGE) {
+                        asm volatile("" ::: "memory");
+                        if (__builtin_amdgcn_inverse_ballot_w64(bad[k])) {            // ((hi, lo) of +0.0f is two zero words)
+                            const cf_u32x2 z2 = {0u, 0u};
+                            *reinterpret_cast<cf_u32x2*>(img + k * 32 * CF_PSF) = z2;
+                            *reinterpret_cast<cf_u32x2*>(img + k * 32 * CF_PSF + 16) = z2;
+                        }
+                    }
+                } else {
+                    *reinterpret_cast<f32x4*>(img + k * 32 * CF_PSF) = osum;
+                    if constexpr (EDGE) {
+                        // (the compiler barrier keeps this a second write under the item's mask: without it the two writes are
+                        // merged back into four selects and one write)
+                        asm volatile("" ::: "memory");
+                        if (__builtin_amdgcn_inverse_ballot_w64(bad[k]))
+                            *reinterpret_cast<f32x4*>(img + k * 32 * CF_PSF) = f32x4{0.f, 0.f, 0.f, 0.f};    // the halo is zero AFTER the transform
+                    }
+                }
+                // skip-sum prologue: the tile's own 8 x 16 pixels store the materialised sum, once per pixel and channel half --
+                // channel half q by the workgroup of cout half q (its partner stages the same tiles and stores the other half)
+                if (SUM && hc == q && __builtin_amdgcn_inverse_ballot_w64(own[k]))
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(cf_u32x4, osum), ro, voff[k] + back + q * 128u, 0, 0);
             }
         };
-        auto commit = [&](int j, const Stage& st) {
-            using T1 = std::integral_constant<int, 1>; using T0 = std::integral_constant<int, 0>;
-            // (prologues without a leaky ReLU have nothing that depends on EASY: one instantiation)
-            constexpr bool HAS_ACT = PRO == SISR_PRO_ACT || PRO == SISR_PRO_AFFINE_ACT || SUM;
-            if (!HAS_ACT || easy_slope) {
-                if (st.edge) commit_t(T1{}, std::true_type{}, j, st); else commit_t(T1{}, std::false_type{}, j, st);
-            } else {
-                if (st.edge) commit_t(T0{}, std::true_type{}, j, st); else commit_t(T0{}, std::false_type{}, j, st);
+        // one tile of the walk: its two channel-half stages as straight-line code.  While the consumers multiply (tile, half 0),
+        // the loads of (next tile, half 0) go out and (tile, half 1) is committed; while they multiply (tile, half 1), the loads
+        // of (next tile, half 1) go out and (next tile, half 0) is committed.  Two barriers per tile, as the consumers count them.
+        // (the edge test is per tile, a flag in a scalar register; its branch is taken at each of the tile's two commits, which
+        // sit on either side of the loop's back edge)
+        auto commit = [&](auto easy_, auto q_c, unsigned back, const Stage& st) {
+            if (edge) commit_t(easy_, std::true_type{}, q_c, back, st); else commit_t(easy_, std::false_type{}, q_c, back, st);
+        };
+        using Q0 = std::integral_constant<int, 0>; using Q1 = std::integral_constant<int, 1>;
+        // this workgroup's tiles: (n, ty, tx) advance by a fixed (dn, dty, dtx) with carries, as the consumers' do
+        const int dn = fdiv(a.streams, a.m_per_img), drem = a.streams - dn * a.per_img;
+        const int dty = fdiv(drem, a.m_tiles_x), dtx = drem - dty * a.tiles_x;
+        int n, ty, tx;
+        tile_coords(stream, n, ty, tx);
+        auto advance = [&]() {
+            tx += dtx;
+            if (tx >= a.tiles_x) { tx -= a.tiles_x; ++ty; }
+            ty += dty;
+            if (ty >= tiles_y) { ty -= tiles_y; ++n; }
+            n += dn;
+        };
+        auto walk = [&](auto easy_) {
+            for (int t = 0; t < n_mine; ++t) {
+                advance();                                  // (past the last tile too: loaded from, never committed)
+                const unsigned o_next = tile_origin(n, ty, tx), step = o_next - origin;
+                origin = o_next;
+#pragma unroll
+                for (int k = 0; k < CF_ITEMS; ++k) voff[k] += step;
+                CFTP(4 + 12 * t);
+                issue(Q0{}, st0);
+                CFTP(5 + 12 * t);
+                commit(easy_, Q1{}, 0u - step, st1);
+                CFTP(8 + 12 * t);
+                __syncthreads();      // (tile, half 1) is complete; the consumers have finished reading (tile, half 0)
+                CFTP(9 + 12 * t);
+                CFTP(10 + 12 * t);
+                issue(Q1{}, st1);
+                CFTP(11 + 12 * t);
+                tile_masks(tile_edges(ty, tx));
+                if (t + 1 < n_mine) commit(easy_, Q0{}, 0u, st0);
+                CFTP(14 + 12 * t);
+                __syncthreads();
+                CFTP(15 + 12 * t);
             }
         };
+        using T1 = std::integral_constant<int, 1>; using T0 = std::integral_constant<int, 0>;
+        // (prologues without a leaky ReLU have nothing that depends on EASY: one instantiation)
+        constexpr bool HAS_ACT = PRO == SISR_PRO_ACT || PRO == SISR_PRO_AFFINE_ACT || SUM;
 
-        issue(0, stA);
-        issue(1, stB);
+        origin = tile_origin(n, ty, tx);
+#pragma unroll
+        for (int k = 0; k < CF_ITEMS; ++k) voff[k] = origin + (unsigned)rel[k];
+        tile_masks(tile_edges(ty, tx));
+        issue(Q0{}, st0);
+        issue(Q1{}, st1);
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
@@ -318,28 +413,13 @@ __global__ void __launch_bounds__(CF_THREADS, 2) conv_trunk_f32_kernel(const CTr
             }
         fill_weights();
         __syncthreads();
-        if (n_stages > 0) commit(0, stA);
-        __syncthreads();
-        // unrolled by two: each set has a fixed name in each half (stB holds stage j + 1 in the first)
-        int j = 0;
-        while (j < n_stages) {
-            CFTP(4 + 6 * j);
-            issue(j + 2, stA);
-            CFTP(5 + 6 * j);
-            if (j + 1 < n_stages) commit(j + 1, stB);
-            CFTP(8 + 6 * j);
-            __syncthreads();      // stage j + 1 is complete; the consumers have finished reading stage j
-            CFTP(9 + 6 * j);
-            if (++j >= n_stages) break;
-            CFTP(4 + 6 * j);
-            issue(j + 2, stB);
-            CFTP(5 + 6 * j);
-            if (j + 1 < n_stages) commit(j + 1, stA);
-            CFTP(8 + 6 * j);
-            __syncthreads();
-            CFTP(9 + 6 * j);
-            ++j;
+        // the slope's range is decided once per launch: one instance of the walk each
+        const bool easy = !HAS_ACT || easy_slope;
+        if (n_mine > 0) {
+            if (easy) commit(T1{}, Q0{}, 0u, st0); else commit(T0{}, Q0{}, 0u, st0);
         }
+        __syncthreads();
+        if (easy) walk(T1{}); else walk(T0{});
     } else {
         // ---- consumers: wave w = tile rows 2 w, 2 w + 1 (32 pixels) x this workgroup's 32 couts -------------------------------
         // operand lane roles (sisr_dev.h; K order chosen here): A = x[pixel l31][ci = 16 kk + s], B = W[ci = 16 kk + s][co = l31];
