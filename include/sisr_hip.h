@@ -1084,6 +1084,44 @@ int sisr_percep_bwd(const float *fa, const float *fb, const float *dmat, const f
                     const float *layer_w, float perceptual_weight, float style_weight, int32_t crit, float *dfa, float *dfb,
                     void *stream);
 
+/* ---- contextual loss (Mechrez, Talmi, Zelnik-Manor, ECCV 2018), cosine form, over the taps of a feature vector, forward and backward
+ *      (DESIGN.md section 31).  fa (the generator side), fb (the target, a constant of the loss): fp32 [B][total], contiguous, taps and
+ *      shapes as sisr_percep_fwd takes them; X[n], Y[n] the C x P slices of a tap, column i the feature point x_i.  Per tap:
+ *          mu = the channel-wise mean of Y over batch and points      x^_i = (x_i - mu) / max(|x_i - mu|, 1e-12),  y^_j likewise
+ *          S_ij = x^_i . y^_j    d_ij = 1 - S_ij    m_i = min_j d_ij    w_ij = exp((1 - d_ij / (m_i + 1e-5)) / band_width)
+ *          Z_i = sum_j w_ij    CX_ij = w_ij / Z_i    c_j = max_i CX_ij    CX[n] = (1 / P) sum_j c_j
+ *          T_l = (1 / B) sum_n -log(CX[n] + 1e-5)      loss = weight sum_l w_l T_l
+ *      Ties of the min and of the max take the lowest index.  S runs on v_mfma_f32_32x32x2_f32 with K = C over the centred features, the
+ *      two 1 / norm factors scale the 32 x 32 tile in the epilogue; mu, the squared norms, Z, CX[n] and the terms are summed in double in
+ *      a fixed order.  No atomics, nothing read back by the host: the same bits on every call.  A NaN in gives a NaN term.
+ *      SISR_E_BADARG before any HIP call for null pointers, tables that are not 4-byte or a workspace that is not 16-byte aligned, B < 1,
+ *      n_taps outside 1 .. SISR_PERCEP_MAX_TAPS, a non-positive dim, a shape sum that is not total, a band_width that is not a finite
+ *      positive number, an unknown `which`; SISR_E_TOOBIG for a tap of more than SISR_CX_MAX_POINTS points (take a deeper tap or pool the
+ *      features). ------- */
+#define SISR_CX_MAX_POINTS 2304
+#define SISR_CX_WS_TABLES 0
+#define SISR_CX_WS_SIM 1
+#define SISR_CX_WS_FWD 2
+#define SISR_CX_WS_BWD 3
+/* HOST: bytes of TABLES: mu (sum_l C_l floats) and seven tables of B sum_l P_l elements, tap after tap as [B][P_l]: |x_i - mu|, |y_j - mu|,
+ * m, Z, c (floats), j*, i* (int32) -- what the backward needs beside the inputs and CX[n]; SIM: the taps' S [B][P_l][P_l] one after the
+ * other; FWD: one double per workgroup of the column pass, then S; BWD: S, then dloss / dx^ [B][total].  < 0: a status code */
+int64_t sisr_cx_ws_bytes(int32_t B, int32_t n_taps, const int32_t *shapes, int32_t which);
+/* sim: SIM floats, the bits the loss forms internally; tab: TABLES (mu and the two norm tables are written).  Three launches */
+int sisr_cx_sim(const float *fa, const float *fb, int32_t B, int64_t total, int32_t n_taps, const int32_t *shapes, void *tab, float *sim,
+                void *stream);
+/* layer_w: HOST array [n_taps].  tab: TABLES, all written; ws: FWD; terms: [n_taps] T_l or NULL; cx: [n_taps][B] CX[n]; loss: the scalar.
+ * Six launches, whatever B is */
+int sisr_cx_fwd(const float *fa, const float *fb, int32_t B, int64_t total, int32_t n_taps, const int32_t *shapes, const float *layer_w,
+                float band_width, float weight, void *tab, void *ws, float *terms, float *cx, float *loss, void *stream);
+/* tab, cx: as the forward left them; g: the upstream gradient of the scalar in DEVICE memory; ws: BWD; dfa: [B][total], every element
+ * stored once.  S is recomputed by the forward's kernel, a row pass turns it into -dloss / dd in place (r_i gathered from the i* table),
+ * dloss / dx^ = Y^ T^T runs on the same instruction with K = P, a thin launch applies the normalisation's projection (0 where
+ * |x_i - mu| < 1e-12).  Four launches.  There is no gradient for fb */
+int sisr_cx_bwd(const float *fa, const float *fb, const void *tab, const float *cx, const float *g, int32_t B, int64_t total,
+                int32_t n_taps, const int32_t *shapes, const float *layer_w, float band_width, float weight, void *ws, float *dfa,
+                void *stream);
+
 /* ---- image resize with torch's half-pixel coordinates, the mode chosen per sample, forward and backward.
  *      x [N][C][H][W] fp32, contiguous -> y [N][C][h][w], any h, w >= 1, up or down, any ratio.  modes [N] int32 in DEVICE memory, one
  *      per sample: the host never reads it, so a captured launch follows whatever the table holds at replay.  A value outside 0 .. 2

@@ -12,16 +12,17 @@ _FILTERS = ('gaussian_taps', 'gaussian_blur', 'usm_sharpen', 'USMSharp')      # 
 _RESIZE = ('resize', 'resize_taps', 'expected_resize_modes')                   # resize.py
 _ARTIFACT = ('artifact_map', 'artifact_loss')                                  # losses.py
 _PERCEP = ('gram_matrix', 'perceptual_loss', 'PerceptualLoss')                 # losses.py
+_CONTEXTUAL = ('contextual_loss', 'contextual_similarity', 'ContextualLoss')     # losses.py
 _NIQE = ('niqe', 'niqe_features', 'NiqeModel')                                 # metrics.py
 
 
 def __getattr__(name):
-    """the public names of ``filters`` and ``resize``, the artifact-aware and perceptual losses of ``losses`` and the no-reference score
+    """the public names of ``filters`` and ``resize``, the artifact-aware, perceptual and contextual losses of ``losses`` and the no-reference score
     of ``metrics`` under the package's own name, resolved on first use (importing the package stays light)"""
     if name in _FILTERS:
         import importlib
         return getattr(importlib.import_module('.filters', __name__), name)
-    if name in _ARTIFACT or name in _PERCEP:
+    if name in _ARTIFACT or name in _PERCEP or name in _CONTEXTUAL:
         import importlib
         return getattr(importlib.import_module('.losses', __name__), name)
     if name in _NIQE:

@@ -24,6 +24,8 @@ FREQ_MAX_SIDE = 256                          # SISR_FREQ_MAX_SIDE: the longest v
 ARTIFACT_MAX_K = 11                          # SISR_ARTIFACT_MAX_K: the largest window of sisr_artifact_fwd
 PERCEP_MAX_TAPS = 8                          # SISR_PERCEP_MAX_TAPS: the most taps sisr_percep_* take
 PERCEP_L1, PERCEP_L2, PERCEP_FRO = range(3)  # crit codes of sisr_percep_fwd / sisr_percep_bwd
+CX_MAX_POINTS = 2304                         # SISR_CX_MAX_POINTS: the most points (H W) of a tap sisr_cx_* take
+CX_WS_TABLES, CX_WS_SIM, CX_WS_FWD, CX_WS_BWD = range(4)    # `which` of sisr_cx_ws_bytes
 GAUSS_MAX_K = 63                             # SISR_GAUSS_MAX_K: the longest filter of sisr_gauss_blur_* / sisr_usm_fwd
 RESIZE_AREA, RESIZE_BILINEAR, RESIZE_BICUBIC = range(3)      # mode codes of sisr_resize_fwd / sisr_resize_bwd
 RESIZE_MAX_TAPS = 64                         # SISR_RESIZE_MAX_TAPS: the row length of sisr_resize_taps_host's table
@@ -282,6 +284,10 @@ _SIGS = {
     'sisr_percep_gram': [_f, _i32, _i64, _i32, C.POINTER(_i32), _f, _f, _f],
     'sisr_percep_fwd': [_f, _f, _i32, _i64, _i32, C.POINTER(_i32), C.POINTER(_f32), _f32, _f32, _i32, _f, _f, _f, _f, _f, _f, _f],
     'sisr_percep_bwd': [_f] * 7 + [_i32, _i64, _i32, C.POINTER(_i32), C.POINTER(_f32), _f32, _f32, _i32, _f, _f, _f],
+    'sisr_cx_ws_bytes': [_i32, _i32, C.POINTER(_i32), _i32],
+    'sisr_cx_sim': [_f, _f, _i32, _i64, _i32, C.POINTER(_i32), _f, _f, _f],
+    'sisr_cx_fwd': [_f, _f, _i32, _i64, _i32, C.POINTER(_i32), C.POINTER(_f32), _f32, _f32, _f, _f, _f, _f, _f, _f],
+    'sisr_cx_bwd': [_f] * 5 + [_i32, _i64, _i32, C.POINTER(_i32), C.POINTER(_f32), _f32, _f32, _f, _f, _f],
     'sisr_niqe_ws_bytes': [_i32] * 5,
     'sisr_niqe_features': [_f] + [_i32] * 5 + [_f32, _f32, _i32, _f, _f, _f, _f, _f],
     'sisr_niqe_score': [_f, _i32, _i32, _f, _f, _f, _f, _f],
@@ -336,6 +342,7 @@ def lib():
     L.sisr_weight_image_bytes.restype = C.c_int64
     L.sisr_usm_ws_bytes.restype = C.c_int64
     L.sisr_percep_ws_bytes.restype = C.c_int64
+    L.sisr_cx_ws_bytes.restype = C.c_int64
     L.sisr_niqe_ws_bytes.restype = C.c_int64
     L.sisr_version.restype = C.c_char_p
     L.sisr_version.argtypes = []

@@ -34,6 +34,12 @@ and the optional style term on the Gram matrices of the same taps, which run on 
 forward with both terms, one backward; saved are the inputs, the derivative ``D`` of the style term with respect to the Gram
 matrices and the per-tap terms.  ``gram_matrix`` is the Gram matrices alone; ``PerceptualLoss`` the module around an extractor.
 
+``contextual_loss`` (csrc/contextual.hip) is the contextual loss of Mechrez et al. (ECCV 2018) in its cosine form over the same taps: it
+compares every feature point of the generator's side with every point of the target's, so it matches the distribution of the
+target's features, not each position's.  The ``P x P`` similarity runs on the exact-fp32 matrix instruction and lives in a workspace;
+six launches forward, four backward; saved are the inputs and ``O(B P)`` tables.  ``contextual_similarity`` is the similarity alone;
+``ContextualLoss`` the module around an extractor.
+
 Nothing here synchronises with the host: losses and statistics are 0-dim fp32 device tensors, bit-identical from call to call,
 and the launches can be captured by ``graph.GraphedStep``.  Opt-in: ``install(fused_losses=True)`` points ``torch.nn.BCELoss`` at
 ``BCELoss``; a trainer rebinds its ``content_loss_g`` / ``adversarial_loss_*`` to the functions below.
@@ -610,6 +616,185 @@ class PerceptualLoss(torch.nn.Module):
         with torch.no_grad():
             fg = self._features(gt.detach())
         return perceptual_loss(fx, fg, shapes, self.layer_weights, self.perceptual_weight, self.style_weight, self.criterion)
+
+
+def _cx_check_taps(feat, shapes, what):
+    taps = _check_taps(feat, shapes, what)
+    if any(h * w > L.CX_MAX_POINTS for _, h, w in taps):
+        raise ValueError('%s: at most %d points (H * W) per tap, got %r: take a deeper tap or pool the features first'
+                         % (what, L.CX_MAX_POINTS, taps))
+    return taps
+
+
+def _cx_buffer(lib, b, taps, which, dev):
+    size = L.check_count(lib.sisr_cx_ws_bytes(b, len(taps), _tap_array(taps), which), 'sisr_cx_ws_bytes')
+    return torch.empty(max(size, 16) // 4, dtype=torch.float32, device=dev)
+
+
+def _cx_table_views(tab, b, taps):
+    """-> per tap a dict of views of the tables buffer: mu [C]; na, nb, m, Z, c (fp32) and jstar, istar (int32), each (B, P)"""
+    n_mu, n_pt = sum(c for c, _, _ in taps), b * sum(h * w for _, h, w in taps)
+    names = ('na', 'nb', 'm', 'Z', 'c', 'jstar', 'istar')
+    out, mu, pt = [], 0, 0
+    for c, h, w in taps:
+        p = h * w
+        d = {'mu': tab[mu:mu + c]}
+        for k, name in enumerate(names):
+            v = tab[n_mu + k * n_pt + pt:n_mu + k * n_pt + pt + b * p].view(b, p)
+            d[name] = v.view(torch.int32) if name in ('jstar', 'istar') else v
+        out.append(d)
+        mu, pt = mu + c, pt + b * p
+    return tuple(out)
+
+
+def _cx_forward(fa, fb, taps, lw, h, weight):
+    """the forward on contiguous detached tensors -> (loss, terms [n_taps], cx [n_taps, B], tables buffer); the P^2 workspace is
+    released on return"""
+    lib, dev, b = L.lib(), fa.device, fa.shape[0]
+    tab = _cx_buffer(lib, b, taps, L.CX_WS_TABLES, dev)
+    work = _cx_buffer(lib, b, taps, L.CX_WS_FWD, dev)
+    loss, terms = _scalar(dev), torch.empty(len(taps), dtype=torch.float32, device=dev)
+    cx = torch.empty((len(taps), b), dtype=torch.float32, device=dev)
+    L.check(lib.sisr_cx_fwd(fa.data_ptr(), fb.data_ptr(), b, fa.shape[1], len(taps), _tap_array(taps), (L._f32 * len(taps))(*lw), h,
+                            weight, tab.data_ptr(), work.data_ptr(), terms.data_ptr(), cx.data_ptr(), loss.data_ptr(), _stream()),
+            'sisr_cx_fwd')
+    return loss, terms, cx, tab
+
+
+class _Contextual(torch.autograd.Function):
+    """-> (loss, terms, cx); ``cfg`` = (taps, layer_weights, band_width, weight)"""
+
+    @staticmethod
+    def forward(ctx, fa, fb, cfg):
+        fa, fb = fa.detach().contiguous(), fb.detach().contiguous()
+        taps, lw, h, weight = cfg
+        loss, terms, cx, tab = _cx_forward(fa, fb, taps, lw, h, weight)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(fa, fb, tab, cx)                 # the inputs, the O(B P) tables with mu, CX[n]: nothing of size P^2
+        ctx.cfg = cfg
+        ctx.mark_non_differentiable(terms, cx)
+        return loss, terms, cx
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_terms, _g_cx):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        fa, fb, tab, cx = ctx.saved_tensors
+        taps, lw, h, weight = ctx.cfg
+        lib, dev, b = L.lib(), fa.device, fa.shape[0]
+        g = g.to(torch.float32).contiguous()
+        work = _cx_buffer(lib, b, taps, L.CX_WS_BWD, dev)
+        dfa = torch.empty_like(fa)
+        L.check(lib.sisr_cx_bwd(fa.data_ptr(), fb.data_ptr(), tab.data_ptr(), cx.data_ptr(), g.data_ptr(), b, fa.shape[1], len(taps),
+                                _tap_array(taps), (L._f32 * len(taps))(*lw), h, weight, work.data_ptr(), dfa.data_ptr(), _stream()),
+                'sisr_cx_bwd')
+        return dfa, None, None
+
+
+def _cx_args(fa, fb, shapes, layer_weights, band_width, weight, what):
+    """the argument errors of ``contextual_loss`` -> (taps, lw, h, weight)"""
+    _validate_pair(fa, fb, what)
+    taps = _cx_check_taps(fa, shapes, what)
+    if layer_weights is None:
+        layer_weights = (1.0,) * len(taps)
+    lw = tuple(float(v) for v in layer_weights)
+    if len(lw) != len(taps):
+        raise ValueError('%s: one layer weight per tap is expected, got %d for %d taps' % (what, len(lw), len(taps)))
+    h, weight = float(band_width), float(weight)
+    if not all(np.isfinite(v) for v in lw + (weight,)):
+        raise ValueError('%s: the weights must be finite, got %r, %r' % (what, lw, weight))
+    if not np.finfo(np.float32).tiny <= h <= np.finfo(np.float32).max:      # (a NaN fails both comparisons)
+        raise ValueError('%s: band_width is a finite positive fp32 number, got %r' % (what, band_width))
+    return taps, lw, h, weight
+
+
+def contextual_loss(fa, fb, shapes, layer_weights=None, band_width=0.5, weight=1.0, return_terms=False):
+    """The contextual loss of Mechrez, Talmi and Zelnik-Manor (ECCV 2018) in its cosine form on two fp32 (B, total) device feature
+    tensors in the layout of ``MaskedVGG.forward``; ``shapes``: the taps' ``(C, H, W)`` as ``perceptual_loss`` takes them, at most 8,
+    each with ``P = H W <= 2304`` points (conv2_2 at HR 96^2, conv3_4 at HR 192^2; above that take a deeper tap or pool the features).
+    ``fa`` is the generator side, ``fb`` the target; the roles are not symmetric.  Per tap and sample, with ``x_i`` / ``y_j`` the
+    feature points (columns of the C x P slices), ``mu`` the channel-wise mean of the TARGET over batch and points and ``h =
+    band_width``:
+
+    ``S_ij = cos(x_i - mu, y_j - mu)`` (norms clamped at 1e-12), ``d = 1 - S``, ``w_ij = exp((1 - d_ij / (min_j d_ij + 1e-5)) / h)``,
+    ``CX_ij = w_ij / sum_j w_ij``, ``CX[n] = mean_j max_i CX_ij``, ``loss = weight * sum_l w_l * mean_n -log(CX[n] + 1e-5)``.
+
+    -> a 0-dim fp32 device tensor; with ``return_terms`` also the detached ``[n_taps]`` per-tap terms and the ``[n_taps, B]`` table of
+    ``CX[n]``.  Differentiable with respect to ``fa`` only, once: ``fb`` is a constant of the loss (detached, as ``ema`` is in
+    ``artifact_loss``) and gets no gradient.  Ties of the min and of the max take the lowest index.  ``P = 1`` gives ``CX = 1`` and a
+    zero gradient; when ``fa`` is close to ``fb`` the loss saturates at ``-log(1 + 1e-5)`` and the gradient underflows to 0 -- the
+    definition's behaviour, not an error; a NaN in gives a NaN term.  Six launches forward, four backward, none depending on B; saved
+    are the inputs, the O(B P) tables and ``CX[n]`` -- the ``B P^2`` similarity lives in a workspace that is released after each pass
+    and is recomputed in the backward.  Non-contiguous inputs are made contiguous first; a bf16 caller casts."""
+    what = 'contextual_loss'
+    cfg = _cx_args(fa, fb, shapes, layer_weights, band_width, weight, what)
+    require_gpu_tensor(fa, 'contextual_loss input fa')
+    require_gpu_tensor(fb, 'contextual_loss input fb')
+    out = _Contextual.apply(fa, fb, cfg)
+    return out if return_terms else out[0]
+
+
+def contextual_similarity(fa, fb, shapes):
+    """The cosine similarities ``S_ij`` of ``contextual_loss`` for every tap of two fp32 (B, total) device feature tensors -> a tuple
+    of detached (B, P, P) tensors (row ``i``: a point of ``fa``, column ``j``: a point of ``fb``), the same bits the loss forms
+    internally; no graph is recorded.  Three launches for all taps and samples."""
+    what = 'contextual_similarity'
+    _validate_pair(fa, fb, what)
+    taps = _cx_check_taps(fa, shapes, what)
+    require_gpu_tensor(fa, 'contextual_similarity input fa')
+    require_gpu_tensor(fb, 'contextual_similarity input fb')
+    with torch.no_grad():
+        fa, fb = fa.detach().contiguous(), fb.detach().contiguous()
+        lib, dev, b = L.lib(), fa.device, fa.shape[0]
+        tab = _cx_buffer(lib, b, taps, L.CX_WS_TABLES, dev)
+        out = _cx_buffer(lib, b, taps, L.CX_WS_SIM, dev)
+        L.check(lib.sisr_cx_sim(fa.data_ptr(), fb.data_ptr(), b, fa.shape[1], len(taps), _tap_array(taps), tab.data_ptr(),
+                                out.data_ptr(), _stream()), 'sisr_cx_sim')
+        sims, off = [], 0
+        for _, h, w in taps:
+            p = h * w
+            sims.append(out[off:off + b * p * p].view(b, p, p))
+            off += b * p * p
+        return tuple(sims)
+
+
+def _contextual_tables(fa, fb, shapes, band_width=0.5):
+    """The tables the forward leaves for the backward, for the tests -> per tap a dict (``_cx_table_views``)"""
+    taps, lw, h, weight = _cx_args(fa, fb, shapes, None, band_width, 1.0, 'contextual tables')
+    require_gpu_tensor(fa, 'contextual tables input fa')
+    with torch.no_grad():
+        tab = _cx_forward(fa.detach().contiguous(), fb.detach().contiguous(), taps, lw, h, weight)[3]
+    return _cx_table_views(tab, fa.shape[0], taps)
+
+
+class ContextualLoss(torch.nn.Module):
+    """``contextual_loss`` around a content extractor of ``model_content_extractor``, beside ``PerceptualLoss``: ``forward(x, gt)`` ->
+    the loss on the extractor's features, the tap shapes taken from ``tap_shapes``.  ``gt``'s features are computed under ``no_grad``
+    and are a constant of the loss.  ``range_norm`` / ``input_norm`` as in ``PerceptualLoss``.  A setting for HR 96^2 patches:
+    ``MaskedVGG(0b01100)`` (conv3_4 and conv4_4: 576 and 144 points)."""
+
+    def __init__(self, extractor, layer_weights=None, band_width=0.5, weight=1.0, input_norm=False, range_norm=False):
+        super().__init__()
+        h = float(band_width)
+        if not np.finfo(np.float32).tiny <= h <= np.finfo(np.float32).max:
+            raise ValueError('ContextualLoss: band_width is a finite positive fp32 number, got %r' % (band_width,))
+        self.extractor = extractor
+        self.layer_weights = None if layer_weights is None else tuple(float(v) for v in layer_weights)
+        self.band_width, self.weight = h, float(weight)
+        self.input_norm, self.range_norm = bool(input_norm), bool(range_norm)
+        self.register_buffer('mean', torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1), persistent=False)
+        self.register_buffer('std', torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1), persistent=False)
+
+    _features = PerceptualLoss._features
+
+    def forward(self, x, gt):
+        from .model_content_extractor import tap_shapes
+        shapes = tap_shapes(self.extractor, x.shape[2], x.shape[3])
+        fx = self._features(x)
+        with torch.no_grad():
+            fg = self._features(gt.detach())
+        return contextual_loss(fx, fg, shapes, self.layer_weights, self.band_width, self.weight)
 
 
 class _BCE(torch.autograd.Function):
