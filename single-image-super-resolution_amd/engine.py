@@ -1380,8 +1380,9 @@ def fc_backward(dy, x, w, in_slope=1.0, need_dx=True):
 
 
 def fc_head_ok(bsz, k, n):
-    """the classifier head of D runs on fc_head.hip (exact-fp32 MFMA weight streaming): up to 16 batch rows, K in 64s, N in 128s"""
-    return bsz <= FC_MAX_BATCH and k % 64 == 0 and n % 128 == 0
+    """the classifier head of D runs on fc_head.hip (exact-fp32 MFMA weight streaming): 1 to 16 batch rows, K in 64s, N in 128s
+    (what sisr_fc1_dgrad takes; the forward alone takes K and N in 16s, the backward any N).  Empty shapes are refused there too."""
+    return 0 < bsz <= FC_MAX_BATCH and k > 0 and k % 64 == 0 and n > 0 and n % 128 == 0
 
 
 def fc_head_forward(x, w1, b1, w2, b2, slope):
@@ -1421,7 +1422,7 @@ def fc1_dgrad(d1, w1):
 
 def fc_wgrad_rows_ok(rows, k, n):
     """sisr_fc_wgrad_rows takes the gathered factors of `rows` batch rows (all ranks)"""
-    return rows <= 256 and k % 128 == 0 and n % 64 == 0
+    return 0 < rows <= 256 and k > 0 and k % 128 == 0 and n > 0 and n % 64 == 0
 
 
 def fc_wgrad_rows(dy_all, x_all, w, scale):

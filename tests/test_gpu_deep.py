@@ -227,6 +227,7 @@ def test_full_size_layers_forward_and_data_gradient(E, L, case):
 
 
 # ---- the classifier head (csrc/fc_head.hip; model_discriminator.py:47-53) -----------------------------------------------------
+# (the workload's shapes against the max-norm; exact operands, edge shapes and element bounds: tests/test_gpu_fc_head.py)
 @pytest.mark.parametrize('shape', [(16, 18432, 1024), (5, 2048, 256), (16, 73728, 1024)])
 def test_classifier_head_forward_backward(L, shape):
     """Linear(K, N) -> LeakyReLU -> Linear(N, 1) -> Sigmoid through fc_head.hip against torch autograd in double (exact-fp32
